@@ -21,8 +21,14 @@ Wilson kernels (channel-pairs/s), cfg5 canonical coherence of 16 groups (bin*gro
 `roofline` and `cpu_baseline`.
 
 Prints ONE JSON line on rank 0 (see the driver contract), with `roofline` for the dominant
-kernel (durations from HIP events on the launch stream) and `cpu_baseline` (the NumPy
-oracle's faithful per-observation path, single core, on a bounded sample).
+kernel (durations from HIP events on the launch stream, taken in the timed steps themselves).
+
+A plain run (`python bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the line: nothing
+else.  `--full` adds what is measured beside the headline, after the timed region: `cpu_baseline` (the NumPy oracle's faithful
+per-observation path, single core, on a bounded sample) and the restructured CPU path, the float64 engine, the chain check, the
+public-API and end-to-end passes, and the other BASELINE configurations (`side_configs`).  `--dump-outputs DIR` writes what the
+timed path returned in its last step as DIR/<name>.npy (see dump_outputs: the channel pairs i != j, off_diagonal); the inputs
+are seeded, the same in every run.
 """
 import argparse
 from ctypes import byref, c_double
@@ -89,6 +95,49 @@ CONFIGS = {
                        "between 16 groups of 16 channels (513 bins x 120 group pairs, fp64)"),
 }
 FS = 1000.0
+DUMP_BYTES = 64_000_000      # --dump-outputs: at most this many bytes of .npy files in all
+PAIRS_SELECTION = "bench.off_diagonal: the pairs i != j of the [..., C, C] result, row-major"
+
+
+def dump_positions(size, keep):
+    """The flat positions --dump-outputs writes of an output with ``size`` entries when it keeps ``keep`` of them: seeded, sorted."""
+    return np.sort(np.random.default_rng(1234).choice(size, keep, replace=False))
+
+
+def off_diagonal(t):
+    """[..., C, C] -> [..., C (C - 1)]: the entries of the channel (or group) pairs i != j, row-major.  What --dump-outputs writes of
+    a pairwise measure: the diagonal pairs a signal with itself, where coherence, canonical coherence and Granger prediction are
+    NaN by definition (the reference's convention) -- no value to compare."""
+    keep = ~torch.eye(t.shape[-1], dtype=torch.bool, device=t.device)
+    return t[..., keep]
+
+
+def dump_outputs(out_dir, outputs, selection=None):
+    """--dump-outputs: what the timed path returned in its last step, one ``out_dir/<name>.npy`` per output (float32 stays float32,
+    float64 stays float64, a complex output gets a trailing (re, im) axis).  When the outputs together exceed DUMP_BYTES, each is
+    written as the same share of its entries, flattened, at seeded positions (sorted flat indices that depend only on the output's
+    size): the same entries in every run, so that two builds compare output for output.  ``selection`` says which entries of the
+    result the outputs are (recorded with them).  Returns what was written."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in outputs.items():
+        a = t.cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        if np.iscomplexobj(a):
+            a = np.stack([a.real, a.imag], axis=-1)
+        host[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+    total = sum(a.nbytes for a in host.values())
+    room = DUMP_BYTES - 4096 * len(host)                     # (the .npy headers)
+    info = {}
+    for name, a in host.items():
+        if total > room:
+            keep = a.size * room // total
+            np.save(os.path.join(out_dir, name + ".npy"), a.reshape(-1)[dump_positions(a.size, keep)])
+        else:
+            keep = a.size
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+        info[name] = {"shape": list(a.shape), "dtype": str(a.dtype), "entries_written": int(keep), "selection": selection,
+                      "sample": "flat positions bench.dump_positions(size, entries_written)" if keep < a.size else None}
+    return info
 
 
 def synth(cfg, r_lo, r_hi, device, seed):
@@ -263,12 +312,12 @@ def run_side_config(args, cfg, device):
         return out
 
     for _ in range(args.warmup):
-        one()
+        out = one()
     torch.cuda.synchronize()
     _lib.timing_enable(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one()
+        out = one()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     timing = _lib.last_timing()
@@ -295,19 +344,24 @@ def run_side_config(args, cfg, device):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 for _ in range(args.steps):
-                    g()
+                    out_g, = g()
                 torch.cuda.synchronize()
                 g_ms = (time.perf_counter() - t0) / args.steps * 1e3
                 launch = {"mode": "engine.GraphedMeasures: hipGraph replay of the pass (stage A, stage B, epilogue captured once by the library); "
                                   "bit-identical to the eager pass",
                           "eager_ms_per_step": round(ms_per_step, 5), "graph_ms_per_step": round(g_ms, 5)}
                 if g_ms < ms_per_step:
-                    ms_per_step, elapsed = g_ms, g_ms * args.steps * 1e-3
+                    ms_per_step, elapsed, out = g_ms, g_ms * args.steps * 1e-3, out_g
             else:
                 launch = {"mode": "eager", "graph": "replay differed from the eager pass: not used"}
         except Exception as exc:                     # capture refused (an allocation or a synchronisation inside the pass): stay eager
             launch = {"mode": "eager", "graph": "capture failed: " + str(exc).splitlines()[0][:160]}
             torch.cuda.synchronize()
+    dumped = None
+    if args.dump_outputs:
+        name = {"coherency": "coherency", "granger": "pairwise_spectral_granger_prediction"}.get(kind, "canonical_coherence")
+        dumped = dump_outputs(args.dump_outputs, {name: off_diagonal(out)}, selection=PAIRS_SELECTION)
+    del out
 
     tri_flops = 8.0 * n_obs_loc * (C * (C + 1) / 2) * W * F
     iters = info.get("wilson", (0, 0, 0))[0]
@@ -408,7 +462,7 @@ def run_side_config(args, cfg, device):
         "config": {"workload": cfg["label"], "name": args.config, "trials_total": R, "n_tapers": K, "n_windows": W,
                    "n_freq_bins": F, "units_per_step": units,
                    **({"wilson_iterations": iters, "wilson_not_converged": info["wilson"][1]} if kind == "granger" else {})},
-        "roofline": roofline, "launch": launch, "cpu_baseline": cpu})
+        "roofline": roofline, "launch": launch, "cpu_baseline": cpu, **({"dump_outputs": dumped} if dumped else {})})
 
 
 def side_configs(args, device):
@@ -419,7 +473,7 @@ def side_configs(args, device):
     out = {}
     for name in ("cfg2", "cfg4", "cfg5"):
         a = copy.copy(args)
-        a.config, a.steps, a.warmup = name, 10, 3
+        a.config, a.steps, a.warmup, a.dump_outputs = name, 10, 3, None
         try:
             t0 = time.perf_counter()
             line = run_side_config(a, dict(CONFIGS[name]), device)
@@ -461,13 +515,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="cfg3", choices=sorted(CONFIGS))
     ap.add_argument("--trials", type=int, default=None, help="override total trial count (debug)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-f64", action="store_true", help="skip the float64-engine side measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what stands beside the headline, after the timed region: CPU baselines, the float64 engine, "
+                         "the chain check, the public-API and end-to-end passes, the other configurations (side_configs); "
+                         "--config cfgN: its CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy: the channel pairs i != j (the "
+                         "diagonal is NaN by definition), float32 / float64, at most 64 MB in all (a fixed seeded sample of larger "
+                         "outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-f64", action="store_true", help="with --full: skip the float64-engine side measurement")
     ap.add_argument("--timed-only", action="store_true",
                     help="nothing but the warm-up and the timed steps (no CPU baselines, float64 engine, end-to-end / API / chain-check "
-                         "passes): the command the rocprofv3 summaries under profiles/ are taken from, so that their per-kernel "
-                         "averages are averages over the steps the line reports")
+                         "passes), also with --full; what a run without --full does: the command the rocprofv3 summaries under "
+                         "profiles/ are taken from, so that their per-kernel averages are averages over the steps the line reports")
     args = ap.parse_args()
+    if not args.full:
+        args.timed_only = True
     if args.timed_only:
         args.no_cpu_baseline = args.no_f64 = True
 
@@ -522,7 +586,7 @@ def main():
             torch.cuda.synchronize()
 
     for _ in range(args.warmup):
-        one_step(x, h, cfg, geom, planes, world)
+        out = one_step(x, h, cfg, geom, planes, world)
     sync()
     _lib.timing_enable(True)                  # hipEvent pairs inside the library from here on (sc_timing.hip)
     exchange = [] if world > 1 else None
@@ -530,7 +594,7 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
-        one_step(x, h, cfg, geom, planes, world, exchange)
+        out = one_step(x, h, cfg, geom, planes, world, exchange)       # (coherence, wPLI); None on ranks other than 0
         marks[i + 1].record()
     sync()
     elapsed = time.perf_counter() - t0
@@ -545,6 +609,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, {"coherence_magnitude": off_diagonal(out[0]),
+                                                  "weighted_phase_lag_index": off_diagonal(out[1])}, selection=PAIRS_SELECTION)
+    del out
     units = W * F * C * C                                   # channel-pair x frequency bins
     value = units / (elapsed / args.steps)
 
@@ -774,6 +843,7 @@ def main():
                 # what the measured numbers should be judged against: bytes per xGMI link and their time at the assumed link rate
                 "model": parallel.exchange_model(4.0 * W * F * 3 * 256 * (((C + 15) // 16) * ((C + 15) // 16 + 1) // 2),   # 3 record planes
                                                  2 * 4.0 * W * F * C * C, world)},
+            **({"dump_outputs": dumped} if dumped else {}),
         }))
     if world > 1:
         dist.destroy_process_group()

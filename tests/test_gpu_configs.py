@@ -273,6 +273,50 @@ def test_bench_self_launches_its_ranks():
     assert rec["n_gpus"] == 2 and rec["exchange"] is not None and rec["value"] > 0
 
 
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """A plain `python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR` times exactly 3 steps, measures nothing
+    beside them (that is --full), and writes the coherence and wPLI of its last step -- the channel pairs i != j, all finite, a
+    seeded sample under 64 MB -- equal
+    bit for bit to the same chain on the same seeded input run here."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import torch
+    import bench
+    from spectral_connectivity_amd import _lib
+    from spectral_connectivity_amd.transforms import _make_tapers
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SC_BENCH_BACKEND")}
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--trials", "64", "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["value"] > 0
+    for extra in ("cpu_baseline", "cpu_baseline_restructured", "float64_engine", "api", "chain_check", "e2e_ms", "side_configs"):
+        assert rec[extra] is None, extra
+    names = ["coherence_magnitude", "weighted_phase_lag_index"]
+    assert sorted(os.listdir(tmp_path)) == [n + ".npy" for n in names]
+    assert sum(os.path.getsize(tmp_path / (n + ".npy")) for n in names) <= 64_000_000
+
+    cfg = dict(bench.CONFIGS["cfg3"], R=64)
+    L, step, T = cfg["L"], cfg["step"], cfg["T"]
+    W = int(np.floor(T / step - L / step + 1))
+    tapers = _make_tapers(L, bench.FS, cfg["NW"], int(np.floor(2 * cfg["NW"] - 1)))
+    h = torch.from_numpy(np.ascontiguousarray(tapers.T / bench.FS, dtype=np.float32)).cuda()
+    x = bench.synth(cfg, 0, 64, torch.device("cuda", 0), seed=3)
+    mine = bench.one_step(x, h, cfg, (L, step, L, W), _lib.PLANE_CSM | _lib.PLANE_ABS_IM, 1)
+    for name, t in zip(names, mine):
+        a = bench.off_diagonal(t).cpu().numpy()                     # the channel pairs i != j: the diagonal is NaN by definition
+        got = np.load(tmp_path / (name + ".npy"))
+        assert got.dtype == np.float32 and rec["dump_outputs"][name]["shape"] == list(a.shape) == [t.shape[0], 128 * 127]
+        assert np.isfinite(got).all(), f"{name}: {int((~np.isfinite(got)).sum())} entries not finite"
+        want = a.reshape(-1)[bench.dump_positions(a.size, got.size)] if got.size < a.size else a
+        np.testing.assert_array_equal(got, want, err_msg=name)
+
+
 def test_hot_kernels_are_bit_reproducible():
     """Stage A and stage B (split bins, L2-atomic folds, direct HBM->LDS row loads, one LDS-only barrier per chunk)
     repeat bit-exactly: every sum has one writer and a fixed order, and a race would show up here."""

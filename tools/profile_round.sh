@@ -1,7 +1,7 @@
 #!/bin/bash
 # Profile collection of a round (ROUND=r03 by default; run on the GPU box from the repo root; raw outputs under gpurun_out/$ROUND/, summaries are
 # written into profiles/ by tools/profile_round.py afterwards):
-#   1. the bench line itself                                 python bench.py
+#   1. the bench line itself                                 python bench.py --full
 #   2. per-kernel durations of the same command              rocprofv3 --kernel-trace --stats
 #   3. HBM traffic, two separate PMC passes                  rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE
 #   4. SQ counters of the dominant kernel                    rocprofv3 --kernel-trace --pmc SQ_...
@@ -12,7 +12,7 @@ ROUND=${ROUND:-r06}
 OUT=$ROOT/gpurun_out/$ROUND
 mkdir -p $OUT
 cd $ROOT
-python bench.py --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench_line.err
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench_line.err
 cd /tmp && export TMPDIR=/tmp
 BENCH="python $ROOT/bench.py --steps 40 --warmup 2 --timed-only"
 rocprofv3 --kernel-trace --stats -d $OUT/kt -- $BENCH > $OUT/bench_under_rocprof.json 2> $OUT/kt.err
@@ -40,7 +40,7 @@ fi
 python tools/shape_sweep.py > $OUT/shape_sweep.txt 2>&1
 MIX_GEOS=0,1 python tools/stage_a_mixed.py time > $OUT/stage_a_mixed.txt 2>&1
 python tools/e2e_lengths.py 256 250 200 500 1000 1024 > $OUT/e2e_lengths.txt 2>&1
-for c in cfg2 cfg4 cfg5; do python bench.py --config $c --steps 10 --warmup 3 > $OUT/bench_$c.json 2> $OUT/bench_$c.err; done
+for c in cfg2 cfg4 cfg5; do python bench.py --full --config $c --steps 10 --warmup 3 > $OUT/bench_$c.json 2> $OUT/bench_$c.err; done
 python tools/api_timeline.py > $OUT/api_timeline.txt 2>&1
 bash tools/sharded_one_rank.sh > $OUT/sharded_one_rank.txt 2>&1
 if [ "${FULL:-0}" = "1" ]; then
