@@ -64,7 +64,7 @@
 extern "C" {
 #endif
 
-#define SC_ABI_VERSION 6
+#define SC_ABI_VERSION 7
 
 /* error codes */
 #define SC_OK 0
@@ -474,6 +474,32 @@ int sc_mvar_factor_f64(const void* d_accum, const void* d_S /*complex128*/, int6
                        int32_t* h_summary, void* stream);
 int sc_mvar_measure_f64(const void* d_G /*complex128*/, int64_t n_groups, int64_t N, int64_t n_signals,
                         int which, void* d_out, void* d_work, size_t work_bytes, void* stream);
+
+/* ---- conditional spectral Granger prediction (ABI v7, fp64) --------------------------------
+ * j -> i given every other signal (Geweke 1984; Ding, Chen & Bressler 2006, section 3.3); the reference raises
+ * NotImplementedError (connectivity.py:1215-1224).  Needs the full factor d_G of sc_mvar_factor_f64 (complex128
+ * [n_groups][N][C][C]) and factors, for every dropped signal j of d_dropped (int32 [n_dropped]), the spectrum with row and
+ * column j removed by the same Wilson iteration (sc_mvar_factor_f64 on n_dropped * n_groups problems of C - 1 signals;
+ * problem d * n_groups + g).  With Psi0 = Re mean_n Psi, Sigma = Psi0 Psi0^T and Phi0 / Sigma^r those of the reduced factor Phi:
+ *     out[g][f][i][j] = ln(Sigma^r[i][i] Sigma[i][i] / |v_i(f)|^2),  v = Phi0 Phi(f)^-1 (Psi(f) Psi0^T)[rows != j, col i]
+ * at the row of i in the reduced system, for every i != j; non-positive values are NaN.
+ *   d_accum / d_S  exactly one: the records sc_mvar_factor_f64 takes (SC_PLANE_CSM, N or N/2+1 bins per group) or
+ *                  complex128 [n_groups][N][C][C] two-sided Hermitian spectra
+ *   d_out          double [n_groups][N/2+1][C][C]; NaN-filled first (diagonal, columns not dropped) unless flags has
+ *                  SC_CONDITIONAL_KEEP_OUTPUT (the caller walks the dropped signals in chunks that share one output)
+ *   d_n_iter, d_status  int32 [n_dropped * n_groups]: Wilson iterations / 1 converged, 0 hit max_iterations, per reduced problem
+ *   h_summary      optional HOST int32[3] {iterations run, reduced problems not converged, identity starts}, as sc_mvar_factor_f64
+ * n_dropped * n_groups <= 65535.  Workspace: sc_conditional_granger_workspace_bytes(n_groups, C, N, n_dropped): the reduced
+ * spectra and factors (two complex128 arrays [n_dropped * n_groups][N][C-1][C-1]), the larger of the reduced factorisation's
+ * workspace and the epilogue's two such arrays, and complex128 [n_groups][N/2+1][C][C].
+ * 2 <= n_signals <= sc_mvar_max_signals(), otherwise SC_EUNSUPPORTED.  Synchronises the stream (as sc_mvar_factor_f64). */
+#define SC_CONDITIONAL_KEEP_OUTPUT 1
+int sc_conditional_granger_workspace_bytes(int64_t n_groups, int64_t n_signals, int64_t N, int64_t n_dropped, size_t* bytes);
+int sc_conditional_granger_f64(const void* d_accum, const void* d_S /*complex128*/, int64_t n_groups, int64_t n_freq_accum,
+                               int64_t N, int64_t n_signals, uint32_t planes, int64_t n_observations,
+                               const void* d_G /*complex128*/, const int32_t* d_dropped, int64_t n_dropped, double tolerance,
+                               int max_iterations, void* d_work, size_t work_bytes, int flags, double* d_out,
+                               int32_t* d_n_iter, int32_t* d_status, int32_t* h_summary, void* stream);
 
 /* ---- global coherence (fp64, from the accumulated CSM) --------------------------------------
  * Replaces Connectivity.global_coherence / _estimate_global_coherence (connectivity.py:822-895,

@@ -21,8 +21,9 @@ from . import _build
 c_int64_p = POINTER(c_int64)
 
 # ---- constants mirrored from include/sc_hip.h -------------------------------------------
-SC_ABI_VERSION = 6
+SC_ABI_VERSION = 7
 GRANGER_KEEP_OUTPUT = 1
+CONDITIONAL_KEEP_OUTPUT = 1
 DETREND = {None: 0, "constant": 1, "c": 1, "linear": 2, "l": 2}
 MVAR_DTF, MVAR_DC, MVAR_PDC, MVAR_GPDC, MVAR_DDTF, MVAR_TRANSFER, MVAR_COEFFICIENTS, MVAR_NOISE_COVARIANCE = range(8)
 PLANE_CSM, PLANE_ABS_IM, PLANE_IM_SQ, PLANE_SIGN_IM, PLANE_UNIT = 0x01, 0x02, 0x04, 0x08, 0x10
@@ -150,6 +151,10 @@ SYMBOLS = {
                                    POINTER(c_int32), c_void_p]),
     "sc_mvar_measure_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_size_t,
                                     c_void_p]),
+    "sc_conditional_granger_workspace_bytes": (c_int, [c_int64, c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    "sc_conditional_granger_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_uint32, c_int64,
+                                           c_void_p, c_void_p, c_int64, c_double, c_int, c_void_p, c_size_t, c_int,
+                                           c_void_p, c_void_p, c_void_p, POINTER(c_int32), c_void_p]),
     "sc_global_coherence_max_signals": (c_int, []),
     "sc_global_coherence_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_uint32, c_int64, c_int, c_int,
                                         c_void_p, c_void_p, c_void_p]),
@@ -180,6 +185,18 @@ _bound_with_torch = None        # True / False once the library is loaded: which
 
 class HipEngineError(RuntimeError):
     """A libsc_hip.so entry point returned a negative status."""
+
+
+CONDITIONAL_WORK_BYTES = 4 << 30    # workspace bound of one sc_conditional_granger_f64 call (the dropped signals go in chunks)
+
+
+def conditional_chunk(n_groups, n_signals, workspace_bytes, cap=None):
+    """Dropped signals per sc_conditional_granger_f64 call (both hosts): as many as keep the workspace under ``cap`` -- at least
+    one, at most n_signals and at most 65535 reduced problems.  ``workspace_bytes(n_dropped)``: the library's query."""
+    cap = CONDITIONAL_WORK_BYTES if cap is None else cap
+    one = workspace_bytes(1)
+    per = max(1, workspace_bytes(2) - one)
+    return int(max(1, min(n_signals, 65535 // n_groups, (cap - (one - per)) // per)))
 
 
 def library_path():

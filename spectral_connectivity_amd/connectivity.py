@@ -455,15 +455,19 @@ class Connectivity:
     # ---- full Wilson factor and the directed MVAR measures (reference connectivity.py:567-589,
     # :1237-1426): one batched C x C factorisation on the device, cached, then one small kernel
     # per measure ------------------------------------------------------------------------------
+    def _check_mvar_signals(self):
+        C = self._shape5[4]
+        if C > _lib.load().sc_mvar_max_signals():
+            raise ValueError(f"the full Wilson factorisation supports n_signals <= "
+                             f"{_lib.load().sc_mvar_max_signals()} (got {C}); use the pairwise measures")
+
     def _mvar_factor_device(self):
         from . import engine
         if getattr(self, "_mvar_G", None) is not None:
             return self._mvar_G
         sp = self._device()
         N, C = self._shape5[3], self._shape5[4]
-        if C > _lib.load().sc_mvar_max_signals():
-            raise ValueError(f"the full Wilson factorisation supports n_signals <= "
-                             f"{_lib.load().sc_mvar_max_signals()} (got {C}); use the pairwise measures")
+        self._check_mvar_signals()
         planes = _lib.PLANE_CSM
         accum, n_obs, n_freq = self._csm_records("granger")
         n_groups = accum.shape[0] // n_freq
@@ -627,7 +631,29 @@ class Connectivity:
         return part
 
     def conditional_spectral_granger_prediction(self):
-        raise NotImplementedError   # reference connectivity.py:1215-1224 raises too
+        """Power at node i explained by node j given every other signal, out[..., i, j] = j -> i | rest (diagonal NaN;
+        Geweke 1984, Ding, Chen & Bressler 2006 section 3.3 -- the reference raises NotImplementedError,
+        connectivity.py:1215-1224).  The full factor is the cached one of the MVAR measures; one reduced Wilson
+        factorisation per dropped signal runs on the device (sc_conditional.hip).  With two signals this is the pairwise
+        measure.  ``_last_wilson`` then describes the reduced factorisations (n_iter / status [n_signals, n_groups])."""
+        from . import engine
+        N, C = self._shape5[3], self._shape5[4]
+        self._check_mvar_signals()
+        G = self._mvar_factor_device()
+        accum, n_obs, n_freq = self._csm_records("granger")
+        n_groups = accum.shape[0] // n_freq
+        out, n_iter, status, (iters, not_conv, fallback) = engine.conditional_granger(
+            G, n_groups, N, C, accum=accum, n_freq_accum=n_freq, planes=_lib.PLANE_CSM,
+            n_obs=self._n_observations_total(n_obs))
+        st = status.cpu().numpy()
+        if fallback:
+            logger.warning("Computing the initial conditions using the Cholesky failed. "
+                           f"Using the identity as initial condition ({fallback} reduced problems).")
+        if not_conv:
+            logger.warning(f"Maximum iterations reached. {st.size - not_conv} of {st.size} converged")
+        self._last_wilson = dict(iterations=iters, not_converged=not_conv, cholesky_fallbacks=fallback,
+                                 n_iter=n_iter.cpu().numpy(), status=st)
+        return engine.to_host(out).reshape(self._kept_shape() + (N // 2 + 1, C, C))
 
     def blockwise_spectral_granger_prediction(self):
         raise NotImplementedError   # reference connectivity.py:1226-1235 raises too

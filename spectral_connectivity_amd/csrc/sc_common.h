@@ -57,6 +57,13 @@ int sc_internal_granger_resident(const void* d_accum, int64_t n_groups, int64_t 
                                  int keep_output, double* d_out, int32_t* d_n_iter, int32_t* d_status, int32_t* h_summary,
                                  hipStream_t st);
 
+// sc_mvar.hip: the explicit inverse and the matrix-core product of the full Wilson factorisation on caller buffers
+// (natural-layout C x C complex128 matrices; see there)
+int sc_internal_mvar_inverse(int64_t C, int64_t P, int64_t N, int64_t n_bins, const void* d_M, void* d_out, void* scratch,
+                             const double* d_zero, hipStream_t st);
+int sc_internal_mvar_gemm(int64_t C, int64_t n_problems, int64_t n_bins, const void* X, int64_t x_sp, int64_t x_sn,
+                          const void* Y, int64_t y_sp, int64_t y_sn, void* O, int64_t o_sp, int64_t o_sn, hipStream_t st);
+
 // sc_timing.hip: brackets the launches of an entry point with two hipEvents on its stream while sc_timing_enable(1)
 struct ScTimed {
     int slot;

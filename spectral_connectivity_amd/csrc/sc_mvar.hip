@@ -1797,3 +1797,36 @@ extern "C" int sc_mvar_measure_f64(const void* d_G, int64_t n_groups, int64_t N,
     }
     return SC_OK;
 }
+
+// ---- the inverse and product launchers above on caller buffers (sc_conditional.hip: conditional Granger's epilogue) ----
+// Out[p][n] = M[p][n]^-1 for the bins n < n_bins of natural-layout C x C matrices (element e = i C + j of problem p, bin n
+// at p N E + n E + e).  Up to 64 signals the register-resident Gauss-Jordan of m_inverse_gj on every one of the N bins
+// (it takes contiguous matrices; d_zero: one double 0, its Tikhonov term), beyond on the matrix-core / blocked inverses
+// of the factorisation, on the n_bins bins only.  scratch: one C x C matrix per (problem, bin) beyond 128 signals.
+int sc_internal_mvar_inverse(int64_t C, int64_t P, int64_t N, int64_t n_bins, const void* d_M, void* d_out, void* scratch,
+                             const double* d_zero, hipStream_t st) {
+    const int64_t E = C * C;
+    if (C > MV_CSMALL)
+        return mv_launch_inverse_big(C, dim3((unsigned)n_bins, (unsigned)P), st, MvMat{(cd*)d_M, N * E, E, 1}, nullptr,
+                                     MvMat{(cd*)d_out, N * E, E, 1}, nullptr, (cd*)scratch);
+    const int Q = (int)((C + 15) / 16);
+    const size_t glds = mv_gj_lds(Q);
+#define MV_INV(QQ)                                                                                              \
+    case QQ:                                                                                                    \
+        SC_CHECK_HIP(hipFuncSetAttribute((const void*)m_inverse_gj<QQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds)); \
+        hipLaunchKernelGGL(m_inverse_gj<QQ>, dim3((unsigned)(P * N)), dim3(256), glds, st, (const cd*)d_M, d_zero, (cd*)d_out, \
+                           (int)C);                                                                             \
+        break;
+    switch (Q) { MV_INV(1) MV_INV(2) MV_INV(3) default: MV_INV(4) }
+#undef MV_INV
+    SC_CHECK_HIP(hipGetLastError());
+    return SC_OK;
+}
+
+// O = X Y per (problem p < n_problems, bin n < n_bins) on the fp64 matrix cores (m_gemm_mfma); every operand is natural-layout
+// with problem stride sp and bin stride sn in complex elements (sn = 0: one matrix for every bin).  O must not alias X or Y.
+int sc_internal_mvar_gemm(int64_t C, int64_t n_problems, int64_t n_bins, const void* X, int64_t x_sp, int64_t x_sn,
+                          const void* Y, int64_t y_sp, int64_t y_sn, void* O, int64_t o_sp, int64_t o_sn, hipStream_t st) {
+    return mv_launch_gemm(C, MV_GEMM_PLAIN, dim3((unsigned)n_bins, (unsigned)n_problems), st, MvMat{(cd*)X, x_sp, x_sn, 1},
+                          MvMat{(cd*)Y, y_sp, y_sn, 1}, MvMat{(cd*)O, o_sp, o_sn, 1}, nullptr, nullptr);
+}

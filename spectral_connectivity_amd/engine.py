@@ -746,6 +746,49 @@ def mvar_factor(n_groups, n_fft, n_signals, accum=None, n_freq_accum=0, planes=0
     return G, n_iter, status, (summary[0], summary[1], summary[2])
 
 
+def conditional_granger(G, n_groups, n_fft, n_signals, accum=None, n_freq_accum=0, planes=0, n_obs=1, spectra=None,
+                        tolerance=1e-8, max_iterations=60):
+    """Conditional spectral Granger prediction (sc_conditional.hip) from the cached full factor ``G`` [n_groups, n_fft, C, C]
+    and the records (or a two-sided complex128 spectrum tensor) it was factored from: one reduced (C - 1)-signal Wilson
+    factorisation per dropped signal, batched over the dropped signals of a chunk.  Returns (out [n_groups, n_fft/2+1, C, C]
+    float64, out[..., i, j] = j -> i given the rest, n_iter [C, n_groups], status [C, n_groups], summary) with summary =
+    (iterations run, reduced problems not converged, identity starts)."""
+    lib = _lib.load()
+    max_iterations = check_max_iterations(max_iterations)
+    C = n_signals
+    dev = G.device
+    F = n_fft // 2 + 1
+
+    def ws(n_dropped):
+        nbytes = ctypes.c_size_t()
+        _lib.check(lib.sc_conditional_granger_workspace_bytes(n_groups, C, n_fft, n_dropped, byref(nbytes)),
+                   "sc_conditional_granger_workspace_bytes")
+        return nbytes.value
+
+    chunk = _lib.conditional_chunk(n_groups, C, ws)
+    nbytes = ws(chunk)
+    work = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    out = torch.empty((n_groups, F, C, C), dtype=torch.float64, device=dev)
+    n_iter = torch.empty((C, n_groups), dtype=torch.int32, device=dev)
+    status = torch.empty((C, n_groups), dtype=torch.int32, device=dev)
+    dropped = torch.arange(C, dtype=torch.int32, device=dev)
+    iters = not_conv = fallback = 0
+    for j0 in range(0, C, chunk):
+        n = min(chunk, C - j0)
+        summary = (ctypes.c_int32 * 3)(0, 0, 0)
+        _lib.check(lib.sc_conditional_granger_f64(_ptr(accum) if accum is not None else None,
+                                                  _ptr(spectra) if spectra is not None else None, n_groups, n_freq_accum,
+                                                  n_fft, C, rec_planes(accum, planes) if accum is not None else planes, n_obs,
+                                                  _ptr(G), _ptr(dropped[j0:j0 + n]), n, tolerance, max_iterations, _ptr(work),
+                                                  nbytes, _lib.CONDITIONAL_KEEP_OUTPUT if j0 else 0, _ptr(out),
+                                                  _ptr(n_iter[j0:j0 + n]), _ptr(status[j0:j0 + n]), summary, _stream()),
+                   "sc_conditional_granger_f64")
+        iters = max(iters, summary[0])
+        not_conv += summary[1]
+        fallback += summary[2]
+    return out, n_iter, status, (iters, not_conv, fallback)
+
+
 def mvar_measure(G, which):
     """A directed MVAR measure / model quantity (``_lib.MVAR_*``) from the minimum-phase factor G."""
     lib = _lib.load()

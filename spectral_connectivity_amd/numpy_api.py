@@ -401,6 +401,51 @@ class Connectivity(_TorchHostConnectivity):
         dev.free()
         return out.reshape(self._kept_shape() + shape[1:])
 
+    def conditional_spectral_granger_prediction(self):
+        h, lib = host(), host().lib
+        N, C = self._shape5[3], self._shape5[4]
+        F = N // 2 + 1
+        self._check_mvar_signals()
+        G, _, _, n_groups = self._mvar_factor_device()
+        rec, n_obs, n_freq = self._csm_records("granger")
+
+        def ws(n_dropped):
+            nbytes = ctypes.c_size_t()
+            _lib.check(lib.sc_conditional_granger_workspace_bytes(n_groups, C, N, n_dropped, byref(nbytes)),
+                       "sc_conditional_granger_workspace_bytes")
+            return nbytes.value
+
+        chunk = _lib.conditional_chunk(n_groups, C, ws)
+        nbytes = ws(chunk)
+        work = h.alloc(nbytes)
+        out = h.alloc(n_groups * F * C * C * 8)
+        d_dropped = h.upload(np.arange(C, dtype=np.int32))
+        n_iter, status = h.alloc(C * n_groups * 4), h.alloc(C * n_groups * 4)
+        iters = not_conv = fallback = 0
+        for j0 in range(0, C, chunk):
+            n = min(chunk, C - j0)
+            summary = (ctypes.c_int32 * 3)(0, 0, 0)
+            _lib.check(lib.sc_conditional_granger_f64(rec.buf.ptr, None, n_groups, n_freq, N, C, rec.planes(_lib.PLANE_CSM),
+                                                      self._n_observations_total(n_obs), G.ptr, ctypes.c_void_p(d_dropped.ptr.value + 4 * j0), n, 1e-8, 60,
+                                                      work.ptr, nbytes, _lib.CONDITIONAL_KEEP_OUTPUT if j0 else 0, out.ptr,
+                                                      ctypes.c_void_p(n_iter.ptr.value + 4 * j0 * n_groups),
+                                                      ctypes.c_void_p(status.ptr.value + 4 * j0 * n_groups), summary,
+                                                      h.stream), "sc_conditional_granger_f64")
+            iters, not_conv, fallback = max(iters, summary[0]), not_conv + summary[1], fallback + summary[2]
+        res = np.array(h.download(out, (n_groups, F, C, C), np.float64))
+        st = np.array(h.download(status, (C, n_groups), np.int32))
+        its = np.array(h.download(n_iter, (C, n_groups), np.int32))
+        for b in (work, out, d_dropped, n_iter, status):
+            b.free()
+        if fallback:
+            logger.warning("Computing the initial conditions using the Cholesky failed. "
+                           f"Using the identity as initial condition ({fallback} reduced problems).")
+        if not_conv:
+            logger.warning(f"Maximum iterations reached. {st.size - not_conv} of {st.size} converged")
+        self._last_wilson = dict(iterations=int(iters), not_converged=int(not_conv), cholesky_fallbacks=int(fallback),
+                                 n_iter=its, status=st)
+        return res.reshape(self._kept_shape() + (F, C, C))
+
     @property
     def _minimum_phase_factor(self):
         h = host()

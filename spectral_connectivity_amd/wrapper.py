@@ -39,7 +39,7 @@ _NOT_IN_DATASET = {
     "phase_slope_index", "subset_pairwise_spectral_granger_prediction", "group_delay", "canonical_coherence",
     "directed_transfer_function", "directed_coherence", "partial_directed_coherence",
     "generalized_partial_directed_coherence", "direct_directed_transfer_function",
-    "blockwise_spectral_granger_prediction",
+    "blockwise_spectral_granger_prediction", "conditional_spectral_granger_prediction",
 }
 _MT_SKIP = {"time_series", "fft", "tapers", "frequencies", "time"}
 
