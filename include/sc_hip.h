@@ -64,7 +64,7 @@
 extern "C" {
 #endif
 
-#define SC_ABI_VERSION 7
+#define SC_ABI_VERSION 8
 
 /* error codes */
 #define SC_OK 0
@@ -500,6 +500,39 @@ int sc_conditional_granger_f64(const void* d_accum, const void* d_S /*complex128
                                const void* d_G /*complex128*/, const int32_t* d_dropped, int64_t n_dropped, double tolerance,
                                int max_iterations, void* d_work, size_t work_bytes, int flags, double* d_out,
                                int32_t* d_n_iter, int32_t* d_status, int32_t* h_summary, void* stream);
+
+/* ---- blockwise spectral Granger prediction (ABI v8, fp64) ----------------------------------
+ * Block b -> block a for pairs of signal BLOCKS (Geweke 1982, multivariate form); the reference raises NotImplementedError
+ * (connectivity.py:1226-1235).  (Signal groups are "blocks" here: n_groups is the records' groups, windows x kept axes.)
+ * Pair q has m signals, d_members[q][0 .. n_a-1] of block a then d_members[q][n_a .. m-1] of block b (n_a = d_split[q]); its
+ * m x m two-sided spectrum S of every group is factored by the Wilson iteration of sc_mvar_factor_f64 (problem q * n_groups + g).
+ * With Psi0 = Re mean_n Psi, U_b an orthonormal basis of the null space of the rows Psi0[a, :] (U_a of Psi0[b, :]),
+ * V_a = Psi[a, :](f) U_b and V_b = Psi[b, :](f) U_a:
+ *     out[g][f][A][B] = ln det S_aa(f) - ln det(S_aa(f) - V_a V_a^H)      (B -> A; A, B = d_cell[q][0], d_cell[q][1])
+ *     out[g][f][B][A] = ln det S_bb(f) - ln det(S_bb(f) - V_b V_b^H)      (A -> B)
+ * = ln det S_aa - ln det(S_aa - H_ab Sigma~_bb H_ab^H), Sigma~_bb = Sigma_bb - Sigma_ba Sigma_aa^-1 Sigma_ab, H = Psi Psi0^-1,
+ * Sigma = Psi0 Psi0^T; with n_a = n_b = 1 the pairwise measure.  A Cholesky pivot that is not positive, or a value <= 0, is NaN.
+ *   d_accum / d_S  exactly one: the records sc_mvar_factor_f64 takes (SC_PLANE_CSM, N or N/2+1 bins per group) or
+ *                  complex128 [n_groups][N][n_signals][n_signals] two-sided Hermitian spectra
+ *   d_members      int32 [n_pairs][m], signals in [0, n_signals); d_split int32 [n_pairs], 1 <= n_a < m (n_a may differ inside a
+ *                  batch); d_cell int32 [n_pairs][2], distinct output block indices in [0, n_blocks).  The three lists are read
+ *                  back and checked before any launch.
+ *   d_out          double [n_groups][N/2+1][n_blocks][n_blocks]; NaN-filled first (diagonal, pairs not computed) unless flags has
+ *                  SC_BLOCKWISE_KEEP_OUTPUT (the caller walks the pairs in batches that share one output); only the two cells of
+ *                  each pair are written
+ *   d_n_iter, d_status  int32 [n_pairs * n_groups]: Wilson iterations / 1 converged, 0 hit max_iterations, per problem
+ *   h_summary      optional HOST int32[3] {iterations run, problems not converged, identity starts}, as sc_mvar_factor_f64
+ * 2 <= m <= sc_mvar_max_signals(), otherwise SC_EUNSUPPORTED; n_pairs * n_groups <= 65535.  Workspace:
+ * sc_blockwise_granger_workspace_bytes(n_groups, m, N, n_pairs): the spectra and factors (two complex128 arrays
+ * [n_pairs * n_groups][N][m][m]) and the larger of the factorisation's workspace and the epilogue's arrays (complex128
+ * [n_pairs * n_groups][N/2+1][m][m] and two [n_pairs * n_groups][m][m]).  Synchronises the stream (as sc_mvar_factor_f64). */
+#define SC_BLOCKWISE_KEEP_OUTPUT 1
+int sc_blockwise_granger_workspace_bytes(int64_t n_groups, int64_t m, int64_t N, int64_t n_pairs, size_t* bytes);
+int sc_blockwise_granger_f64(const void* d_accum, const void* d_S /*complex128*/, int64_t n_groups, int64_t n_freq_accum,
+                             int64_t N, int64_t n_signals, uint32_t planes, int64_t n_observations, const int32_t* d_members,
+                             const int32_t* d_split, const int32_t* d_cell, int64_t n_pairs, int64_t m, int64_t n_blocks,
+                             double tolerance, int max_iterations, void* d_work, size_t work_bytes, int flags, double* d_out,
+                             int32_t* d_n_iter, int32_t* d_status, int32_t* h_summary, void* stream);
 
 /* ---- global coherence (fp64, from the accumulated CSM) --------------------------------------
  * Replaces Connectivity.global_coherence / _estimate_global_coherence (connectivity.py:822-895,

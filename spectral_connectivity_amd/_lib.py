@@ -21,9 +21,10 @@ from . import _build
 c_int64_p = POINTER(c_int64)
 
 # ---- constants mirrored from include/sc_hip.h -------------------------------------------
-SC_ABI_VERSION = 7
+SC_ABI_VERSION = 8
 GRANGER_KEEP_OUTPUT = 1
 CONDITIONAL_KEEP_OUTPUT = 1
+BLOCKWISE_KEEP_OUTPUT = 1
 DETREND = {None: 0, "constant": 1, "c": 1, "linear": 2, "l": 2}
 MVAR_DTF, MVAR_DC, MVAR_PDC, MVAR_GPDC, MVAR_DDTF, MVAR_TRANSFER, MVAR_COEFFICIENTS, MVAR_NOISE_COVARIANCE = range(8)
 PLANE_CSM, PLANE_ABS_IM, PLANE_IM_SQ, PLANE_SIGN_IM, PLANE_UNIT = 0x01, 0x02, 0x04, 0x08, 0x10
@@ -155,6 +156,10 @@ SYMBOLS = {
     "sc_conditional_granger_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_uint32, c_int64,
                                            c_void_p, c_void_p, c_int64, c_double, c_int, c_void_p, c_size_t, c_int,
                                            c_void_p, c_void_p, c_void_p, POINTER(c_int32), c_void_p]),
+    "sc_blockwise_granger_workspace_bytes": (c_int, [c_int64, c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    "sc_blockwise_granger_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_uint32, c_int64,
+                                         c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double, c_int, c_void_p,
+                                         c_size_t, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_int32), c_void_p]),
     "sc_global_coherence_max_signals": (c_int, []),
     "sc_global_coherence_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_uint32, c_int64, c_int, c_int,
                                         c_void_p, c_void_p, c_void_p]),
@@ -197,6 +202,55 @@ def conditional_chunk(n_groups, n_signals, workspace_bytes, cap=None):
     one = workspace_bytes(1)
     per = max(1, workspace_bytes(2) - one)
     return int(max(1, min(n_signals, 65535 // n_groups, (cap - (one - per)) // per)))
+
+
+def blockwise_chunk(n_groups, n_pairs, workspace_bytes, cap=None):
+    """Block pairs per sc_blockwise_granger_f64 call (both hosts), among ``n_pairs`` pairs of one size m: as many as keep the
+    workspace under ``cap`` (CONDITIONAL_WORK_BYTES) -- at least one, at most 65535 problems.  ``workspace_bytes(n)``: the
+    library's query for n pairs."""
+    return conditional_chunk(n_groups, n_pairs, workspace_bytes, cap)
+
+
+def blockwise_pairs(group_labels, n_signals, max_signals):
+    """Labels of blockwise_spectral_granger_prediction, checked before any device work (both hosts): (labels, pairs).
+    ``labels`` = np.unique of ``group_labels``; ``pairs`` the unordered block pairs a < b as (members [m] int32: the signals of
+    a, then of b; n_a; (a, b)).  ValueError for a label list of the wrong length, fewer than two blocks and a pair of more than
+    ``max_signals`` signals."""
+    import numpy as np
+    group_labels = np.asarray(group_labels)
+    if group_labels.ndim != 1 or len(group_labels) != n_signals:
+        raise ValueError(f"group_labels must have one label per signal ({n_signals}), got {group_labels.shape}")
+    labels = np.unique(group_labels)
+    if len(labels) < 2:
+        raise ValueError(f"blockwise Granger needs at least two groups of signals (got {len(labels)})")
+    blocks = [np.flatnonzero(group_labels == lab) for lab in labels]
+    pairs = []
+    for a in range(len(blocks)):
+        for b in range(a + 1, len(blocks)):
+            m = len(blocks[a]) + len(blocks[b])
+            if m > max_signals:
+                raise ValueError(f"blockwise Granger: groups {labels[a].item()!r} and {labels[b].item()!r} have {m} signals together; "
+                                 f"a group pair supports at most {max_signals}")
+            pairs.append((np.concatenate([blocks[a], blocks[b]]).astype(np.int32), len(blocks[a]), (a, b)))
+    return labels, pairs
+
+
+def blockwise_batches(pairs, n_obs):
+    """The pairs of blockwise_pairs grouped by m = n_a + n_b: (batches, n_skipped), ``batches`` maps m (ascending) to
+    (members [n][m], split [n], cell [n][2]) int32 arrays.  A pair of more signals than the ``n_obs`` observations has a
+    rank-deficient spectrum: it is left out (NaN) and counted in ``n_skipped``."""
+    import numpy as np
+    by_m, n_skipped = {}, 0
+    for members, na, cell in pairs:
+        if len(members) > n_obs:
+            n_skipped += 1
+            continue
+        by_m.setdefault(len(members), []).append((members, na, cell))
+    batches = {}
+    for m, items in sorted(by_m.items()):
+        batches[m] = (np.stack([it[0] for it in items]).astype(np.int32), np.array([it[1] for it in items], dtype=np.int32),
+                      np.array([it[2] for it in items], dtype=np.int32))
+    return batches, n_skipped
 
 
 def library_path():

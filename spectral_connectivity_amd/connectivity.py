@@ -655,5 +655,46 @@ class Connectivity:
                                  n_iter=n_iter.cpu().numpy(), status=st)
         return engine.to_host(out).reshape(self._kept_shape() + (N // 2 + 1, C, C))
 
-    def blockwise_spectral_granger_prediction(self):
-        raise NotImplementedError   # reference connectivity.py:1226-1235 raises too
+    # (the reference declares the method without arguments, tests/golden/api_surface.json: group_labels is bound here)
+    def blockwise_spectral_granger_prediction(self, *args, **kwargs):
+        """Power in group a explained by group b, out[..., a, b] = b -> a, for groups of signals (Geweke 1982, multivariate
+        form -- the reference raises NotImplementedError, connectivity.py:1226-1235).  ``group_labels``: one label per signal;
+        returns (values [kept axes..., n_freq, n_groups, n_groups] float64 with a NaN diagonal, np.unique(group_labels)).
+        One Wilson factorisation of the n_a + n_b signals of every group pair runs on the device (sc_blockwise.hip), so a pair
+        may have up to sc_mvar_max_signals() signals whatever the total.  A pair with more signals than observations has a
+        rank-deficient spectrum and is NaN (one warning counts them).  ``_last_wilson`` then describes the pair factorisations
+        (n_iter / status [computed pairs, n_groups], pairs in order of their size m, then of the labels)."""
+        return self._blockwise_granger(*args, **kwargs)
+
+    def _blockwise_pairs(self, group_labels):
+        return _lib.blockwise_pairs(group_labels, self._shape5[4], int(_lib.load().sc_mvar_max_signals()))
+
+    def _blockwise_batches(self, pairs, n_obs_total):
+        batches, n_skipped = _lib.blockwise_batches(pairs, n_obs_total)
+        if n_skipped:
+            logger.warning(f"blockwise Granger: {n_skipped} group pairs have more signals than the {n_obs_total} observations "
+                           "(rank-deficient spectra): NaN")
+        return batches
+
+    def _blockwise_wilson(self, iters, not_conv, fallback, n_iter, status):
+        if fallback:
+            logger.warning("Computing the initial conditions using the Cholesky failed. "
+                           f"Using the identity as initial condition ({fallback} group-pair problems).")
+        if not_conv:
+            logger.warning(f"Maximum iterations reached. {status.size - not_conv} of {status.size} converged")
+        self._last_wilson = dict(iterations=int(iters), not_converged=int(not_conv), cholesky_fallbacks=int(fallback),
+                                 n_iter=n_iter, status=status)
+
+    def _blockwise_granger(self, group_labels):
+        from . import engine
+        N = self._shape5[3]
+        labels, pairs = self._blockwise_pairs(group_labels)      # (the labels are checked before any device work)
+        accum, n_obs, n_freq = self._csm_records("granger")
+        n_total = self._n_observations_total(n_obs)
+        batches = self._blockwise_batches(pairs, n_total)
+        n_groups = accum.shape[0] // n_freq
+        out, n_iter, status, (iters, not_conv, fallback) = engine.blockwise_granger(
+            n_groups, N, self._shape5[4], batches, len(labels), accum=accum, n_freq_accum=n_freq, planes=_lib.PLANE_CSM,
+            n_obs=n_total)
+        self._blockwise_wilson(iters, not_conv, fallback, n_iter.cpu().numpy(), status.cpu().numpy())
+        return engine.to_host(out).reshape(self._kept_shape() + (N // 2 + 1, len(labels), len(labels))), labels

@@ -764,44 +764,6 @@ __global__ void __launch_bounds__(256) canonical_big_kernel(CanonArgs a, cd* scr
 #define CBH_LDS_N 96
 #define CBH_SMALL 64           // pairs of groups of at most this many channels are processed in LDS entirely
 #define CBH_LD 65              // their row length (odd: a column walk touches every bank)
-// in-place lower Cholesky of the n x n Hermitian matrix L (row-major, row length ld, lower triangle valid), all 256 threads
-__device__ inline void cbh_cholesky(cd* L, int ld, int n, int* bad) {
-    const int tid = threadIdx.x;
-    for (int k = 0; k < n; ++k) {
-        if (tid == 0) {
-            const double d = L[k * ld + k].x;
-            if (!(d > 0.0)) *bad = 1;
-            L[k * ld + k] = make_double2(sqrt(d > 0.0 ? d : 1.0), 0.0);
-        }
-        __syncthreads();
-        const double dk = L[k * ld + k].x;
-        for (int i = k + 1 + tid; i < n; i += 256) {
-            const cd v = L[i * ld + k];
-            L[i * ld + k] = make_double2(v.x / dk, v.y / dk);
-        }
-        __syncthreads();
-        const int m = n - k - 1;
-        for (int e = tid; e < m * m; e += 256) {           // trailing lower triangle: L[i][j] -= L[i][k] conj(L[j][k]), k < j <= i
-            const int i = k + 1 + e / m, j = k + 1 + e % m;
-            if (j <= i) {
-                const cd t = zmulc(L[i * ld + k], L[j * ld + k]);
-                cd v = L[i * ld + j];
-                v.x -= t.x; v.y -= t.y;
-                L[i * ld + j] = v;
-            }
-        }
-        __syncthreads();
-    }
-}
-__device__ __forceinline__ double cbh_sum(double v, double* red4, int tid) {      // block sum over 256 threads, two barriers
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    if ((tid & 63) == 0) red4[tid >> 6] = v;
-    __syncthreads();
-    const double r = red4[0] + red4[1] + red4[2] + red4[3];
-    __syncthreads();
-    return r;
-}
 __global__ void __launch_bounds__(256) canonical_big_hh_kernel(CanonArgs a, cd* scratch, int64_t n_items, int small_n, int small_ld) {
     extern __shared__ __align__(16) unsigned char cb_smem[];
     cd* Bl = reinterpret_cast<cd*>(cb_smem);                 // CBH_LDS_N^2 elements: B (column-major) or, for pairs of groups of at
@@ -838,7 +800,7 @@ __global__ void __launch_bounds__(256) canonical_big_hh_kernel(CanonArgs a, cd* 
         for (int e = tid; e < na * na; e += 256) { const int i = e / na, j = e % na; if (j <= i) PA[i * ld + j] = csm_read(rec, a, ma[i], ma[j]); }
         for (int e = tid; e < na * nb; e += 256) { const int i = e / nb, j = e % nb; PM[i * ld + j] = csm_read(rec, a, ma[i], mb[j]); }
         __syncthreads();
-        cbh_cholesky(PA, ld, na, &bad);
+        sc_wg_cholesky(PA, ld, na, &bad);
         // M <- L_a^-1 M, right-looking: row k is final once it is divided by L_a[k][k]; every row below loses its multiple of it
         for (int k = 0; k < na; ++k) {
             const double dk = PA[k * ld + k].x;
@@ -856,7 +818,7 @@ __global__ void __launch_bounds__(256) canonical_big_hh_kernel(CanonArgs a, cd* 
         }
         for (int e = tid; e < nb * nb; e += 256) { const int i = e / nb, j = e % nb; if (j <= i) PB[i * ld + j] = csm_read(rec, a, mb[i], mb[j]); }
         __syncthreads();
-        cbh_cholesky(PB, ld, nb, &bad);
+        sc_wg_cholesky(PB, ld, nb, &bad);
         // M <- M L_b^-H: column k is final once it is divided by L_b[k][k]; every column to its right loses conj(L_b[j][k]) times it
         for (int k = 0; k < nb; ++k) {
             const double dk = PB[k * ld + k].x;
@@ -889,7 +851,7 @@ __global__ void __launch_bounds__(256) canonical_big_hh_kernel(CanonArgs a, cd* 
             cd xi = make_double2(0.0, 0.0);
             if (tid < m) xi = col[tid];
             if (tid == 0) { sh[0] = xi.x; sh[1] = xi.y; dg[k] = B[(size_t)k * na + k].x; }
-            const double xn2 = cbh_sum((tid >= 1 && tid < m) ? xi.x * xi.x + xi.y * xi.y : 0.0, red4, tid);
+            const double xn2 = sc_wg_sum((tid >= 1 && tid < m) ? xi.x * xi.x + xi.y * xi.y : 0.0, red4, tid);
             const double alr = sh[0], ali = sh[1];
             if (xn2 == 0.0 && ali == 0.0) {                  // H = I (uniform over the workgroup)
                 if (tid == 0) e2[k] = alr * alr;
@@ -918,8 +880,8 @@ __global__ void __launch_bounds__(256) canonical_big_hh_kernel(CanonArgs a, cd* 
                 }
                 pi = zmul(tk, acc);
             }
-            const double dre = cbh_sum(pi.x * vi.x + pi.y * vi.y, red4, tid);       // p^H v
-            const double dim = cbh_sum(pi.x * vi.y - pi.y * vi.x, red4, tid);
+            const double dre = sc_wg_sum(pi.x * vi.x + pi.y * vi.y, red4, tid);       // p^H v
+            const double dim = sc_wg_sum(pi.x * vi.y - pi.y * vi.x, red4, tid);
             const cd al2 = zmul(make_double2(-0.5 * tk.x, -0.5 * tk.y), make_double2(dre, dim));
             cd wi = make_double2(0.0, 0.0);
             if (tid < m) {

@@ -137,6 +137,87 @@ __host__ __device__ inline int sc_tile_index(int bi, int bj, int nb) {
     return bi * nb - bi * (bi - 1) / 2 + (bj - bi);
 }
 
+// CSM records as the consumers of a C x C two-sided spectrum read them (sc_conditional.hip, sc_blockwise.hip): F = N or N/2+1
+// bins per group (N/2+1: real input, S(-f) = conj S(f) completes the bins past N/2), upper-triangular 16 x 16 tiles of
+// un-normalised sums divided by n_obs.  sc_csm_view: from the arguments of an entry point (d_accum non-NULL).
+struct ScCsmView {
+    int64_t N, F, floats_per_bin;
+    int NB, n_tiles, p_csm, two_sided;
+    double n_obs;
+};
+inline int sc_csm_view(uint32_t planes, int64_t n_freq_accum, int64_t N, int64_t C, int64_t n_obs, ScCsmView* v) {
+    SC_REQUIRE(planes & SC_PLANE_CSM, "accumulator record must contain SC_PLANE_CSM");
+    SC_REQUIRE(n_freq_accum == N || n_freq_accum == N / 2 + 1, "accumulators must hold N or N/2+1 bins");
+    SC_REQUIRE(n_obs >= 1, "n_observations must be positive");
+    v->N = N; v->F = n_freq_accum;
+    v->NB = sc_n_blocks(C); v->n_tiles = sc_n_tiles(v->NB);
+    v->p_csm = sc_plane_offset(planes, SC_PLANE_CSM);
+    v->two_sided = n_freq_accum == N ? 1 : 0;
+    v->floats_per_bin = (int64_t)sc_plane_count(planes) * v->n_tiles * SC_TILE_ELEMS;
+    v->n_obs = (double)n_obs;
+    return SC_OK;
+}
+// S_g(n)[i][j] (two-sided bin n of group g)
+__device__ inline double2 sc_csm_two_sided(ScRec accum, const ScCsmView& v, int64_t g, int64_t n, int i, int j) {
+    int64_t bin = n;
+    bool conj = false;
+    if (!v.two_sided && n > v.N / 2) { bin = v.N - n; conj = true; }
+    const ScRec rec = accum + (g * v.F + bin) * v.floats_per_bin;
+    int ti = i >> 4, tj = j >> 4, ii = i & 15, jj = j & 15;
+    const bool m = (ti > tj) || (ti == tj && ii > jj);
+    if (m) { int t = ti; ti = tj; tj = t; t = ii; ii = jj; jj = t; }
+    const int64_t off = (int64_t)sc_tile_index(ti, tj, v.NB) * SC_TILE_ELEMS + ii * 16 + jj;
+    const double re = rec[(int64_t)v.p_csm * v.n_tiles * SC_TILE_ELEMS + off] / v.n_obs;
+    double im = rec[(int64_t)(v.p_csm + 1) * v.n_tiles * SC_TILE_ELEMS + off] / v.n_obs;
+    if (m) im = -im;
+    if (conj) im = -im;
+    if (i == j) im = 0.0;
+    return make_double2(re, im);
+}
+
+// Workgroup-wide helpers of 256-thread kernels (sc_canonical.hip, sc_blockwise.hip).
+// In-place lower Cholesky of the n x n Hermitian matrix L (row-major, row length ld, lower triangle valid), all 256 threads,
+// right-looking; a pivot that is not positive is replaced by 1 and sets *bad.
+__device__ inline void sc_wg_cholesky(double2* L, int ld, int n, int* bad) {
+    const int tid = threadIdx.x;
+    for (int k = 0; k < n; ++k) {
+        if (tid == 0) {
+            const double d = L[k * ld + k].x;
+            if (!(d > 0.0)) *bad = 1;
+            L[k * ld + k] = make_double2(sqrt(d > 0.0 ? d : 1.0), 0.0);
+        }
+        __syncthreads();
+        const double dk = L[k * ld + k].x;
+        for (int i = k + 1 + tid; i < n; i += 256) {
+            const double2 v = L[i * ld + k];
+            L[i * ld + k] = make_double2(v.x / dk, v.y / dk);
+        }
+        __syncthreads();
+        const int m = n - k - 1;
+        for (int e = tid; e < m * m; e += 256) {           // trailing lower triangle: L[i][j] -= L[i][k] conj(L[j][k]), k < j <= i
+            const int i = k + 1 + e / m, j = k + 1 + e % m;
+            if (j <= i) {
+                const double2 a = L[i * ld + k], b = L[j * ld + k];
+                const double2 t = make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y);
+                double2 v = L[i * ld + j];
+                v.x -= t.x; v.y -= t.y;
+                L[i * ld + j] = v;
+            }
+        }
+        __syncthreads();
+    }
+}
+// block sum over 256 threads, two barriers (every thread gets the sum)
+__device__ __forceinline__ double sc_wg_sum(double v, double* red4, int tid) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if ((tid & 63) == 0) red4[tid >> 6] = v;
+    __syncthreads();
+    const double r = red4[0] + red4[1] + red4[2] + red4[3];
+    __syncthreads();
+    return r;
+}
+
 // Decoding of group / observation indices into element offsets (see sc_spectra_desc).
 struct ScAxes {
     int64_t sW, sR, sK, sF;

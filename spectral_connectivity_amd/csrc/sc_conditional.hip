@@ -24,10 +24,9 @@
 typedef double2 cd;
 
 struct CgDims {
-    int64_t G, N, F;     // groups, two-sided length, accumulated bins per group (N or N/2+1)
-    int C, NB, n_tiles, p_csm, two_sided;
-    int64_t floats_per_bin;
-    double n_obs;
+    int64_t G, N;        // groups, two-sided length
+    int C;
+    ScCsmView v;         // the records (d_accum)
 };
 
 __device__ __forceinline__ int cg_full(int k, int j) { return k < j ? k : k + 1; }     // reduced index -> full index
@@ -50,20 +49,7 @@ __global__ void __launch_bounds__(256) cg_gather(ScRec accum, const cd* __restri
         if (S) {
             v = S[((g * d.N + n) * d.C + i) * d.C + j];
         } else {
-            int64_t bin = n;
-            bool conj = false;
-            if (!d.two_sided && n > d.N / 2) { bin = d.N - n; conj = true; }
-            const ScRec rec = accum + (g * d.F + bin) * d.floats_per_bin;
-            int ti = i >> 4, tj = j >> 4, ii = i & 15, jj = j & 15;
-            const bool m = (ti > tj) || (ti == tj && ii > jj);
-            if (m) { int t = ti; ti = tj; tj = t; t = ii; ii = jj; jj = t; }
-            const int64_t off = (int64_t)sc_tile_index(ti, tj, d.NB) * SC_TILE_ELEMS + ii * 16 + jj;
-            const double re = rec[(int64_t)d.p_csm * d.n_tiles * SC_TILE_ELEMS + off] / d.n_obs;
-            double im = rec[(int64_t)(d.p_csm + 1) * d.n_tiles * SC_TILE_ELEMS + off] / d.n_obs;
-            if (m) im = -im;
-            if (conj) im = -im;
-            if (i == j) im = 0.0;
-            v = make_double2(re, im);
+            v = sc_csm_two_sided(accum, d.v, g, n, i, j);
         }
         Sred[(pr * d.N + n) * Er + e] = v;
     }
@@ -188,19 +174,9 @@ extern "C" int sc_conditional_granger_f64(const void* d_accum, const void* d_S, 
     }
     SC_CHECK_HIP(hipMemsetAsync(zero, 0, 256, st));
     // reduced spectra
-    CgDims d;
-    d.G = G; d.N = N; d.F = n_freq_accum; d.C = (int)C;
-    d.NB = sc_n_blocks(C); d.n_tiles = sc_n_tiles(d.NB);
-    d.p_csm = 0; d.two_sided = 1; d.floats_per_bin = 0; d.n_obs = 1.0;
-    if (d_accum) {
-        SC_REQUIRE(planes & SC_PLANE_CSM, "accumulator record must contain SC_PLANE_CSM");
-        SC_REQUIRE(n_freq_accum == N || n_freq_accum == N / 2 + 1, "accumulators must hold N or N/2+1 bins");
-        SC_REQUIRE(n_obs >= 1, "n_observations must be positive");
-        d.p_csm = sc_plane_offset(planes, SC_PLANE_CSM);
-        d.two_sided = n_freq_accum == N ? 1 : 0;
-        d.floats_per_bin = (int64_t)sc_plane_count(planes) * d.n_tiles * SC_TILE_ELEMS;
-        d.n_obs = (double)n_obs;
-    }
+    CgDims d = {};
+    d.G = G; d.N = N; d.C = (int)C;
+    if (d_accum && (rc = sc_csm_view(planes, n_freq_accum, N, C, n_obs, &d.v)) != SC_OK) return rc;
     const dim3 gridG((unsigned)((Er + 255) / 256), (unsigned)(N < 1024 ? N : 1024), (unsigned)P);
     hipLaunchKernelGGL(cg_gather, gridG, dim3(256), 0, st, sc_rec(d_accum, planes), (const cd*)d_S, d, d_dropped, Sred);
     SC_CHECK_HIP(hipGetLastError());

@@ -789,6 +789,61 @@ def conditional_granger(G, n_groups, n_fft, n_signals, accum=None, n_freq_accum=
     return out, n_iter, status, (iters, not_conv, fallback)
 
 
+def blockwise_granger(n_groups, n_fft, n_signals, batches, n_blocks, accum=None, n_freq_accum=0, planes=0, n_obs=1, spectra=None,
+                       tolerance=1e-8, max_iterations=60, device=None):
+    """Blockwise spectral Granger prediction (sc_blockwise.hip) from the records (or a two-sided complex128 spectrum tensor):
+    one m-signal Wilson factorisation per (block pair, group), the pairs of one size m batched under the workspace cap.
+    ``batches``: {m: (members [n, m], split [n], cell [n, 2])} int32 arrays (_lib.blockwise_batches).  Returns (out [n_groups,
+    n_fft/2+1, n_blocks, n_blocks] float64, out[..., a, b] = b -> a, NaN where no pair was computed, n_iter [pairs, n_groups],
+    status [pairs, n_groups] in the order of the batches, summary) with summary = (iterations run, problems not converged,
+    identity starts)."""
+    lib = _lib.load()
+    max_iterations = check_max_iterations(max_iterations)
+    dev = device if device is not None else (accum if accum is not None else spectra).device
+    F = n_fft // 2 + 1
+    total = sum(len(split) for _, split, _ in batches.values())
+    out = torch.empty((n_groups, F, n_blocks, n_blocks), dtype=torch.float64, device=dev)
+    n_iter = torch.zeros((total, n_groups), dtype=torch.int32, device=dev)
+    status = torch.zeros((total, n_groups), dtype=torch.int32, device=dev)
+    iters = not_conv = fallback = 0
+    row, flags = 0, 0              # the first call NaN-fills the output, the others keep it
+    for m, (members, split, cell) in batches.items():
+        n_pairs = len(split)
+
+        def ws(n, m=m):
+            nbytes = ctypes.c_size_t()
+            _lib.check(lib.sc_blockwise_granger_workspace_bytes(n_groups, m, n_fft, n, byref(nbytes)),
+                       "sc_blockwise_granger_workspace_bytes")
+            return nbytes.value
+
+        chunk = _lib.blockwise_chunk(n_groups, n_pairs, ws)
+        nbytes = ws(chunk)
+        work = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        d_members = torch.as_tensor(members, device=dev)
+        d_split = torch.as_tensor(split, device=dev)
+        d_cell = torch.as_tensor(cell, device=dev)
+        for q0 in range(0, n_pairs, chunk):
+            n = min(chunk, n_pairs - q0)
+            summary = (ctypes.c_int32 * 3)(0, 0, 0)
+            _lib.check(lib.sc_blockwise_granger_f64(_ptr(accum) if accum is not None else None,
+                                                    _ptr(spectra) if spectra is not None else None, n_groups, n_freq_accum, n_fft,
+                                                    n_signals, rec_planes(accum, planes) if accum is not None else planes, n_obs,
+                                                    _ptr(d_members[q0:q0 + n]), _ptr(d_split[q0:q0 + n]), _ptr(d_cell[q0:q0 + n]), n,
+                                                    m, n_blocks, tolerance, max_iterations, _ptr(work), nbytes,
+                                                    flags, _ptr(out), _ptr(n_iter[row + q0:row + q0 + n]),
+                                                    _ptr(status[row + q0:row + q0 + n]), summary, _stream()),
+                       "sc_blockwise_granger_f64")
+            iters = max(iters, summary[0])
+            not_conv += summary[1]
+            fallback += summary[2]
+            flags = _lib.BLOCKWISE_KEEP_OUTPUT
+        row += n_pairs
+        del work
+    if not flags:
+        out.fill_(float("nan"))
+    return out, n_iter, status, (iters, not_conv, fallback)
+
+
 def mvar_measure(G, which):
     """A directed MVAR measure / model quantity (``_lib.MVAR_*``) from the minimum-phase factor G."""
     lib = _lib.load()

@@ -446,6 +446,58 @@ class Connectivity(_TorchHostConnectivity):
                                  n_iter=its, status=st)
         return res.reshape(self._kept_shape() + (F, C, C))
 
+    def _blockwise_granger(self, group_labels):
+        h, lib = host(), host().lib
+        N, C = self._shape5[3], self._shape5[4]
+        F = N // 2 + 1
+        labels, pairs = self._blockwise_pairs(group_labels)      # (the labels are checked before any device work)
+        rec, n_obs, n_freq = self._csm_records("granger")
+        n_total = self._n_observations_total(n_obs)
+        batches = self._blockwise_batches(pairs, n_total)
+        n_groups, B = rec.n_bins // n_freq, len(labels)
+        total = sum(len(split) for _, split, _ in batches.values())
+        out = h.alloc(n_groups * F * B * B * 8)
+        n_iter, status = h.alloc(max(1, total) * n_groups * 4), h.alloc(max(1, total) * n_groups * 4)
+        iters = not_conv = fallback = 0
+        row, flags = 0, 0                  # the first call NaN-fills the output, the others keep it
+        for m, (members, split, cell) in batches.items():
+            n_pairs = len(split)
+
+            def ws(n, m=m):
+                nbytes = ctypes.c_size_t()
+                _lib.check(lib.sc_blockwise_granger_workspace_bytes(n_groups, m, N, n, byref(nbytes)),
+                           "sc_blockwise_granger_workspace_bytes")
+                return nbytes.value
+
+            chunk = _lib.blockwise_chunk(n_groups, n_pairs, ws)
+            nbytes = ws(chunk)
+            work = h.alloc(nbytes)
+            lists = [h.upload(a) for a in (members, split, cell)]
+            for q0 in range(0, n_pairs, chunk):
+                n = min(chunk, n_pairs - q0)
+                summary = (ctypes.c_int32 * 3)(0, 0, 0)
+                at = [ctypes.c_void_p(buf.ptr.value + 4 * q0 * width) for buf, width in zip(lists, (m, 1, 2))]
+                _lib.check(lib.sc_blockwise_granger_f64(rec.buf.ptr, None, n_groups, n_freq, N, C, rec.planes(_lib.PLANE_CSM), n_total,
+                                                        at[0], at[1], at[2], n, m, B, 1e-8, 60, work.ptr, nbytes, flags, out.ptr,
+                                                        ctypes.c_void_p(n_iter.ptr.value + 4 * (row + q0) * n_groups),
+                                                        ctypes.c_void_p(status.ptr.value + 4 * (row + q0) * n_groups), summary,
+                                                        h.stream), "sc_blockwise_granger_f64")
+                iters, not_conv, fallback = max(iters, summary[0]), not_conv + summary[1], fallback + summary[2]
+                flags = _lib.BLOCKWISE_KEEP_OUTPUT
+            row += n_pairs
+            for b in [work] + lists:
+                b.free()
+        if flags:
+            res = np.array(h.download(out, (n_groups, F, B, B), np.float64))
+        else:
+            res = np.full((n_groups, F, B, B), np.nan)
+        st = np.array(h.download(status, (total, n_groups), np.int32)) if total else np.zeros((0, n_groups), np.int32)
+        its = np.array(h.download(n_iter, (total, n_groups), np.int32)) if total else np.zeros((0, n_groups), np.int32)
+        for b in (out, n_iter, status):
+            b.free()
+        self._blockwise_wilson(iters, not_conv, fallback, its, st)
+        return res.reshape(self._kept_shape() + (F, B, B)), labels
+
     @property
     def _minimum_phase_factor(self):
         h = host()

@@ -56,7 +56,7 @@ def _xarray():
 
 
 def _check_method(method):
-    if method in ("group_delay", "canonical_coherence") or "directed" in method:
+    if method in ("group_delay", "canonical_coherence", "blockwise_spectral_granger_prediction") or "directed" in method:
         raise ValueError(
             f"The method '{method}' is not supported by the xarray interface. "
             f"Please use the Connectivity class directly instead:\n\n"
