@@ -570,6 +570,21 @@ int sc_canonical_coherence_f64(const void* d_accum, int64_t n_bins, int64_t n_si
                                int n_groups, int max_group_size, double* d_out, int32_t* d_fail,
                                void* stream);
 
+/* ---- multivariate imaginary coherence between channel groups (fp64, from the accumulated CSM) ----
+ * The leakage-robust group measures of Ewald, Marzetti, Zappasodi, Meinecke & Nolte 2012 (NeuroImage 62:1964-1971), per
+ * (bin, group pair), with R_g = Re S_gg, I = Im S_ab and D = R_a^-1/2 I R_b^-1/2:
+ *     MIC = sigma_max(D)                                 in [0, 1]
+ *     MIM = sum_k sigma_k(D)^2 = tr(R_a^-1 I R_b^-1 I^T)   in [0, min(n_a, n_b)]
+ * Both are 0 wherever the cross-spectrum is real.  The kernels and conventions of sc_canonical_coherence_f64 (same member
+ * table and stride, group sizes up to sc_canonical_max_group(), workspace, argument checks and error codes) on a second read
+ * view of the records -- group blocks (Re S, 0), cross blocks (0, Im S) -- always with the Householder / Sturm kernels.
+ *   d_mic, d_mim  double [n_bins][n_groups][n_groups], symmetric, NaN diagonal
+ *   d_fail        int32 [1]: number of pairs with a group block whose real part was not positive definite (NaN in both) */
+int sc_imaginary_interaction_f64(const void* d_accum, int64_t n_bins, int64_t n_signals, uint32_t planes,
+                                 int64_t n_observations, const int32_t* d_members, const int32_t* d_sizes,
+                                 int n_groups, int max_group_size, double* d_mic, double* d_mim,
+                                 int32_t* d_fail, void* stream);
+
 /* ---- host-pointer side of the boundary: memory, copies, streams (sc_memory.hip, ABI v3) ---------------------
  * What the reference's CuPy backend does with `xp.asarray(time_series)` on the way in and `.get()` on the way out
  * (transforms.py:405-439, connectivity.py:31-65): with these a host that has only ctypes + NumPy drives the whole path

@@ -166,6 +166,8 @@ SYMBOLS = {
     "sc_canonical_max_group": (c_int, []),
     "sc_canonical_coherence_f64": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_void_p, c_void_p,
                                            c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "sc_imaginary_interaction_f64": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_void_p, c_void_p,
+                                             c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sc_measure_f32": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_int, c_void_p, c_void_p]),
     # host-pointer side (sc_memory.hip)
     "sc_device_alloc": (c_int, [POINTER(c_void_p), c_size_t, c_void_p]),
@@ -251,6 +253,52 @@ def blockwise_batches(pairs, n_obs):
         batches[m] = (np.stack([it[0] for it in items]).astype(np.int32), np.array([it[1] for it in items], dtype=np.int32),
                       np.array([it[2] for it in items], dtype=np.int32))
     return batches, n_skipped
+
+
+def member_stride(max_group_size):
+    """Row length of the member table of sc_canonical_coherence_f64 / sc_imaginary_interaction_f64 for groups of at most
+    ``max_group_size`` channels (include/sc_hip.h): 16, 32 or 128."""
+    return 16 if max_group_size <= 16 else (32 if max_group_size <= 32 else 128)
+
+
+def member_table(groups):
+    """(members int32 [G][stride] channel indices, -1 padded; sizes int32 [G]; stride) of the int arrays ``groups``."""
+    import numpy as np
+    sizes = np.array([len(g) for g in groups], dtype=np.int32)
+    stride = member_stride(int(sizes.max()))
+    members = np.full((len(groups), stride), -1, dtype=np.int32)
+    for i, g in enumerate(groups):
+        members[i, :len(g)] = g
+    return members, sizes, stride
+
+
+def interaction_groups(group_labels, n_signals, max_group):
+    """Labels of maximized_imaginary_coherence / multivariate_interaction_measure, checked before any device work (both hosts):
+    (labels, members, sizes, stride) -- ``labels`` = np.unique of ``group_labels``, then member_table of the groups in that
+    order.  ValueError for a label list of the wrong length, fewer than two groups and a group of more than ``max_group``
+    channels (sc_canonical_max_group())."""
+    import numpy as np
+    group_labels = np.asarray(group_labels)
+    if group_labels.ndim != 1 or len(group_labels) != n_signals:
+        raise ValueError(f"group_labels must have one label per signal ({n_signals}), got {group_labels.shape}")
+    labels = np.unique(group_labels)
+    if len(labels) < 2:
+        raise ValueError(f"imaginary interaction needs at least two groups of signals (got {len(labels)})")
+    groups = [np.flatnonzero(group_labels == lab) for lab in labels]
+    for lab, g in zip(labels, groups):
+        if len(g) > max_group:
+            raise ValueError(f"imaginary interaction: group {lab.item()!r} has {len(g)} channels; a group may have at most "
+                             f"{max_group}")
+    return (labels,) + member_table(groups)
+
+
+def interaction_kept(sizes, n_obs):
+    """Groups whose real cross-spectral block can be positive definite: Re S_gg has rank at most 2 n_obs, so the groups of more
+    channels are left out (NaN) before any device work -- the kernels' Cholesky may round such a block to a tiny positive pivot.
+    Returns (indices of the kept groups, number left out)."""
+    import numpy as np
+    keep = np.flatnonzero(np.asarray(sizes) <= 2 * n_obs)
+    return keep, len(sizes) - len(keep)
 
 
 def library_path():

@@ -10,7 +10,7 @@ the hot-path measures.  All arithmetic runs on an MI355X through ``libsc_hip.so`
                        for few channels, the f32-MFMA / per-plane VALU kernels for strided spectra (sc_csm.hip, sc_nonlinear.hip)
         float64 engine (dtype=complex128, the default): fp64 matrix cores + fp64 VALU, double records (sc_f64.hip)
     measure algebra, eps clamps, NaN diagonals  -> fp64 epilogue, several measures per launch (sc_measure.hip)
-    pairwise Granger / full Wilson + MVAR measures / canonical / global coherence -> sc_wilson.hip, sc_wilson_fft.hip,
+    pairwise Granger / full Wilson + MVAR measures / canonical / global coherence / MIC, MIM -> sc_wilson.hip, sc_wilson_fft.hip,
         sc_mvar.hip, sc_canonical.hip, sc_global.hip (fp64)
 
 There is no NumPy fallback: without the HIP extension / a GPU every measure raises.
@@ -629,6 +629,70 @@ class Connectivity:
 
     def _canonical_gather(self, part, n_bins, per):
         return part
+
+    # ---- multivariate imaginary coherence (Ewald, Marzetti, Zappasodi, Meinecke & Nolte 2012) ----------------
+    def maximized_imaginary_coherence(self, group_labels):
+        """Maximized imaginary coherence (MIC) between each pair of channel groups: the largest singular value of
+        (Re S_aa)^-1/2 Im S_ab (Re S_bb)^-1/2, in [0, 1].  Like imaginary_coherence, instantaneous mixing (volume conduction,
+        source leakage) cannot create it: it is 0 wherever the cross-spectrum is real, and real invertible mixing inside a group
+        leaves it unchanged.  With one channel per group it is |imaginary_coherence()|.
+
+        Returns (array [kept axes..., n_frequencies, n_groups, n_groups] float64, symmetric with a NaN diagonal,
+        np.unique(group_labels)); the expectation is the object's ``expectation_type``.  Groups of up to
+        sc_canonical_max_group() = 128 channels (sc_canonical.hip).  A group of more than 2 n_observations channels has a
+        singular real block: its pairs are NaN (one warning counts the groups), as are the pairs with a block the device
+        reports not positive definite (one warning).
+        """
+        mic, _, labels = self._imaginary_interaction(group_labels)
+        return mic, labels
+
+    def multivariate_interaction_measure(self, group_labels):
+        """Multivariate interaction measure (MIM) between each pair of channel groups: the sum of the squared singular values of
+        (Re S_aa)^-1/2 Im S_ab (Re S_bb)^-1/2 = tr((Re S_aa)^-1 Im S_ab (Re S_bb)^-1 Im S_ab^T), in [0, min(n_a, n_b)];
+        MIC^2 <= MIM <= min(n_a, n_b) MIC^2.  Returns, computes and limits as maximized_imaginary_coherence (one device call
+        gives both)."""
+        _, mim, labels = self._imaginary_interaction(group_labels)
+        return mim, labels
+
+    def _interaction_groups(self, group_labels):
+        return _lib.interaction_groups(group_labels, self._shape5[4], int(_lib.load().sc_canonical_max_group()))
+
+    def _interaction_kept(self, sizes, n_obs_total):
+        keep, n_out = _lib.interaction_kept(sizes, n_obs_total)
+        if n_out:
+            logger.warning(f"imaginary interaction: {n_out} groups have more channels than twice the {n_obs_total} observations "
+                           "(singular real cross-spectral blocks): NaN")
+        return keep
+
+    def _interaction_failed(self, n_fail):
+        if n_fail:
+            logger.warning(f"imaginary interaction: {n_fail} group pairs have a real cross-spectral block that is not positive "
+                           "definite (NaN output)")
+
+    def _imaginary_interaction(self, group_labels):
+        from . import engine
+        import torch
+        labels, members, sizes, _ = self._interaction_groups(group_labels)      # (the labels are checked before any device work)
+        accum, n_obs, _ = self._csm_records("interaction", two_sided=False)
+        n_total = self._n_observations_total(n_obs)
+        keep = self._interaction_kept(sizes, n_total)
+        G = len(labels)
+        lo, hi, per = self._canonical_bins(accum.shape[0])
+        mic = torch.full((max(hi - lo, 0), G, G), float("nan"), dtype=torch.float64, device=accum.device)
+        mim = mic.clone()
+        n_fail = 0
+        if hi > lo and len(keep) >= 2:
+            sub_members, sub_sizes, _ = _lib.member_table([members[k, :sizes[k]] for k in keep])
+            a, b, n_fail = engine.imaginary_interaction(accum[lo:hi], self._shape5[4], _lib.PLANE_CSM, n_total, sub_members,
+                                                        sub_sizes)
+            idx = torch.as_tensor(keep, device=accum.device)
+            mic[:, idx[:, None], idx[None, :]] = a
+            mim[:, idx[:, None], idx[None, :]] = b
+        mic = self._canonical_gather(mic, accum.shape[0], per)
+        mim = self._canonical_gather(mim, accum.shape[0], per)
+        self._interaction_failed(n_fail)
+        shape = self._kept_shape() + (self._n_freq, G, G)
+        return engine.to_host(mic).reshape(shape), engine.to_host(mim).reshape(shape), labels
 
     def conditional_spectral_granger_prediction(self):
         """Power at node i explained by node j given every other signal, out[..., i, j] = j -> i | rest (diagonal NaN;

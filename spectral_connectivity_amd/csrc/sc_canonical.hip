@@ -11,6 +11,12 @@
 // eigenvalue of a c_g x c_g Hermitian matrix (cyclic complex Jacobi, eigenvalues only).
 // One thread per (bin, group pair), fp64, matrices in per-lane scratch: the work is
 // O(bins * pairs * c^3) and tiny next to stage B.
+//
+// The same kernels give the multivariate imaginary coherence of Ewald, Marzetti, Zappasodi, Meinecke & Nolte 2012
+// (NeuroImage 62:1964-1971) through a second READ VIEW of the records (template parameter IM): group blocks Re S_gg, cross
+// blocks i Im S_gh.  M = L_a^-1 (i Im S_ab) L_b^-H with L_g L_g^T = Re S_gg has the singular values of
+// D = (Re S_aa)^-1/2 Im S_ab (Re S_bb)^-1/2, so lambda_max(M M^H) = MIC^2 and trace(M M^H) = MIM = tr((Re S_aa)^-1 Im S_ab
+// (Re S_bb)^-1 Im S_ab^T) -- no other eigen-solver.
 #include <math.h>
 #include <stdlib.h>
 #include "sc_common.h"
@@ -31,6 +37,7 @@ struct CanonArgs {
     int mstride;              // row length of `members` for the workgroup-per-problem kernels (32 or CBIG_C)
     double jtol;
     double n_obs;
+    double* out_mim;          // interaction view: [n_bins][G][G] MIM (`out` then holds MIC)
 };
 
 __device__ inline cd csm_read(ScRec rec, const CanonArgs& a, int i, int j) {
@@ -43,6 +50,31 @@ __device__ inline cd csm_read(ScRec rec, const CanonArgs& a, int i, int j) {
     if (m) im = -im;
     if (i == j) im = 0.0;
     return make_double2(re, im);
+}
+
+// the records as the kernels read them: S (IM = false: canonical coherence) or the interaction view (IM = true) -- a group
+// block entry as (Re S_ij, 0), a cross block entry as (0, Im S_ij)
+template <bool IM>
+__device__ inline cd csm_group(ScRec rec, const CanonArgs& a, int i, int j) {
+    const cd s = csm_read(rec, a, i, j);
+    return IM ? make_double2(s.x, 0.0) : s;
+}
+template <bool IM>
+__device__ inline cd csm_cross(ScRec rec, const CanonArgs& a, int i, int j) {
+    const cd s = csm_read(rec, a, i, j);
+    return IM ? make_double2(0.0, s.y) : s;
+}
+
+// interaction view: MIC = sqrt(lambda_max) and MIM = trace(B) of a pair; B is positive semi-definite, so lambda_max <= trace(B)
+// (the clamp keeps MIC^2 <= MIM to the last bit and makes MIC exactly 0 where B is 0).  NaN for both when a block failed.
+__device__ inline void canon_store_interaction(const CanonArgs& a, int64_t bin, int ga, int gb, double lmax, double tr, bool ok) {
+    const double mic = ok ? sqrt(fmin(fmax(lmax, 0.0), tr)) : nan(""), mim = ok ? tr : nan("");
+    double* o = a.out + bin * a.G * a.G;
+    double* p = a.out_mim + bin * a.G * a.G;
+    o[ga * a.G + gb] = mic;
+    o[gb * a.G + ga] = mic;
+    p[ga * a.G + gb] = mim;
+    p[gb * a.G + ga] = mim;
 }
 
 // in-place lower Cholesky of Hermitian positive-definite n x n (row-major, stride CMAX)
@@ -190,6 +222,7 @@ __device__ inline double cb_wave_sum(double v) {
 #ifndef CB_SWEEPS
 #define CB_SWEEPS 12
 #endif
+template <bool IM>
 __global__ void __launch_bounds__(64 * CB_WAVES) canonical_factor_kernel(CanonArgs a, cd* Lg, int* okb) {
     extern __shared__ __align__(16) unsigned char cb_smem[];
     const int G = a.G;
@@ -205,7 +238,7 @@ __global__ void __launch_bounds__(64 * CB_WAVES) canonical_factor_kernel(CanonAr
         cd* L = Ls + (size_t)wave * CB_C * CB_C;
         for (int e = lane; e < CB_C * CB_C; e += 64) {
             const int i = e / CB_C, j = e % CB_C;
-            L[e] = (i < n && j < n) ? csm_read(rec, a, mg[i], mg[j]) : make_double2(0.0, 0.0);
+            L[e] = (i < n && j < n) ? csm_group<IM>(rec, a, mg[i], mg[j]) : make_double2(0.0, 0.0);
         }
         CB_WSYNC();
         int ok = 1;
@@ -537,6 +570,7 @@ __device__ double cb_top_eigenvalue(cd (&a)[4], cd* vb, int lane) {
     return 0.5 * (lo + hi) * top;
 }
 
+template <bool IM>
 __global__ void __launch_bounds__(64 * CB_WAVES) canonical_pair_hh_kernel(CanonArgs a, const cd* Lg, const int* okb) {
     extern __shared__ __align__(16) unsigned char cb_smem[];
     const int G = a.G;
@@ -564,7 +598,7 @@ __global__ void __launch_bounds__(64 * CB_WAVES) canonical_pair_hh_kernel(CanonA
     const bool ok = okg[ga] && okg[gb];
     for (int e = lane; e < CB_C * CB_C; e += 64) {
         const int i = e / CB_C, j = e % CB_C;
-        M[e] = (i < na && j < nb) ? csm_read(rec, a, ma[i], mb[j]) : make_double2(0.0, 0.0);
+        M[e] = (i < na && j < nb) ? csm_cross<IM>(rec, a, ma[i], mb[j]) : make_double2(0.0, 0.0);
     }
     CB_WSYNC();
     // M <- Linv_a M Linv_b^H as two dense products through T (the inverse factors come from the workspace: L2)
@@ -606,12 +640,24 @@ __global__ void __launch_bounds__(64 * CB_WAVES) canonical_pair_hh_kernel(CanonA
             breg[c] = sv;
         }
     }
+    double tr = 0.0;                                      // interaction view: trace(B), the diagonal of breg summed over the wave
+    if constexpr (IM) {
+        const int i = lane & 15, jq = lane >> 4;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) tr += (4 * jq + c == i) ? breg[c].x : 0.0;
+        tr = cb_wave_sum(tr);
+    }
     double lmax = cb_top_eigenvalue(breg, vb, lane);
     if (lane == 0) {
-        if (!ok) { lmax = nan(""); atomicAdd(a.fail, 1); }
-        double* o = a.out + bin * G * G;
-        o[ga * G + gb] = lmax;
-        o[gb * G + ga] = lmax;
+        if constexpr (IM) {
+            if (!ok) atomicAdd(a.fail, 1);
+            canon_store_interaction(a, bin, ga, gb, lmax, tr, ok);
+        } else {
+            if (!ok) { lmax = nan(""); atomicAdd(a.fail, 1); }
+            double* o = a.out + bin * G * G;
+            o[ga * G + gb] = lmax;
+            o[gb * G + ga] = lmax;
+        }
     }
 }
 
@@ -764,12 +810,13 @@ __global__ void __launch_bounds__(256) canonical_big_kernel(CanonArgs a, cd* scr
 #define CBH_LDS_N 96
 #define CBH_SMALL 64           // pairs of groups of at most this many channels are processed in LDS entirely
 #define CBH_LD 65              // their row length (odd: a column walk touches every bank)
+template <bool IM>
 __global__ void __launch_bounds__(256) canonical_big_hh_kernel(CanonArgs a, cd* scratch, int64_t n_items, int small_n, int small_ld) {
     extern __shared__ __align__(16) unsigned char cb_smem[];
     cd* Bl = reinterpret_cast<cd*>(cb_smem);                 // CBH_LDS_N^2 elements: B (column-major) or, for pairs of groups of at
     __shared__ double dg[CBIG_C], e2[CBIG_C];                // most CBH_SMALL channels, the whole problem (one factor block + M)
     __shared__ cd vs[CBIG_C], ws[CBIG_C];
-    __shared__ double red4[4], sh[4];
+    __shared__ double red4[4], sh[2];
     __shared__ int bad, first_above;
     const int tid = threadIdx.x;
     // (scratch == nullptr: every pair of this launch fits LDS -- small_n is the largest group -- and the three pointers are never used)
@@ -797,8 +844,8 @@ __global__ void __launch_bounds__(256) canonical_big_hh_kernel(CanonArgs a, cd* 
         cd* PM = small ? Bl + small_n * small_ld : Mg;
         const int ld = small ? small_ld : CBIG_C;
         if (tid == 0) bad = 0;
-        for (int e = tid; e < na * na; e += 256) { const int i = e / na, j = e % na; if (j <= i) PA[i * ld + j] = csm_read(rec, a, ma[i], ma[j]); }
-        for (int e = tid; e < na * nb; e += 256) { const int i = e / nb, j = e % nb; PM[i * ld + j] = csm_read(rec, a, ma[i], mb[j]); }
+        for (int e = tid; e < na * na; e += 256) { const int i = e / na, j = e % na; if (j <= i) PA[i * ld + j] = csm_group<IM>(rec, a, ma[i], ma[j]); }
+        for (int e = tid; e < na * nb; e += 256) { const int i = e / nb, j = e % nb; PM[i * ld + j] = csm_cross<IM>(rec, a, ma[i], mb[j]); }
         __syncthreads();
         sc_wg_cholesky(PA, ld, na, &bad);
         // M <- L_a^-1 M, right-looking: row k is final once it is divided by L_a[k][k]; every row below loses its multiple of it
@@ -816,7 +863,7 @@ __global__ void __launch_bounds__(256) canonical_big_hh_kernel(CanonArgs a, cd* 
             }
             __syncthreads();
         }
-        for (int e = tid; e < nb * nb; e += 256) { const int i = e / nb, j = e % nb; if (j <= i) PB[i * ld + j] = csm_read(rec, a, mb[i], mb[j]); }
+        for (int e = tid; e < nb * nb; e += 256) { const int i = e / nb, j = e % nb; if (j <= i) PB[i * ld + j] = csm_group<IM>(rec, a, mb[i], mb[j]); }
         __syncthreads();
         sc_wg_cholesky(PB, ld, nb, &bad);
         // M <- M L_b^-H: column k is final once it is divided by L_b[k][k]; every column to its right loses conj(L_b[j][k]) times it
@@ -942,10 +989,17 @@ __global__ void __launch_bounds__(256) canonical_big_hh_kernel(CanonArgs a, cd* 
         }
         if (tid == 0) {
             double v = 0.5 * (lo + hi);
-            if (bad) { v = nan(""); atomicAdd(a.fail, 1); }
-            double* o = a.out + bin * a.G * a.G;
-            o[ga * a.G + gb] = v;
-            o[gb * a.G + ga] = v;
+            if constexpr (IM) {
+                double tr = 0.0;                             // trace(B) = trace(T): the reflections are unitary similarities
+                for (int i = 0; i < na; ++i) tr += dg[i];
+                if (bad) atomicAdd(a.fail, 1);
+                canon_store_interaction(a, bin, ga, gb, v, tr, !bad);
+            } else {
+                if (bad) { v = nan(""); atomicAdd(a.fail, 1); }
+                double* o = a.out + bin * a.G * a.G;
+                o[ga * a.G + gb] = v;
+                o[gb * a.G + ga] = v;
+            }
         }
         __syncthreads();
     }
@@ -953,21 +1007,24 @@ __global__ void __launch_bounds__(256) canonical_big_hh_kernel(CanonArgs a, cd* 
 
 extern "C" int sc_canonical_max_group(void) { return CBIG_C; }
 
-extern "C" int sc_canonical_coherence_f64(const void* d_accum, int64_t n_bins, int64_t n_signals, uint32_t planes,
-                                          int64_t n_observations, const int32_t* d_members, const int32_t* d_sizes,
-                                          int n_groups, int max_group_size, double* d_out, int32_t* d_fail,
-                                          void* stream) {
-    ScTimed timed_("canonical_coherence", stream);
-    SC_REQUIRE(d_accum && d_members && d_sizes && d_out && d_fail, "NULL argument");
+// The launches of both entry points: the tier of the largest group (<= 16 channels: factor + pair kernels; <= 64: a workgroup per
+// pair in LDS; <= 128: the same with the blocks in a global scratch) and its workspace.  IM: the interaction view, MIC into `out`
+// and MIM into `out_mim`; it always takes the Householder / Sturm kernels (SC_CANON_EIG=jacobi selects the Jacobi kernels of
+// canonical coherence only).  The entry points check their pointers first.
+template <bool IM>
+static int canonical_launch(const char* what, const void* d_accum, int64_t n_bins, int64_t n_signals, uint32_t planes,
+                            int64_t n_observations, const int32_t* d_members, const int32_t* d_sizes, int n_groups,
+                            int max_group_size, double* d_out, double* d_out_mim, int32_t* d_fail, void* stream) {
     SC_REQUIRE(planes & SC_PLANE_CSM, "accumulator record must contain SC_PLANE_CSM");
     SC_REQUIRE(n_groups >= 1 && n_bins >= 1, "empty problem");
     if (max_group_size > CBIG_C) {
-        sc_set_error("canonical coherence supports groups of at most %d channels (got %d)", CBIG_C, max_group_size);
+        sc_set_error("%s supports groups of at most %d channels (got %d)", what, CBIG_C, max_group_size);
         return SC_EUNSUPPORTED;
     }
     hipStream_t st = (hipStream_t)stream;
     CanonArgs a;
     a.accum = sc_rec(d_accum, planes); a.members = d_members; a.sizes = d_sizes; a.out = d_out; a.fail = d_fail;
+    a.out_mim = d_out_mim;
     a.n_bins = n_bins; a.G = n_groups; a.n_gpairs = n_groups * (n_groups - 1) / 2;
     a.NB = sc_n_blocks(n_signals); a.n_tiles = sc_n_tiles(a.NB);
     a.floats_per_bin = (int64_t)sc_plane_count(planes) * a.n_tiles * SC_TILE_ELEMS;
@@ -977,8 +1034,15 @@ extern "C" int sc_canonical_coherence_f64(const void* d_accum, int64_t n_bins, i
     a.jtol = 1e-24;          // off^2 <= jtol dia^2: eigenvalues to ~1e-12 relative (quadratic convergence)
     const int64_t total_out = n_bins * n_groups * n_groups;
     hipLaunchKernelGGL(canon_fill_nan, dim3((unsigned)((total_out + 255) / 256)), dim3(256), 0, st, d_out, total_out);
+    if (IM) {
+        hipLaunchKernelGGL(canon_fill_nan, dim3((unsigned)((total_out + 255) / 256)), dim3(256), 0, st, d_out_mim, total_out);
+    }
     (void)hipMemsetAsync(d_fail, 0, 4, st);
     const int64_t threads = n_bins * a.n_gpairs;
+    // (SC_CANON_EIG=jacobi: the parallel Jacobi kernels of rounds 1-4, every eigenvalue of B -- canonical coherence only, A/B and
+    //  cross-check)
+    const char* eig = sc_switch(SC_SW_CANON_EIG);
+    const bool jacobi = !IM && eig && eig[0] == 'j';
     if (threads > 0) {
         const unsigned blocks = (unsigned)((threads + 63) / 64);
         // members stride must match the instantiated CMAX
@@ -988,34 +1052,32 @@ extern "C" int sc_canonical_coherence_f64(const void* d_accum, int64_t n_bins, i
             const size_t lg_bytes = (size_t)n_bins * n_groups * CB_C * CB_C * sizeof(cd);
             const size_t ok_bytes = (((size_t)n_bins * n_groups * sizeof(int)) + 255) & ~(size_t)255;
             if (hipMallocAsync((void**)&Lg, lg_bytes + ok_bytes, st) != hipSuccess) {
-                sc_set_error("canonical coherence: workspace allocation of %zu bytes failed", lg_bytes + ok_bytes);
+                sc_set_error("%s: workspace allocation of %zu bytes failed", what, lg_bytes + ok_bytes);
                 return SC_ENOMEM;
             }
             int* okb = reinterpret_cast<int*>(reinterpret_cast<char*>(Lg) + lg_bytes);
             const size_t lds_f = (size_t)CB_WAVES * CB_C * CB_C * sizeof(cd);
             const size_t lds_p = (size_t)CB_WAVES * 2 * CB_C * CB_C * sizeof(cd) + CB_WAVES * 24 * 8;
             (void)hipFuncSetAttribute((const void*)canonical_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p);
-            hipLaunchKernelGGL(canonical_factor_kernel, dim3((unsigned)n_bins), dim3(64 * CB_WAVES), lds_f, st, a, Lg, okb);
+            hipLaunchKernelGGL(canonical_factor_kernel<IM>, dim3((unsigned)n_bins), dim3(64 * CB_WAVES), lds_f, st, a, Lg, okb);
             const int64_t n_gp = a.n_gpairs;
             const int64_t n_wg = ((n_gp + CB_WAVES - 1) / CB_WAVES) * n_bins;
-            if (n_wg > 0x7fffffffLL) { (void)hipFreeAsync(Lg, st); sc_set_error("canonical coherence: too many (bin, pair) tasks"); return SC_EINVAL; }
-            // (SC_CANON_EIG=jacobi: the parallel Jacobi of rounds 1-4, all sixteen eigenvalues -- A/B and cross-check)
-            const char* eig = sc_switch(SC_SW_CANON_EIG);
-            if (eig && eig[0] == 'j') {
+            if (n_wg > 0x7fffffffLL) { (void)hipFreeAsync(Lg, st); sc_set_error("%s: too many (bin, pair) tasks", what); return SC_EINVAL; }
+            if (jacobi) {
                 hipLaunchKernelGGL(canonical_pair_kernel, dim3((unsigned)n_wg), dim3(64 * CB_WAVES), lds_p, st, a, (const cd*)Lg,
                                    (const int*)okb);
             } else {
                 const size_t lds_h = (size_t)CB_WAVES * (2 * CB_C * CB_C + 32) * sizeof(cd);
-                (void)hipFuncSetAttribute((const void*)canonical_pair_hh_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h);
-                hipLaunchKernelGGL(canonical_pair_hh_kernel, dim3((unsigned)n_wg), dim3(64 * CB_WAVES), lds_h, st, a, (const cd*)Lg,
+                (void)hipFuncSetAttribute((const void*)canonical_pair_hh_kernel<IM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h);
+                hipLaunchKernelGGL(canonical_pair_hh_kernel<IM>, dim3((unsigned)n_wg), dim3(64 * CB_WAVES), lds_h, st, a, (const cd*)Lg,
                                    (const int*)okb);
             }
             (void)hipFreeAsync(Lg, st);
-        } else if (max_group_size <= 32 && sc_switch(SC_SW_CANON_EIG) && sc_switch(SC_SW_CANON_EIG)[0] == 'j') {
+        } else if (max_group_size <= 32 && jacobi) {
             // (rounds 1-5: a wave per problem, its three blocks in the lanes' scratch, Jacobi -- 134 ms for 8 groups of 32 x 513 bins
             //  where the workgroup-per-problem kernel below takes 22: kept for A/B and cross-check only)
             hipLaunchKernelGGL(canonical_kernel<32>, dim3(blocks), dim3(64), 0, st, a);
-        } else if (max_group_size <= CBH_SMALL && !(sc_switch(SC_SW_CANON_EIG) && sc_switch(SC_SW_CANON_EIG)[0] == 'j')) {
+        } else if (max_group_size <= CBH_SMALL && !jacobi) {
             // every pair fits LDS: no scratch, and as many persistent workgroups per compute unit as their LDS allows
             const int sn = max_group_size, sld = max_group_size | 1;
             const size_t lds = (size_t)2 * sn * sld * sizeof(cd);
@@ -1023,19 +1085,18 @@ extern "C" int sc_canonical_coherence_f64(const void* d_accum, int64_t n_bins, i
             per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
             const int64_t want = (int64_t)256 * per_cu;
             const int slots = (int)(threads < want ? threads : want);
-            SC_CHECK_HIP(hipFuncSetAttribute((const void*)canonical_big_hh_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(canonical_big_hh_kernel, dim3((unsigned)slots), dim3(256), lds, st, a, (cd*)nullptr, threads, sn, sld);
+            SC_CHECK_HIP(hipFuncSetAttribute((const void*)canonical_big_hh_kernel<IM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(canonical_big_hh_kernel<IM>, dim3((unsigned)slots), dim3(256), lds, st, a, (cd*)nullptr, threads, sn, sld);
         } else {
             // (members stride CBIG_C) persistent workgroups, three C x C matrices each in a stream-ordered scratch
             const int slots = (int)(threads < 256 ? threads : 256);
             cd* scratch = nullptr;
             const size_t sbytes = (size_t)slots * 3 * CBIG_C * CBIG_C * sizeof(cd);
             if (hipMallocAsync((void**)&scratch, sbytes, st) != hipSuccess) {
-                sc_set_error("canonical coherence: scratch allocation of %zu bytes failed", sbytes);
+                sc_set_error("%s: scratch allocation of %zu bytes failed", what, sbytes);
                 return SC_ENOMEM;
             }
-            const char* eig = sc_switch(SC_SW_CANON_EIG);       // (=jacobi: the round-2 kernel, every eigenvalue of B -- A/B and cross-check)
-            if (eig && eig[0] == 'j') {
+            if (jacobi) {                  // (the round-2 kernel, every eigenvalue of B -- A/B and cross-check)
                 constexpr size_t HM = CBIG_C / 2;
                 const size_t lds = (size_t)CBIG_C * (CBIG_C + 1) / 2 * sizeof(cd) + HM * 8 + HM * 16 + 2 * HM * 4 +
                                    HM * (HM + 1) * 2 + 64;
@@ -1043,12 +1104,32 @@ extern "C" int sc_canonical_coherence_f64(const void* d_accum, int64_t n_bins, i
                 hipLaunchKernelGGL(canonical_big_kernel, dim3((unsigned)slots), dim3(256), lds, st, a, scratch, threads);
             } else {
                 const size_t lds = (size_t)CBH_LDS_N * CBH_LDS_N * sizeof(cd);
-                SC_CHECK_HIP(hipFuncSetAttribute((const void*)canonical_big_hh_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(canonical_big_hh_kernel, dim3((unsigned)slots), dim3(256), lds, st, a, scratch, threads, CBH_SMALL, CBH_LD);
+                SC_CHECK_HIP(hipFuncSetAttribute((const void*)canonical_big_hh_kernel<IM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                hipLaunchKernelGGL(canonical_big_hh_kernel<IM>, dim3((unsigned)slots), dim3(256), lds, st, a, scratch, threads, CBH_SMALL, CBH_LD);
             }
             (void)hipFreeAsync(scratch, st);
         }
     }
     SC_CHECK_HIP(hipGetLastError());
     return SC_OK;
+}
+
+extern "C" int sc_canonical_coherence_f64(const void* d_accum, int64_t n_bins, int64_t n_signals, uint32_t planes,
+                                          int64_t n_observations, const int32_t* d_members, const int32_t* d_sizes,
+                                          int n_groups, int max_group_size, double* d_out, int32_t* d_fail,
+                                          void* stream) {
+    ScTimed timed_("canonical_coherence", stream);
+    SC_REQUIRE(d_accum && d_members && d_sizes && d_out && d_fail, "NULL argument");
+    return canonical_launch<false>("canonical coherence", d_accum, n_bins, n_signals, planes, n_observations, d_members, d_sizes,
+                                   n_groups, max_group_size, d_out, nullptr, d_fail, stream);
+}
+
+extern "C" int sc_imaginary_interaction_f64(const void* d_accum, int64_t n_bins, int64_t n_signals, uint32_t planes,
+                                            int64_t n_observations, const int32_t* d_members, const int32_t* d_sizes,
+                                            int n_groups, int max_group_size, double* d_mic, double* d_mim,
+                                            int32_t* d_fail, void* stream) {
+    ScTimed timed_("imaginary_interaction", stream);
+    SC_REQUIRE(d_accum && d_members && d_sizes && d_mic && d_mim && d_fail, "NULL argument");
+    return canonical_launch<true>("imaginary interaction", d_accum, n_bins, n_signals, planes, n_observations, d_members, d_sizes,
+                                  n_groups, max_group_size, d_mic, d_mim, d_fail, stream);
 }

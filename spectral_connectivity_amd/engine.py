@@ -896,6 +896,22 @@ def canonical_coherence(accum, n_signals, planes, n_obs, groups):
     return out, int(fail.item())
 
 
+def imaginary_interaction(accum, n_signals, planes, n_obs, members, sizes):
+    """members / sizes: _lib.member_table of the groups.  Returns (MIC, MIM [n_bins, G, G] float64, n_fail)."""
+    lib = _lib.load()
+    dev = accum.device
+    G = len(sizes)
+    members_t, sizes_t = torch.from_numpy(members).to(dev), torch.from_numpy(sizes).to(dev)
+    n_bins = accum.shape[0]
+    mic = torch.empty((n_bins, G, G), dtype=torch.float64, device=dev)
+    mim = torch.empty((n_bins, G, G), dtype=torch.float64, device=dev)
+    fail = torch.zeros((1,), dtype=torch.int32, device=dev)
+    _lib.check(lib.sc_imaginary_interaction_f64(_ptr(accum), n_bins, n_signals, rec_planes(accum, planes), n_obs, _ptr(members_t),
+                                                _ptr(sizes_t), G, int(sizes.max()), _ptr(mic), _ptr(mim), _ptr(fail), _stream()),
+               "sc_imaginary_interaction_f64")
+    return mic, mim, int(fail.item())
+
+
 class GraphedMeasures:
     """Stage A, stage B and the epilogue of ONE fixed request, captured once in a hipGraph and replayed per time series.
 

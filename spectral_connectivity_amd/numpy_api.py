@@ -11,8 +11,8 @@
 imported.  Same constructor, properties, methods, shapes, dtypes, warnings and errors as the PyTorch-host class (it IS that class:
 only the methods that touch the device are replaced), both engines (``dtype=complex64`` -> float32 engine, planes format
 included; ``complex128``, the default -> float64 engine), every expectation-type measure, pairwise / subset Granger, the full
-Wilson factor and the directed MVAR measures, canonical and global coherence, the band statistics, more than 256 signals (channel
-blocks of 128, tiled on the host).  Not here: complex-valued time series, multi-GPU (``parallel.ShardedConnectivity`` needs
+Wilson factor and the directed MVAR measures, canonical and global coherence, MIC / MIM, the band statistics, more than 256
+signals (channel blocks of 128, tiled on the host).  Not here: complex-valued time series, multi-GPU (``parallel.ShardedConnectivity`` needs
 ``torch.distributed``), hipGraph replay (``engine.GraphedMeasures``).
 """
 import ctypes
@@ -561,3 +561,29 @@ class Connectivity(_TorchHostConnectivity):
                 logger.warning(f"{n_fail} group cross-spectral blocks were not positive definite (NaN output)")
         W = self._shape5[0]
         return res.reshape(W, self._n_freq, n_g, n_g), labels
+
+    def _imaginary_interaction(self, group_labels):
+        h, lib = host(), host().lib
+        labels, members, sizes, _ = self._interaction_groups(group_labels)      # (the labels are checked before any device work)
+        rec, n_obs, _ = self._csm_records("interaction", two_sided=False)
+        n_total = self._n_observations_total(n_obs)
+        keep = self._interaction_kept(sizes, n_total)
+        G, n_bins, C = len(labels), rec.n_bins, self._shape5[4]
+        mic, mim = np.full((n_bins, G, G), np.nan), np.full((n_bins, G, G), np.nan)
+        if len(keep) >= 2:
+            sub_members, sub_sizes, _ = _lib.member_table([members[k, :sizes[k]] for k in keep])
+            g = len(keep)
+            d_members, d_sizes = h.upload(sub_members), h.upload(sub_sizes)
+            d_mic, d_mim, fail = h.alloc(n_bins * g * g * 8), h.alloc(n_bins * g * g * 8), h.alloc(4)
+            _lib.check(lib.sc_imaginary_interaction_f64(rec.buf.ptr, n_bins, C, rec.planes(_lib.PLANE_CSM), n_total, d_members.ptr,
+                                                        d_sizes.ptr, g, int(sub_sizes.max()), d_mic.ptr, d_mim.ptr, fail.ptr,
+                                                        h.stream), "sc_imaginary_interaction_f64")
+            cells = np.ix_(np.arange(n_bins), keep, keep)
+            mic[cells] = h.download(d_mic, (n_bins, g, g), np.float64)
+            mim[cells] = h.download(d_mim, (n_bins, g, g), np.float64)
+            n_fail = int(h.download(fail, (1,), np.int32)[0])
+            for b in (d_members, d_sizes, d_mic, d_mim, fail):
+                b.free()
+            self._interaction_failed(n_fail)
+        shape = self._kept_shape() + (self._n_freq, G, G)
+        return mic.reshape(shape), mim.reshape(shape), labels

@@ -453,7 +453,7 @@ class ShardedConnectivity(_connectivity_base()):
       over bins -> epilogue on the owned 1/N of the bins with the job-wide n_observations -> all-gather;
     * pairwise spectral Granger: records all-reduced once, the channel pairs dealt out over the ranks, each rank
       factorises its pairs, one merge of the disjoint outputs;
-    * canonical coherence: records all-reduced once, the bins split over the ranks, all-gather of the owned bins;
+    * canonical coherence, MIC / MIM: records all-reduced once, the bins split over the ranks, all-gather of the owned bins;
     * the full Wilson factor / MVAR measures and global coherence: records all-reduced, then computed redundantly
       (one C x C problem per window: nothing to deal out below the window count).
 
