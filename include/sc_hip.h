@@ -585,6 +585,46 @@ int sc_imaginary_interaction_f64(const void* d_accum, int64_t n_bins, int64_t n_
                                  int n_groups, int max_group_size, double* d_mic, double* d_mim,
                                  int32_t* d_fail, void* stream);
 
+/* ---- delete-one jackknife of power and coherence (sc_jackknife.hip; additive, ABI v8) ------------------------
+ * Standard errors that rest on the data (Thomson & Chave 1991; Chronux coherencyc / mtspectrumc with err = [2 p]); the
+ * reference has only the closed forms of statistics.py.  Per kept index and bin the delete units u = 1 .. n hold g
+ * observations each, G_u = sum over the unit's observations of x_i conj(x_j), S = sum_u G_u is the un-normalised CSM record
+ * (SC_PLANE_CSM of sc_csm_accumulate_f32 / sc_accumulate_f64 ..., summed over every rank's trials), and for each measure
+ *     d_u = theta(S - G_u) - theta(S),
+ *     SC_JACKKNIFE_POWER                theta = ln(S_ii / n_observations_used)              [n_bins][C]
+ *     SC_JACKKNIFE_COHERENCE_MAGNITUDE  theta = atanh(|S_ij| / sqrt(S_ii S_jj))             [n_bins][C][C], diagonal NaN
+ *     SC_JACKKNIFE_IMAGINARY_COHERENCE  theta = Im(S_ij) / sqrt(S_ii S_jj), signed          [n_bins][C][C], antisymmetric, diagonal NaN
+ * over = SC_JACKKNIFE_OVER_TRIALS: a unit is everything one trial contributes (its reduced windows x tapers; needs
+ * desc->reduce_trial); SC_JACKKNIFE_OVER_OBSERVATIONS: every averaged observation is a unit (g = 1).  desc describes the spectra
+ * of THIS process (strides, reduce flags; n_freq bins from the first); units [unit_begin, unit_end) of them are walked, and
+ * n_units_total >= 2 is the unit count of the whole job (it enters the power statistic).  bin = kept group * n_freq + f as in the
+ * records.
+ *   d_out   double [sc_jackknife_layout out_doubles]: for each requested measure in the order above three arrays of the shape
+ *           given there -- theta(S), sum_u d_u, sum_u d_u^2 over the units walked (partial sums of different processes add).
+ *           A channel without power in a bin gives NaN in its entries.  The caller finishes: m = sum d / n,
+ *           bias corrected = theta - (n - 1) m, standard error = sqrt((n - 1) / n * (sum d^2 - n m^2)).
+ *   d_workspace  sc_jackknife_workspace_bytes (0 when bins x channel tile pairs fill the device; otherwise the units are split
+ *           over several workgroups whose partial sums are added in a fixed order).  No floating-point atomics: bit-identical
+ *           results from run to run.
+ * G_u is summed in the spectra's precision (_f32: complex64 spectra, _f64: complex128); the subtraction, the statistic and the
+ * sums are fp64 in both.  d_total: float records, or double with SC_RECORD_F64 in `planes`.  Any n_signals <= 32768 (the kernel
+ * tiles the channels itself). */
+#define SC_JACKKNIFE_POWER 0x1u
+#define SC_JACKKNIFE_COHERENCE_MAGNITUDE 0x2u
+#define SC_JACKKNIFE_IMAGINARY_COHERENCE 0x4u
+#define SC_JACKKNIFE_OVER_TRIALS 0
+#define SC_JACKKNIFE_OVER_OBSERVATIONS 1
+int sc_jackknife_layout(const sc_spectra_desc* desc, uint32_t measures, int over, int64_t* n_bins, int64_t* n_units,
+                        int64_t* unit_size, int64_t* out_doubles);
+int64_t sc_jackknife_workspace_bytes(const sc_spectra_desc* desc, uint32_t measures, int over, int64_t unit_begin,
+                                     int64_t unit_end);
+int sc_jackknife_f32(const void* d_X /*float2*/, const sc_spectra_desc* desc, const void* d_total, uint32_t planes,
+                     uint32_t measures, int over, int64_t unit_begin, int64_t unit_end, int64_t n_units_total, double* d_out,
+                     void* d_workspace, int64_t workspace_bytes, void* stream);
+int sc_jackknife_f64(const void* d_X /*double2*/, const sc_spectra_desc* desc, const void* d_total, uint32_t planes,
+                     uint32_t measures, int over, int64_t unit_begin, int64_t unit_end, int64_t n_units_total, double* d_out,
+                     void* d_workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- host-pointer side of the boundary: memory, copies, streams (sc_memory.hip, ABI v3) ---------------------
  * What the reference's CuPy backend does with `xp.asarray(time_series)` on the way in and `.get()` on the way out
  * (transforms.py:405-439, connectivity.py:31-65): with these a host that has only ctypes + NumPy drives the whole path

@@ -168,6 +168,12 @@ SYMBOLS = {
                                            c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sc_imaginary_interaction_f64": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_void_p, c_void_p,
                                              c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sc_jackknife_layout": (c_int, [POINTER(SpectraDesc), c_uint32, c_int, c_int64_p, c_int64_p, c_int64_p, c_int64_p]),
+    "sc_jackknife_workspace_bytes": (c_int64, [POINTER(SpectraDesc), c_uint32, c_int, c_int64, c_int64]),
+    "sc_jackknife_f32": (c_int, [c_void_p, POINTER(SpectraDesc), c_void_p, c_uint32, c_uint32, c_int, c_int64, c_int64, c_int64,
+                                 c_void_p, c_void_p, c_int64, c_void_p]),
+    "sc_jackknife_f64": (c_int, [c_void_p, POINTER(SpectraDesc), c_void_p, c_uint32, c_uint32, c_int, c_int64, c_int64, c_int64,
+                                 c_void_p, c_void_p, c_int64, c_void_p]),
     "sc_measure_f32": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_int, c_void_p, c_void_p]),
     # host-pointer side (sc_memory.hip)
     "sc_device_alloc": (c_int, [POINTER(c_void_p), c_size_t, c_void_p]),
@@ -299,6 +305,64 @@ def interaction_kept(sizes, n_obs):
     import numpy as np
     keep = np.flatnonzero(np.asarray(sizes) <= 2 * n_obs)
     return keep, len(sizes) - len(keep)
+
+
+# ---- delete-one jackknife (sc_jackknife.hip): the request, checked before any device work (both hosts) ----------------------------
+# measure name -> (bit of the `measures` mask of sc_jackknife_*, variance-stabilising transform, entries per bin: 1 = C, 2 = C x C);
+# dict order = order of the blocks in the library's output
+JACKKNIFE_MEASURES = {
+    "power": (0x1, "log", 1),
+    "coherence_magnitude": (0x2, "fisher_z", 2),
+    "imaginary_coherence": (0x4, "identity", 2),
+}
+JACKKNIFE_OVER = {"trials": 0, "observations": 1}
+
+
+def jackknife_request(measures, over, expectation_type, n_trials, n_observations):
+    """(names in output order, measures mask, `over` code, n_units) of Connectivity.jackknife; ValueError -- with the valid choices
+    spelled out -- for an empty or unknown measure list, a bad ``over``, an expectation that keeps the trial axis with
+    over="trials", and fewer than two delete units.  ``n_trials`` / ``n_observations``: of the whole job."""
+    if isinstance(measures, str):
+        measures = (measures,)
+    measures = tuple(measures)
+    valid = ", ".join(repr(k) for k in JACKKNIFE_MEASURES)
+    if not measures:
+        raise ValueError(f"jackknife: measures is empty; choose from {valid}")
+    unknown = [m for m in measures if m not in JACKKNIFE_MEASURES]
+    if unknown:
+        raise ValueError(f"jackknife: unknown measure {unknown[0]!r}; choose from {valid}")
+    if over not in JACKKNIFE_OVER:
+        raise ValueError(f"jackknife: over must be 'trials' or 'observations' (got {over!r})")
+    if over == "trials":
+        if 1 not in EXPECTATION_AXES[expectation_type]:
+            ok = ", ".join(repr(k) for k, axes in EXPECTATION_AXES.items() if 1 in axes)
+            raise ValueError(f"jackknife over trials needs an expectation_type that averages over trials ({ok}), got "
+                             f"{expectation_type!r}; use over='observations'")
+        n_units = int(n_trials)
+        if n_units < 2:
+            raise ValueError(f"jackknife over trials needs n_trials >= 2 (got {n_units}); use over='observations'")
+    else:
+        n_units = int(n_observations)
+        if n_units < 2:
+            raise ValueError(f"jackknife over observations needs n_observations >= 2 (got {n_units} with expectation_type "
+                             f"{expectation_type!r})")
+    names = [k for k in JACKKNIFE_MEASURES if k in measures]
+    mask = 0
+    for k in names:
+        mask |= JACKKNIFE_MEASURES[k][0]
+    return names, mask, JACKKNIFE_OVER[over], n_units
+
+
+def jackknife_blocks(names, n_bins, n_signals):
+    """[(name, first double, doubles per array, array shape)] of the library's output for the measures ``names`` (output order):
+    every block is three arrays -- theta(S), sum d, sum d^2."""
+    out, at = [], 0
+    for k in names:
+        shape = (n_bins, n_signals) if JACKKNIFE_MEASURES[k][2] == 1 else (n_bins, n_signals, n_signals)
+        size = n_bins * n_signals ** JACKKNIFE_MEASURES[k][2]
+        out.append((k, at, size, shape))
+        at += 3 * size
+    return out, at
 
 
 def library_path():

@@ -694,6 +694,68 @@ class Connectivity:
         shape = self._kept_shape() + (self._n_freq, G, G)
         return engine.to_host(mic).reshape(shape), engine.to_host(mim).reshape(shape), labels
 
+    # ---- delete-one jackknife standard errors (Thomson & Chave 1991; Chronux err = [2 p]) --------------------
+    def jackknife(self, measures=("coherence_magnitude",), over="trials"):
+        """Delete-one jackknife of power and coherence on their variance-stabilising scales: standard errors that rest on the data
+        (overlapping windows, non-stationary trials) instead of the closed forms of ``statistics``.
+
+        ``measures``: any of "power" (theta = ln power, transform "log"), "coherence_magnitude" (theta = arctanh |coherency|,
+        "fisher_z"; ``coherence_magnitude()`` itself is the squared magnitude, tanh(theta)^2) and "imaginary_coherence" (signed, "identity": its absolute value at the full estimate is
+        ``imaginary_coherence()``); all of them come from ONE pass over the spectra (sc_jackknife.hip).  ``over="trials"``: a
+        delete unit is everything one trial contributes to the expectation (needs an ``expectation_type`` that averages over
+        trials and n_trials >= 2); ``over="observations"``: every averaged observation is a unit (the Chronux choice; any
+        ``expectation_type``, n_observations >= 2).  Leaving a unit out is S - G_u with G_u the unit's own cross-spectrum.
+
+        Returns {name: statistics.JackknifeResult}: ``estimate``, ``bias_corrected`` and ``standard_error`` are float64 arrays
+        shaped like the measure's own output ([kept axes..., n_frequencies, n_signals] for power, [..., n_signals, n_signals] with
+        a NaN diagonal otherwise; the imaginary coherence is antisymmetric); ``statistics.jackknife_confidence_intervals`` turns
+        one into an interval on the natural scale.  A channel without power in a bin gives NaN in its entries (one warning counts
+        them).  The coherence magnitude is formed as |S_ij| (1 / sqrt S_ii) (1 / sqrt S_jj); where it is 1 up to rounding (two
+        identical channels; a leave-one-out estimate of a single observation, which also warns) the pair's ``estimate`` is
+        arctanh of a number within a few ulp of 1 -- at least 17, inf, or NaN beyond 1 -- and its other two outputs carry no
+        promise (the float64 reference rounds differently there); no other entry is affected.  ValueError for an
+        unknown or empty measure list, a bad ``over`` and fewer than two units, before any device work.
+        """
+        from .statistics import JackknifeResult, jackknife_finish
+        names, mask, over_id, n_units = _lib.jackknife_request(measures, over, self.expectation_type, self._jackknife_trials(),
+                                                               self.n_observations)
+        if n_units == 2 and self.n_observations == 2 and "coherence_magnitude" in names:
+            logger.warning("jackknife: with two delete units of one observation each a leave-one-out estimate is a single observation, "
+                           "whose coherence magnitude is identically 1: the coherence_magnitude results are inf, NaN or rounding noise")
+        flat, n_bins = self._jackknife_sums(mask, over_id, n_units)
+        blocks, _ = _lib.jackknife_blocks(names, n_bins, self._shape5[4])
+        out = {}
+        for name, at, size, shape in blocks:
+            theta, s1, s2 = (flat[at + k * size:at + (k + 1) * size].reshape(self._kept_shape() + (self._n_freq,) + shape[1:])
+                             for k in range(3))
+            est, corrected, se = jackknife_finish(theta, s1, s2, n_units)
+            out[name] = JackknifeResult(est, corrected, se, _lib.JACKKNIFE_MEASURES[name][1], n_units, over)
+        first = out[names[0]].estimate
+        n_nan = int(np.isnan(first).sum())
+        if names[0] != "power":
+            n_nan -= first.size // first.shape[-1]          # (the diagonal is NaN by definition)
+        if n_nan:
+            logger.warning(f"jackknife: {n_nan} entries of {names[0]} are NaN (a channel without power in a bin)")
+        return out
+
+    def _jackknife_trials(self):
+        """Trials of the whole job (parallel.ShardedConnectivity: over every rank)."""
+        return int(self._shape5[1])
+
+    def _jackknife_sums(self, mask, over_id, n_units):
+        """(the library's output as a flat float64 NumPy array -- _lib.jackknife_blocks --, n_bins).  The spectra are asked for
+        without a planes hint (the kernel reads complex64 / complex128; spectra already held as f16 pieces are decoded once);
+        the total is the CSM record of every rank's trials -- the one MIC / MIM read, cached under the same key."""
+        from . import engine
+        sp = self._device()
+        accum, _, _ = self._csm_records("interaction", two_sided=False)
+        out, n_bins = engine.jackknife(sp, self.expectation_type, accum, _lib.PLANE_CSM, mask, over_id, n_units, n_freq=self._n_freq)
+        return engine.to_host(self._jackknife_reduce(out, mask, n_bins)), n_bins
+
+    def _jackknife_reduce(self, out, mask, n_bins):
+        """Sum of the partial sums over the processes that hold the trials (nothing to add here)."""
+        return out
+
     def conditional_spectral_granger_prediction(self):
         """Power at node i explained by node j given every other signal, out[..., i, j] = j -> i | rest (diagonal NaN;
         Geweke 1984, Ding, Chen & Bressler 2006 section 3.3 -- the reference raises NotImplementedError,

@@ -912,6 +912,27 @@ def imaginary_interaction(accum, n_signals, planes, n_obs, members, sizes):
     return mic, mim, int(fail.item())
 
 
+def jackknife(spectra, expectation_type, total, planes, measures, over, n_units_total, n_freq=None, unit_range=None):
+    """Delete-one jackknife sums (sc_jackknife.hip): ONE pass over the complex64 / complex128 spectra for every measure of the mask
+    ``measures`` (_lib.JACKKNIFE_MEASURES) against the total CSM record ``total`` (any rank's sum).  ``over``: _lib.JACKKNIFE_OVER;
+    ``n_units_total``: delete units of the whole job; ``unit_range``: the units of these spectra to walk (default: all of them).
+    Returns (float64 device tensor laid out as _lib.jackknife_blocks says, n_bins)."""
+    lib = _lib.load()
+    total = fold_parts(total)
+    d = spectra.desc(expectation_type, n_freq)
+    n_bins, n_units, unit_size, n_out = c_int64(), c_int64(), c_int64(), c_int64()
+    _lib.check(lib.sc_jackknife_layout(byref(d), measures, over, byref(n_bins), byref(n_units), byref(unit_size), byref(n_out)),
+               "sc_jackknife_layout")
+    lo, hi = (0, n_units.value) if unit_range is None else unit_range
+    ws_bytes = int(lib.sc_jackknife_workspace_bytes(byref(d), measures, over, lo, hi))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=spectra.device) if ws_bytes else None
+    out = torch.empty((n_out.value,), dtype=torch.float64, device=spectra.device)
+    fn = lib.sc_jackknife_f64 if spectra.f64 else lib.sc_jackknife_f32
+    _lib.check(fn(_ptr(spectra.X), byref(d), _ptr(total), rec_planes(total, planes), measures, over, lo, hi, n_units_total, _ptr(out),
+                  _ptr(ws) if ws is not None else None, ws_bytes, _stream()), "sc_jackknife")
+    return out, n_bins.value
+
+
 class GraphedMeasures:
     """Stage A, stage B and the epilogue of ONE fixed request, captured once in a hipGraph and replayed per time series.
 

@@ -11,7 +11,7 @@
 imported.  Same constructor, properties, methods, shapes, dtypes, warnings and errors as the PyTorch-host class (it IS that class:
 only the methods that touch the device are replaced), both engines (``dtype=complex64`` -> float32 engine, planes format
 included; ``complex128``, the default -> float64 engine), every expectation-type measure, pairwise / subset Granger, the full
-Wilson factor and the directed MVAR measures, canonical and global coherence, MIC / MIM, the band statistics, more than 256
+Wilson factor and the directed MVAR measures, canonical and global coherence, MIC / MIM, the jackknife, the band statistics, more than 256
 signals (channel blocks of 128, tiled on the host).  Not here: complex-valued time series, multi-GPU (``parallel.ShardedConnectivity`` needs
 ``torch.distributed``), hipGraph replay (``engine.GraphedMeasures``).
 """
@@ -561,6 +561,30 @@ class Connectivity(_TorchHostConnectivity):
                 logger.warning(f"{n_fail} group cross-spectral blocks were not positive definite (NaN output)")
         W = self._shape5[0]
         return res.reshape(W, self._n_freq, n_g, n_g), labels
+
+    def _jackknife_sums(self, mask, over_id, n_units):
+        h, lib = host(), host().lib
+        if self._shape5[4] > 256:
+            # (this host holds no complex spectra of more than 256 signals: _WideSeries, _decode_planes)
+            raise ValueError("jackknife of more than 256 signals needs device spectra of the whole array: use the PyTorch host "
+                             "(SC_HIP_HOST=torch)")
+        rec, _, _ = self._csm_records("interaction", two_sided=False)      # (decodes spectra held as f16 pieces once)
+        sp = self._spectra
+        d = h._desc(sp, self.expectation_type, False, self._n_freq)
+        n_bins, n_all, unit_size, n_out = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(lib.sc_jackknife_layout(byref(d), mask, over_id, byref(n_bins), byref(n_all), byref(unit_size), byref(n_out)),
+                   "sc_jackknife_layout")
+        ws_bytes = int(lib.sc_jackknife_workspace_bytes(byref(d), mask, over_id, 0, n_all.value))
+        ws = h.alloc(ws_bytes) if ws_bytes else None
+        out = h.alloc(n_out.value * 8)
+        fn = lib.sc_jackknife_f64 if sp["f64"] else lib.sc_jackknife_f32
+        _lib.check(fn(sp["X"].ptr, byref(d), rec.buf.ptr, rec.planes(_lib.PLANE_CSM), mask, over_id, 0, n_all.value, n_units, out.ptr,
+                      ws.ptr if ws else None, ws_bytes, h.stream), "sc_jackknife")
+        flat = np.array(h.download(out, (n_out.value,), np.float64))
+        out.free()
+        if ws:
+            ws.free()
+        return flat, n_bins.value
 
     def _imaginary_interaction(self, group_labels):
         h, lib = host(), host().lib

@@ -454,6 +454,7 @@ class ShardedConnectivity(_connectivity_base()):
     * pairwise spectral Granger: records all-reduced once, the channel pairs dealt out over the ranks, each rank
       factorises its pairs, one merge of the disjoint outputs;
     * canonical coherence, MIC / MIM: records all-reduced once, the bins split over the ranks, all-gather of the owned bins;
+    * jackknife: records all-reduced once, every rank walks its own units against the total, one sum of the partial sums;
     * the full Wilson factor / MVAR measures and global coherence: records all-reduced, then computed redundantly
       (one C x C problem per window: nothing to deal out below the window count).
 
@@ -547,6 +548,25 @@ class ShardedConnectivity(_connectivity_base()):
                              device=accum.device)
         merged = merge_disjoint(out, self._group)
         return engine_to_host(merged).reshape(self._kept_shape() + (N // 2 + 1, C, C))
+
+    def _jackknife_trials(self):
+        return self._n_trials_total
+
+    def _jackknife_reduce(self, out, mask, n_bins):
+        """Every rank walked ITS units against the total record: one sum over ranks of the two partial sums of every measure
+        (theta(S) is the same on every rank and stays as it is)."""
+        from . import _lib
+        if _no_exchange(self._group):
+            return out
+        names = [k for k, v in _lib.JACKKNIFE_MEASURES.items() if mask & v[0]]
+        blocks, _ = _lib.jackknife_blocks(names, n_bins, self._shape5[4])
+        sums = torch.cat([out[at + size:at + 3 * size] for _, at, size, _ in blocks])
+        all_reduce_sum_(sums, self._group)
+        pos = 0
+        for _, at, size, _ in blocks:
+            out[at + size:at + 3 * size] = sums[pos:pos + 2 * size]
+            pos += 2 * size
+        return out
 
     def _canonical_bins(self, n_bins):
         """The bins this rank evaluates: a contiguous 1/N, padded so that every rank holds the same count."""

@@ -4,6 +4,8 @@ Mirrors the public functions of the reference's ``statistics`` module (reference
 so that code written against it keeps working.  These run on a few kilobytes of already-reduced
 measures (coherency per frequency and channel pair); they are not part of the device hot path.
 """
+from collections import namedtuple
+
 import numpy as np
 import scipy.special
 import scipy.stats
@@ -108,3 +110,38 @@ def power_fisher_z_transform(spectrum1, n_obs1, spectrum2=0, n_obs2=0):
     z1 = np.log(spectrum1) - power_bias(n_obs1)
     z2 = np.log(spectrum2) - power_bias(n_obs2)
     return (z1 - z2) / np.sqrt(power_variance(n_obs1) + power_variance(n_obs2))
+
+
+# ---- delete-one jackknife (Connectivity.jackknife; Thomson & Chave 1991) -----------------------------------------------------
+JackknifeResult = namedtuple("JackknifeResult", ["estimate", "bias_corrected", "standard_error", "transform", "n_units", "over"])
+JackknifeResult.__doc__ = """One measure of Connectivity.jackknife, on its variance-stabilising scale (``transform``: "log" for
+power, "fisher_z" = arctanh for the coherence magnitude, "identity" for the signed imaginary coherence): ``estimate`` = theta(S),
+``bias_corrected`` = theta(S) - (n - 1) mean_u d_u and ``standard_error`` = sqrt((n - 1) / n sum_u (d_u - mean d)^2) with
+d_u = theta(S without unit u) - theta(S); float64 arrays shaped like the measure's own output.  ``n_units`` = n delete units,
+``over`` = "trials" or "observations"."""
+
+_JACKKNIFE_BACK = {"log": np.exp, "fisher_z": np.tanh, "identity": lambda v: v}
+
+
+def jackknife_finish(theta, sum_d, sum_d2, n_units):
+    """(estimate, bias_corrected, standard_error) from theta(S) and the device's two sums over the n delete units.  The deviations
+    d_u are centred on the full estimate, so their mean m is of their own order and sum (d - m)^2 = sum d^2 - n m^2 loses nothing."""
+    n = float(n_units)
+    m = sum_d / n
+    spread = np.maximum(sum_d2 - n * m * m, 0.0)          # (NaN stays NaN)
+    return theta, theta - (n - 1.0) * m, np.sqrt((n - 1.0) / n * spread)
+
+
+def jackknife_confidence_intervals(result, ci=0.95):
+    """(lower, upper) of a JackknifeResult on the measure's natural scale: back(bias_corrected -/+ t * standard_error) with t the
+    two-sided Student-t quantile of ``ci`` at n_units - 1 degrees of freedom and back = exp (power), tanh (coherence magnitude),
+    identity (imaginary coherence)."""
+    if not 0.0 < ci < 1.0:
+        raise ValueError(f"ci must lie strictly between 0 and 1 (got {ci})")
+    if result.transform not in _JACKKNIFE_BACK:
+        raise ValueError(f"unknown transform {result.transform!r}; expected one of {sorted(_JACKKNIFE_BACK)}")
+    t = scipy.stats.t.ppf(0.5 + ci / 2.0, result.n_units - 1)
+    back = _JACKKNIFE_BACK[result.transform]
+    half = t * np.asarray(result.standard_error)
+    centre = np.asarray(result.bias_corrected)
+    return back(centre - half), back(centre + half)
