@@ -200,7 +200,14 @@ class HipEngineError(RuntimeError):
     """A libsc_hip.so entry point returned a negative status."""
 
 
-CONDITIONAL_WORK_BYTES = 4 << 30    # workspace bound of one sc_conditional_granger_f64 call (the dropped signals go in chunks)
+def record_planes(planes, f64):
+    """`planes` as the consumers of accumulator records want it: with RECORD_F64 when the records hold doubles."""
+    return (planes | RECORD_F64) if f64 else (planes & ~RECORD_F64)
+
+
+# workspace bounds of the chunked stage-D drivers (_stage_d.py), read at call time
+GRANGER_WORK_BYTES = 8 << 30        # one sc_granger_pairwise_f64 call (160 bytes per problem and bin; the pairs go in chunks)
+CONDITIONAL_WORK_BYTES = 4 << 30    # one sc_conditional_granger_f64 / sc_blockwise_granger_f64 call (dropped signals / block pairs in chunks)
 
 
 def conditional_chunk(n_groups, n_signals, workspace_bytes, cap=None):
@@ -259,6 +266,45 @@ def blockwise_batches(pairs, n_obs):
         batches[m] = (np.stack([it[0] for it in items]).astype(np.int32), np.array([it[1] for it in items], dtype=np.int32),
                       np.array([it[2] for it in items], dtype=np.int32))
     return batches, n_skipped
+
+
+BLOCK_SIGNALS = 128        # channel block of the tiling of more than 256 signals (a multiple of the 16-channel record tile)
+
+
+def tile_plan(n_signals, block=BLOCK_SIGNALS):
+    """Stage B for MORE signals than one launch of the kernels stages (256), both hosts: the channels are cut into blocks of
+    ``block``, every pair of blocks (a < b) is accumulated as a request of its own (<= 256 signals) and its 16 x 16 record tiles
+    are copied to their places in the full record.  Yields (a, b, cols, src, dst) per block pair: ``cols`` the channels of the
+    request (block a, then block b), ``src`` the tiles of its record to keep and ``dst`` their indices in the full record (tile
+    (bi, bj), bi <= bj, of a record of nb tile rows has index bi nb - bi (bi - 1) / 2 + (bj - bi): include/sc_hip.h).  The cross
+    tiles of (a, b) come from that pair, the tiles inside block a from the pair (a, a + 1), those inside the last block from the
+    last pair -- every tile of the full record exactly once."""
+    import numpy as np
+
+    def tile(bi, bj, nb):
+        return bi * nb - bi * (bi - 1) // 2 + (bj - bi)
+
+    n_blk, NB, per = -(-n_signals // block), -(-n_signals // 16), block // 16
+    for a in range(n_blk - 1):
+        for b in range(a + 1, n_blk):
+            cols = np.concatenate([np.arange(a * block, (a + 1) * block), np.arange(b * block, min((b + 1) * block, n_signals))])
+            nb_s = -(-len(cols) // 16)
+            src, dst = [], []
+            for ti in range(nb_s):
+                for tj in range(ti, nb_s):
+                    in_a_i, in_a_j = ti < per, tj < per
+                    if in_a_i and in_a_j:
+                        keep = b == a + 1                                   # inside block a: from its first partner
+                    elif not in_a_i and not in_a_j:
+                        keep = a == n_blk - 2 and b == n_blk - 1            # inside the last block: from the last pair
+                    else:
+                        keep = True                                         # cross tiles of (a, b)
+                    if keep:
+                        gi = a * per + ti if in_a_i else b * per + (ti - per)
+                        gj = a * per + tj if in_a_j else b * per + (tj - per)
+                        src.append(tile(ti, tj, nb_s))
+                        dst.append(tile(gi, gj, NB))
+            yield a, b, cols, src, dst
 
 
 def member_stride(max_group_size):

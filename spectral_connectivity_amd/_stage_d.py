@@ -1,0 +1,254 @@
+"""Stage D: the call sequences of every measure that runs on accumulated cross-spectral records, written once for both hosts.
+
+Each function drives one entry-point family of include/sc_hip.h -- sizes the workspace, cuts the job into chunks under the
+workspace bound (``_lib.GRANGER_WORK_BYTES`` / ``_lib.CONDITIONAL_WORK_BYTES``, read at call time), keeps the output on every
+call but the first, offsets the per-chunk pointers and combines the three-int summaries -- and never imports torch.  What differs
+between the hosts is behind the memory adapter ``mem``, the first argument (engine.TorchMemory: tensors on the current stream;
+numpy_host.NumpyMemory: DeviceArray over the library's own allocator):
+
+    mem.empty(shape, dtype) / mem.zeros(shape, dtype)    a device array (NumPy dtypes: uint8, int32, float64, complex128)
+    mem.upload(numpy_array)                              a device array holding a copy
+    mem.ptr(array, first_row=0)                          c_void_p of the array's row ``first_row``
+    mem.stream()                                         the stream every call is launched on
+    mem.is_f64(record)                                   records of doubles (the SC_RECORD_F64 bit of ``planes``)
+    mem.fill_nan(array)                                  NaN into an output no call wrote
+    mem.read_int(array)                                  the first int32 of an array, on the host
+    mem.hstack(chunks, n_rows)                           flat [n_rows, n_0], [n_rows, n_1], ... joined along the columns, flat
+    mem.download(array)                                  NumPy copy (the callers' side: no driver downloads a result)
+
+Returned arrays are device arrays of the host's own type.  A new stage-D measure adds its entry point to ``_lib.SYMBOLS``, one
+driver here and one thin wrapper in engine.py.
+"""
+import ctypes
+from ctypes import byref, c_int64
+
+import numpy as np
+
+from . import _lib
+
+MAX_WILSON_ITERATIONS = 1024      # iterations the device kernels can log (WILSON_HIST / MV_HIST in csrc)
+
+
+def check_max_iterations(max_iterations):
+    """The reference takes any positive count (minimum_phase_decomposition.py:227-322); the device kernels log at most 1024."""
+    if not 1 <= int(max_iterations) <= MAX_WILSON_ITERATIONS:
+        raise ValueError(f"max_iterations must be between 1 and {MAX_WILSON_ITERATIONS} on the device path (got {max_iterations}); "
+                         "Wilson's iteration converges in tens of steps or not at all")
+    return int(max_iterations)
+
+
+def _planes(mem, accum, planes):
+    """`planes` as the consumers of the records ``accum`` want it (a spectrum tensor instead of records: as given)."""
+    return planes if accum is None else _lib.record_planes(planes, mem.is_f64(accum))
+
+
+def _ptr(mem, array):
+    return None if array is None else mem.ptr(array)
+
+
+def _size(fn, what, *args):
+    """A workspace query of the library: its byte count."""
+    nbytes = ctypes.c_size_t()
+    _lib.check(fn(*args, byref(nbytes)), what)
+    return nbytes.value
+
+
+def _wilson(mem, fn, what, total, *args):
+    """One call of a Wilson entry point (its last two arguments are the summary and the stream); its summary = (iterations run,
+    problems not converged, identity starts) goes into ``total`` as max, sum, sum."""
+    summary = (ctypes.c_int32 * 3)(0, 0, 0)
+    _lib.check(fn(*args, summary, mem.stream()), what)
+    total[0] = max(total[0], summary[0])
+    total[1] += summary[1]
+    total[2] += summary[2]
+
+
+def granger_workspace(mem, n_groups, n_problems, n_fft):
+    """(workspace, its bytes) of the 2x2 Wilson kernels for ``n_problems`` problems per group (sc_granger_pairwise_f64,
+    sc_wilson_factor_f64)."""
+    nbytes = _size(_lib._handle().sc_granger_workspace_bytes, "sc_granger_workspace_bytes", n_groups, n_problems, n_fft)
+    return mem.empty((nbytes,), np.uint8), nbytes
+
+
+def granger_pairwise(mem, accum, n_groups, n_freq_accum, n_fft, n_signals, planes, n_obs, pairs, tolerance=1e-8, max_iterations=60):
+    """Batched 2x2 Wilson + spectral Granger (sc_wilson.hip).  Returns (out [n_groups, n_fft/2+1, C, C] float64, n_iter, status,
+    summary): n_iter / status are [n_groups, n_pairs] flattened, whatever the chunking, and summary = (iterations run, problems not
+    converged, problems started from the identity because their lag-0 covariance was not positive definite).  A long pair list is
+    walked in chunks that bound the workspace (160 bytes per problem and bin); every chunk writes its pairs into the same output."""
+    lib = _lib._handle()
+    max_iterations = check_max_iterations(max_iterations)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    n_pairs = pairs.shape[0]
+    out = mem.empty((n_groups, n_fft // 2 + 1, n_signals, n_signals), np.float64)
+    chunk = int(max(1, min(n_pairs, _lib.GRANGER_WORK_BYTES // (n_groups * n_fft * 160))))
+    work, nbytes = granger_workspace(mem, n_groups, chunk, n_fft)
+    d_pairs = mem.upload(pairs)
+    total, n_iter, status = [0, 0, 0], [], []
+    for p0 in range(0, n_pairs, chunk):
+        n = min(chunk, n_pairs - p0)
+        n_iter.append(mem.empty((n_groups * n,), np.int32))          # [n_groups, n] of this chunk
+        status.append(mem.empty((n_groups * n,), np.int32))
+        _wilson(mem, lib.sc_granger_pairwise_f64, "sc_granger_pairwise_f64", total,
+                mem.ptr(accum), n_groups, n_freq_accum, n_fft, n_signals, _planes(mem, accum, planes), n_obs, mem.ptr(d_pairs, p0), n,
+                tolerance, max_iterations, mem.ptr(work), nbytes, _lib.GRANGER_KEEP_OUTPUT if p0 else 0, mem.ptr(out),
+                mem.ptr(n_iter[-1]), mem.ptr(status[-1]))
+    return out, mem.hstack(n_iter, n_groups), mem.hstack(status, n_groups), tuple(total)
+
+
+def _mvar_workspace(mem, n_groups, n_signals, n_fft):
+    nbytes = _size(_lib._handle().sc_mvar_workspace_bytes, "sc_mvar_workspace_bytes", n_groups, n_signals, n_fft)
+    return mem.empty((nbytes,), np.uint8), nbytes
+
+
+def mvar_factor(mem, n_groups, n_fft, n_signals, accum=None, n_freq_accum=0, planes=0, n_obs=1, spectra=None, tolerance=1e-8,
+                max_iterations=60):
+    """Full C x C Wilson factor (sc_mvar.hip) of accumulator records or of a two-sided complex128 spectrum array
+    [n_groups, n_fft, C, C].  Returns (G [n_groups, n_fft, C, C] complex128, n_iter, status, summary)."""
+    max_iterations = check_max_iterations(max_iterations)
+    work, nbytes = _mvar_workspace(mem, n_groups, n_signals, n_fft)
+    G = mem.empty((n_groups, n_fft, n_signals, n_signals), np.complex128)
+    n_iter, status = mem.empty((n_groups,), np.int32), mem.empty((n_groups,), np.int32)
+    total = [0, 0, 0]
+    _wilson(mem, _lib._handle().sc_mvar_factor_f64, "sc_mvar_factor_f64", total,
+            _ptr(mem, accum), _ptr(mem, spectra), n_groups, n_freq_accum, n_fft, n_signals, _planes(mem, accum, planes), n_obs,
+            tolerance, max_iterations, mem.ptr(work), nbytes, mem.ptr(G), mem.ptr(n_iter), mem.ptr(status))
+    return G, n_iter, status, tuple(total)
+
+
+def mvar_measure(mem, G, which):
+    """A directed MVAR measure / model quantity (``_lib.MVAR_*``) from the minimum-phase factor G."""
+    n_groups, n_fft, C, _ = G.shape
+    F = n_fft // 2 + 1
+    work, nbytes = _mvar_workspace(mem, n_groups, C, n_fft)
+    if which == _lib.MVAR_NOISE_COVARIANCE:
+        out = mem.empty((n_groups, C, C), np.float64)
+    else:
+        out = mem.empty((n_groups, F, C, C), np.complex128 if which in (_lib.MVAR_TRANSFER, _lib.MVAR_COEFFICIENTS) else np.float64)
+    _lib.check(_lib._handle().sc_mvar_measure_f64(mem.ptr(G), n_groups, n_fft, C, which, mem.ptr(out), mem.ptr(work), nbytes,
+                                                  mem.stream()), "sc_mvar_measure_f64")
+    return out
+
+
+def conditional_granger(mem, G, n_groups, n_fft, n_signals, accum=None, n_freq_accum=0, planes=0, n_obs=1, spectra=None,
+                        tolerance=1e-8, max_iterations=60):
+    """Conditional spectral Granger prediction (sc_conditional.hip) from the cached full factor ``G`` [n_groups, n_fft, C, C]
+    and the records (or a two-sided complex128 spectrum array) it was factored from: one reduced (C - 1)-signal Wilson
+    factorisation per dropped signal, batched over the dropped signals of a chunk.  Returns (out [n_groups, n_fft/2+1, C, C]
+    float64, out[..., i, j] = j -> i given the rest, n_iter [C, n_groups], status [C, n_groups], summary) with summary =
+    (iterations run, reduced problems not converged, identity starts)."""
+    lib = _lib._handle()
+    max_iterations = check_max_iterations(max_iterations)
+    C = n_signals
+
+    def ws(n_dropped):
+        return _size(lib.sc_conditional_granger_workspace_bytes, "sc_conditional_granger_workspace_bytes", n_groups, C, n_fft,
+                     n_dropped)
+
+    chunk = _lib.conditional_chunk(n_groups, C, ws)
+    nbytes = ws(chunk)
+    work = mem.empty((nbytes,), np.uint8)
+    out = mem.empty((n_groups, n_fft // 2 + 1, C, C), np.float64)
+    n_iter, status = mem.empty((C, n_groups), np.int32), mem.empty((C, n_groups), np.int32)
+    dropped = mem.upload(np.arange(C, dtype=np.int32))
+    total = [0, 0, 0]
+    for j0 in range(0, C, chunk):
+        _wilson(mem, lib.sc_conditional_granger_f64, "sc_conditional_granger_f64", total,
+                _ptr(mem, accum), _ptr(mem, spectra), n_groups, n_freq_accum, n_fft, C, _planes(mem, accum, planes), n_obs, mem.ptr(G),
+                mem.ptr(dropped, j0), min(chunk, C - j0), tolerance, max_iterations, mem.ptr(work), nbytes,
+                _lib.CONDITIONAL_KEEP_OUTPUT if j0 else 0, mem.ptr(out), mem.ptr(n_iter, j0), mem.ptr(status, j0))
+    return out, n_iter, status, tuple(total)
+
+
+def blockwise_granger(mem, n_groups, n_fft, n_signals, batches, n_blocks, accum=None, n_freq_accum=0, planes=0, n_obs=1, spectra=None,
+                      tolerance=1e-8, max_iterations=60):
+    """Blockwise spectral Granger prediction (sc_blockwise.hip) from the records (or a two-sided complex128 spectrum array):
+    one m-signal Wilson factorisation per (block pair, group), the pairs of one size m batched under the workspace cap.
+    ``batches``: {m: (members [n, m], split [n], cell [n, 2])} int32 arrays (_lib.blockwise_batches).  Returns (out [n_groups,
+    n_fft/2+1, n_blocks, n_blocks] float64, out[..., a, b] = b -> a, NaN where no pair was computed, n_iter [pairs, n_groups],
+    status [pairs, n_groups] in the order of the batches, summary) with summary = (iterations run, problems not converged,
+    identity starts)."""
+    lib = _lib._handle()
+    max_iterations = check_max_iterations(max_iterations)
+    n_total = sum(len(split) for _, split, _ in batches.values())
+    out = mem.empty((n_groups, n_fft // 2 + 1, n_blocks, n_blocks), np.float64)
+    n_iter, status = mem.zeros((n_total, n_groups), np.int32), mem.zeros((n_total, n_groups), np.int32)
+    total = [0, 0, 0]
+    row, flags = 0, 0              # the first call NaN-fills the output, the others keep it
+    for m, (members, split, cell) in batches.items():
+        n_pairs = len(split)
+
+        def ws(n, m=m):
+            return _size(lib.sc_blockwise_granger_workspace_bytes, "sc_blockwise_granger_workspace_bytes", n_groups, m, n_fft, n)
+
+        chunk = _lib.blockwise_chunk(n_groups, n_pairs, ws)
+        nbytes = ws(chunk)
+        work = mem.empty((nbytes,), np.uint8)
+        d_members, d_split, d_cell = mem.upload(members), mem.upload(split), mem.upload(cell)
+        for q0 in range(0, n_pairs, chunk):
+            _wilson(mem, lib.sc_blockwise_granger_f64, "sc_blockwise_granger_f64", total,
+                    _ptr(mem, accum), _ptr(mem, spectra), n_groups, n_freq_accum, n_fft, n_signals, _planes(mem, accum, planes), n_obs,
+                    mem.ptr(d_members, q0), mem.ptr(d_split, q0), mem.ptr(d_cell, q0), min(chunk, n_pairs - q0), m, n_blocks,
+                    tolerance, max_iterations, mem.ptr(work), nbytes, flags, mem.ptr(out), mem.ptr(n_iter, row + q0),
+                    mem.ptr(status, row + q0))
+            flags = _lib.BLOCKWISE_KEEP_OUTPUT
+        row += n_pairs
+    if not flags:
+        mem.fill_nan(out)
+    return out, n_iter, status, tuple(total)
+
+
+def global_coherence(mem, accum, n_groups, n_freq_accum, n_fft, n_signals, planes, n_obs, max_rank, ascending):
+    """Leading eigenpairs of the CSM per (window, two-sided bin) (sc_global.hip): (values [n_groups, n_fft, max_rank] float64,
+    vectors [n_groups, n_fft, C, max_rank] complex128)."""
+    values = mem.empty((n_groups, n_fft, max_rank), np.float64)
+    vectors = mem.empty((n_groups, n_fft, n_signals, max_rank), np.complex128)
+    _lib.check(_lib._handle().sc_global_coherence_f64(mem.ptr(accum), n_groups, n_freq_accum, n_fft, n_signals,
+                                                      _planes(mem, accum, planes), n_obs, max_rank, int(ascending), mem.ptr(values),
+                                                      mem.ptr(vectors), mem.stream()), "sc_global_coherence_f64")
+    return values, vectors
+
+
+def canonical_coherence(mem, accum, n_signals, planes, n_obs, groups):
+    """groups: list of int arrays (channel indices per group).  Returns ([n_bins, G, G] float64, n_fail)."""
+    members, sizes, _ = _lib.member_table(groups)
+    G, n_bins = len(sizes), accum.shape[0]
+    d_members, d_sizes = mem.upload(members), mem.upload(sizes)
+    out = mem.empty((n_bins, G, G), np.float64)
+    fail = mem.zeros((1,), np.int32)
+    _lib.check(_lib._handle().sc_canonical_coherence_f64(mem.ptr(accum), n_bins, n_signals, _planes(mem, accum, planes), n_obs,
+                                                         mem.ptr(d_members), mem.ptr(d_sizes), G, int(sizes.max()), mem.ptr(out),
+                                                         mem.ptr(fail), mem.stream()), "sc_canonical_coherence_f64")
+    return out, mem.read_int(fail)
+
+
+def imaginary_interaction(mem, accum, n_signals, planes, n_obs, members, sizes):
+    """members / sizes: _lib.member_table of the groups.  Returns (MIC, MIM [n_bins, G, G] float64, n_fail)."""
+    G, n_bins = len(sizes), accum.shape[0]
+    d_members, d_sizes = mem.upload(members), mem.upload(sizes)
+    mic, mim = mem.empty((n_bins, G, G), np.float64), mem.empty((n_bins, G, G), np.float64)
+    fail = mem.zeros((1,), np.int32)
+    _lib.check(_lib._handle().sc_imaginary_interaction_f64(mem.ptr(accum), n_bins, n_signals, _planes(mem, accum, planes), n_obs,
+                                                           mem.ptr(d_members), mem.ptr(d_sizes), G, int(sizes.max()), mem.ptr(mic),
+                                                           mem.ptr(mim), mem.ptr(fail), mem.stream()), "sc_imaginary_interaction_f64")
+    return mic, mim, mem.read_int(fail)
+
+
+def jackknife(mem, spectra, expectation_type, total, planes, measures, over, n_units_total, n_freq=None, unit_range=None):
+    """Delete-one jackknife sums (sc_jackknife.hip): ONE pass over the complex64 / complex128 spectra (``spectra.X``, described by
+    ``spectra.desc``) for every measure of the mask ``measures`` (_lib.JACKKNIFE_MEASURES) against the total CSM record ``total``
+    (any rank's sum).  ``over``: _lib.JACKKNIFE_OVER; ``n_units_total``: delete units of the whole job; ``unit_range``: the units
+    of these spectra to walk (default: all of them).  Returns (float64 device array laid out as _lib.jackknife_blocks says,
+    n_bins)."""
+    lib = _lib._handle()
+    d = spectra.desc(expectation_type, n_freq)
+    n_bins, n_units, unit_size, n_out = c_int64(), c_int64(), c_int64(), c_int64()
+    _lib.check(lib.sc_jackknife_layout(byref(d), measures, over, byref(n_bins), byref(n_units), byref(unit_size), byref(n_out)),
+               "sc_jackknife_layout")
+    lo, hi = (0, n_units.value) if unit_range is None else unit_range
+    ws_bytes = int(lib.sc_jackknife_workspace_bytes(byref(d), measures, over, lo, hi))
+    ws = mem.empty((ws_bytes,), np.uint8) if ws_bytes else None
+    out = mem.empty((n_out.value,), np.float64)
+    fn = lib.sc_jackknife_f64 if spectra.f64 else lib.sc_jackknife_f32
+    _lib.check(fn(mem.ptr(spectra.X), byref(d), mem.ptr(total), _planes(mem, total, planes), measures, over, lo, hi, n_units_total,
+                  mem.ptr(out), _ptr(mem, ws), ws_bytes, mem.stream()), "sc_jackknife")
+    return out, n_bins.value

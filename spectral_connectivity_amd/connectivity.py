@@ -278,6 +278,24 @@ class Connectivity:
         (one process per GPU, trials sharded) all-reduces."""
         return accum
 
+    def _memory(self, like):
+        """The memory adapter of the stage-D drivers (_stage_d.py) on the host in use -- here the PyTorch host's, for the device
+        of the tensor ``like``; its ``download`` brings a result to NumPy."""
+        from . import engine
+        return engine.TorchMemory(like.device)
+
+    def _wilson_done(self, mem, noun, summary, n_iter, status):
+        """The warnings of a batch of Wilson factorisations (``noun``: what one problem is) and ``_last_wilson``."""
+        iters, not_conv, fallback = (int(v) for v in summary)
+        n_iter, status = mem.download(n_iter), mem.download(status)
+        if fallback:
+            # reference minimum_phase_decomposition.py:78-93 (there the start is a random draw around the identity)
+            logger.warning("Computing the initial conditions using the Cholesky failed. "
+                           f"Using the identity as initial condition ({fallback} {noun}).")
+        if not_conv:
+            logger.warning(f"Maximum iterations reached. {status.size - not_conv} of {status.size} converged")
+        self._last_wilson = dict(iterations=iters, not_converged=not_conv, cholesky_fallbacks=fallback, n_iter=n_iter, status=status)
+
     def _kept_shape(self):
         W, R, K = self._shape5[:3]
         axes = EXPECTATION_AXES[self.expectation_type]
@@ -397,27 +415,19 @@ class Connectivity:
 
     # ---- pairwise spectral Granger (reference connectivity.py:1161-1213) -----------------
     def _granger(self, pairs):
-        from . import engine
         N, C = self._shape5[3], self._shape5[4]
-        return engine.to_host(self._granger_device(pairs)).reshape(self._kept_shape() + (N // 2 + 1, C, C))
+        out = self._granger_device(pairs)
+        return self._memory(out).download(out).reshape(self._kept_shape() + (N // 2 + 1, C, C))
 
     def _granger_device(self, pairs):
-        """Device tensor [n_groups, N/2+1, C, C] float64: the listed pairs filled in, NaN elsewhere."""
-        from . import engine
+        """Device array [n_groups, N/2+1, C, C] float64: the listed pairs filled in, NaN elsewhere."""
+        from . import _stage_d
         N, C = self._shape5[3], self._shape5[4]
-        planes = _lib.PLANE_CSM
         accum, n_obs, n_freq = self._csm_records("granger")
-        n_groups = accum.shape[0] // n_freq
-        out, n_iter, status, (iters, not_conv, fallback) = engine.granger_pairwise(
-            accum, n_groups, n_freq, N, C, planes, self._n_observations_total(n_obs), pairs)
-        if fallback:
-            # reference minimum_phase_decomposition.py:78-93 (there the start is a random draw around the identity)
-            logger.warning("Computing the initial conditions using the Cholesky failed. "
-                           f"Using the identity as initial condition ({fallback} problems).")
-        if not_conv:
-            logger.warning(f"Maximum iterations reached. {status.numel() - not_conv} of {status.numel()} converged")
-        self._last_wilson = dict(iterations=iters, not_converged=not_conv, cholesky_fallbacks=fallback,
-                                 n_iter=n_iter.cpu().numpy(), status=status.cpu().numpy())
+        mem = self._memory(accum)
+        out, n_iter, status, summary = _stage_d.granger_pairwise(mem, accum, accum.shape[0] // n_freq, n_freq, N, C, _lib.PLANE_CSM,
+                                                                 self._n_observations_total(n_obs), pairs)
+        self._wilson_done(mem, "problems", summary, n_iter, status)
         return out
 
     def pairwise_spectral_granger_prediction(self):
@@ -462,40 +472,30 @@ class Connectivity:
                              f"{_lib.load().sc_mvar_max_signals()} (got {C}); use the pairwise measures")
 
     def _mvar_factor_device(self):
-        from . import engine
+        from . import _stage_d
         if getattr(self, "_mvar_G", None) is not None:
             return self._mvar_G
-        sp = self._device()
         N, C = self._shape5[3], self._shape5[4]
         self._check_mvar_signals()
-        planes = _lib.PLANE_CSM
         accum, n_obs, n_freq = self._csm_records("granger")
-        n_groups = accum.shape[0] // n_freq
-        G, n_iter, status, (iters, not_conv, fallback) = engine.mvar_factor(
-            n_groups, N, C, accum=accum, n_freq_accum=n_freq, planes=planes, n_obs=self._n_observations_total(n_obs))
-        st = status.cpu().numpy()
-        if fallback:
-            # reference minimum_phase_decomposition.py:78-93 (there the start is a random draw around the identity)
-            logger.warning("Computing the initial conditions using the Cholesky failed. "
-                           f"Using the identity as initial condition ({fallback} windows).")
-        if not_conv:
-            logger.warning(f"Maximum iterations reached. {st.size - not_conv} of {st.size} converged")
-        self._last_wilson = dict(iterations=iters, not_converged=not_conv, cholesky_fallbacks=fallback,
-                                 n_iter=n_iter.cpu().numpy(), status=st)
+        mem = self._memory(accum)
+        G, n_iter, status, summary = _stage_d.mvar_factor(mem, accum.shape[0] // n_freq, N, C, accum=accum, n_freq_accum=n_freq,
+                                                          planes=_lib.PLANE_CSM, n_obs=self._n_observations_total(n_obs))
+        self._wilson_done(mem, "windows", summary, n_iter, status)
         self._mvar_G = G
         return G
 
     def _mvar(self, which, n_freq_axis=True):
-        from . import engine
-        out = engine.to_host(engine.mvar_measure(self._mvar_factor_device(), which))
-        C = self._shape5[4]
-        tail = (self._shape5[3] // 2 + 1, C, C) if n_freq_axis else (C, C)
-        return out.reshape(self._kept_shape() + tail)
+        from . import _stage_d
+        G = self._mvar_factor_device()
+        mem = self._memory(G)
+        out = mem.download(_stage_d.mvar_measure(mem, G, which))
+        return out.reshape(self._kept_shape() + out.shape[1:])
 
     @property
     def _minimum_phase_factor(self):
-        from . import engine
-        G = engine.to_host(self._mvar_factor_device())
+        G = self._mvar_factor_device()
+        G = self._memory(G).download(G)
         return G.reshape(self._kept_shape() + G.shape[1:])
 
     @property
@@ -562,19 +562,18 @@ class Connectivity:
         smallest-first when max_rank < n_signals - 1 (scipy svds) and largest-first otherwise; vectors
         are unit norm with their largest component real positive (the reference's phase is arbitrary).
         """
-        from . import engine
-        sp = self._device()
+        from . import _stage_d
         W, R, K, N, C = self._shape5
         max_rank = int(max_rank)
         if not 1 <= max_rank <= min(C, R * K):
             raise ValueError(f"max_rank must be between 1 and min(n_signals, n_trials * n_tapers) = {min(C, R * K)}")
         if C > _lib.load().sc_global_coherence_max_signals():
             raise ValueError(f"global_coherence supports n_signals <= {_lib.load().sc_global_coherence_max_signals()}")
-        planes = _lib.PLANE_CSM
         accum, n_obs, n_freq = self._csm_records("global", "trials_tapers")
-        values, vectors = engine.global_coherence(accum, W, n_freq, N, C, planes, self._n_observations_total(n_obs),
-                                                  max_rank, ascending=max_rank < C - 1)
-        return values.cpu().numpy(), vectors.cpu().numpy()
+        mem = self._memory(accum)
+        values, vectors = _stage_d.global_coherence(mem, accum, W, n_freq, N, C, _lib.PLANE_CSM, self._n_observations_total(n_obs),
+                                                    max_rank, ascending=max_rank < C - 1)
+        return mem.download(values), mem.download(vectors)
 
     # ---- canonical coherence (reference connectivity.py:745-820) --------------------------
     def canonical_coherence(self, group_labels):
@@ -584,12 +583,33 @@ class Connectivity:
         Like the reference this always averages over trials and tapers.
         """
         from . import engine
+        accum, n_obs, _ = self._csm_records("canonical", "trials_tapers", two_sided=False)
+        n_total = self._n_observations_total(n_obs)
+        labels, groups, small = self._canonical_groups(group_labels, n_total)
+        lo, hi, per = self._canonical_bins(accum.shape[0])
+        n_g = len(groups)
+        import torch
+        if hi > lo:
+            out = torch.ones((hi - lo, n_g, n_g), dtype=torch.float64, device=accum.device)
+            out[:, torch.arange(n_g), torch.arange(n_g)] = float("nan")
+            n_fail = 0
+            if len(small) >= 2:
+                sub, n_fail = engine.canonical_coherence(accum[lo:hi], self._shape5[4], _lib.PLANE_CSM, n_total,
+                                                         [groups[k] for k in small])
+                idx = torch.as_tensor(small, device=accum.device)
+                out[:, idx[:, None], idx[None, :]] = sub
+        else:                                  # more processes than bins: this one has nothing to evaluate
+            out, n_fail = torch.empty((0, n_g, n_g), dtype=torch.float64, device=accum.device), 0
+        out = self._canonical_gather(out, accum.shape[0], per)
+        self._canonical_failed(n_fail)
+        W = self._shape5[0]
+        return out.cpu().numpy().reshape(W, self._n_freq, len(labels), len(labels)), labels
+
+    def _canonical_groups(self, group_labels, n_total):
+        """(np.unique of the labels, the channel indices of every group, the indices of the groups that go to the device)."""
         group_labels = np.asarray(group_labels)
         labels = np.unique(group_labels)
         groups = [np.flatnonzero(np.isin(group_labels, lab)) for lab in labels]
-        planes = _lib.PLANE_CSM
-        accum, n_obs, _ = self._csm_records("canonical", "trials_tapers", two_sided=False)
-        n_total = self._n_observations_total(n_obs)
         # A group with at least as many channels as there are observations spans the whole observation space: the
         # orthonormal row-space basis V_g the reference gets from its thin SVD (connectivity.py:1979-2032) is then the full
         # n_obs-dimensional space, V_g^H V_h has orthonormal columns for ANY other group h, and every singular value of the
@@ -602,25 +622,11 @@ class Connectivity:
             raise ValueError(f"canonical_coherence: groups of more than {max_group} channels need n_trials * n_tapers "
                              "<= the group size (their coherence is then 1) -- the whitening kernel takes up to "
                              f"{max_group} channels per group")
-        lo, hi, per = self._canonical_bins(accum.shape[0])
-        n_g = len(groups)
-        import torch
-        if hi > lo:
-            out = torch.ones((hi - lo, n_g, n_g), dtype=torch.float64, device=accum.device)
-            out[:, torch.arange(n_g), torch.arange(n_g)] = float("nan")
-            n_fail = 0
-            if len(small) >= 2:
-                sub, n_fail = engine.canonical_coherence(accum[lo:hi], self._shape5[4], planes, n_total,
-                                                         [groups[k] for k in small])
-                idx = torch.as_tensor(small, device=accum.device)
-                out[:, idx[:, None], idx[None, :]] = sub
-        else:                                  # more processes than bins: this one has nothing to evaluate
-            out, n_fail = torch.empty((0, n_g, n_g), dtype=torch.float64, device=accum.device), 0
-        out = self._canonical_gather(out, accum.shape[0], per)
+        return labels, groups, small
+
+    def _canonical_failed(self, n_fail):
         if n_fail:
             logger.warning(f"{n_fail} group cross-spectral blocks were not positive definite (NaN output)")
-        W = self._shape5[0]
-        return out.cpu().numpy().reshape(W, self._n_freq, len(labels), len(labels)), labels
 
     def _canonical_bins(self, n_bins):
         """Bins [lo, hi) this process evaluates and the per-process count (all of them here; 1/N of them in
@@ -746,11 +752,12 @@ class Connectivity:
         """(the library's output as a flat float64 NumPy array -- _lib.jackknife_blocks --, n_bins).  The spectra are asked for
         without a planes hint (the kernel reads complex64 / complex128; spectra already held as f16 pieces are decoded once);
         the total is the CSM record of every rank's trials -- the one MIC / MIM read, cached under the same key."""
-        from . import engine
-        sp = self._device()
+        from . import _stage_d
         accum, _, _ = self._csm_records("interaction", two_sided=False)
-        out, n_bins = engine.jackknife(sp, self.expectation_type, accum, _lib.PLANE_CSM, mask, over_id, n_units, n_freq=self._n_freq)
-        return engine.to_host(self._jackknife_reduce(out, mask, n_bins)), n_bins
+        mem = self._memory(accum)
+        out, n_bins = _stage_d.jackknife(mem, self._device(), self.expectation_type, accum, _lib.PLANE_CSM, mask, over_id, n_units,
+                                         n_freq=self._n_freq)
+        return mem.download(self._jackknife_reduce(out, mask, n_bins)), n_bins
 
     def _jackknife_reduce(self, out, mask, n_bins):
         """Sum of the partial sums over the processes that hold the trials (nothing to add here)."""
@@ -762,24 +769,17 @@ class Connectivity:
         connectivity.py:1215-1224).  The full factor is the cached one of the MVAR measures; one reduced Wilson
         factorisation per dropped signal runs on the device (sc_conditional.hip).  With two signals this is the pairwise
         measure.  ``_last_wilson`` then describes the reduced factorisations (n_iter / status [n_signals, n_groups])."""
-        from . import engine
+        from . import _stage_d
         N, C = self._shape5[3], self._shape5[4]
         self._check_mvar_signals()
         G = self._mvar_factor_device()
         accum, n_obs, n_freq = self._csm_records("granger")
-        n_groups = accum.shape[0] // n_freq
-        out, n_iter, status, (iters, not_conv, fallback) = engine.conditional_granger(
-            G, n_groups, N, C, accum=accum, n_freq_accum=n_freq, planes=_lib.PLANE_CSM,
+        mem = self._memory(accum)
+        out, n_iter, status, summary = _stage_d.conditional_granger(
+            mem, G, accum.shape[0] // n_freq, N, C, accum=accum, n_freq_accum=n_freq, planes=_lib.PLANE_CSM,
             n_obs=self._n_observations_total(n_obs))
-        st = status.cpu().numpy()
-        if fallback:
-            logger.warning("Computing the initial conditions using the Cholesky failed. "
-                           f"Using the identity as initial condition ({fallback} reduced problems).")
-        if not_conv:
-            logger.warning(f"Maximum iterations reached. {st.size - not_conv} of {st.size} converged")
-        self._last_wilson = dict(iterations=iters, not_converged=not_conv, cholesky_fallbacks=fallback,
-                                 n_iter=n_iter.cpu().numpy(), status=st)
-        return engine.to_host(out).reshape(self._kept_shape() + (N // 2 + 1, C, C))
+        self._wilson_done(mem, "reduced problems", summary, n_iter, status)
+        return mem.download(out).reshape(self._kept_shape() + (N // 2 + 1, C, C))
 
     # (the reference declares the method without arguments, tests/golden/api_surface.json: group_labels is bound here)
     def blockwise_spectral_granger_prediction(self, *args, **kwargs):
@@ -802,25 +802,16 @@ class Connectivity:
                            "(rank-deficient spectra): NaN")
         return batches
 
-    def _blockwise_wilson(self, iters, not_conv, fallback, n_iter, status):
-        if fallback:
-            logger.warning("Computing the initial conditions using the Cholesky failed. "
-                           f"Using the identity as initial condition ({fallback} group-pair problems).")
-        if not_conv:
-            logger.warning(f"Maximum iterations reached. {status.size - not_conv} of {status.size} converged")
-        self._last_wilson = dict(iterations=int(iters), not_converged=int(not_conv), cholesky_fallbacks=int(fallback),
-                                 n_iter=n_iter, status=status)
-
     def _blockwise_granger(self, group_labels):
-        from . import engine
+        from . import _stage_d
         N = self._shape5[3]
         labels, pairs = self._blockwise_pairs(group_labels)      # (the labels are checked before any device work)
         accum, n_obs, n_freq = self._csm_records("granger")
         n_total = self._n_observations_total(n_obs)
         batches = self._blockwise_batches(pairs, n_total)
-        n_groups = accum.shape[0] // n_freq
-        out, n_iter, status, (iters, not_conv, fallback) = engine.blockwise_granger(
-            n_groups, N, self._shape5[4], batches, len(labels), accum=accum, n_freq_accum=n_freq, planes=_lib.PLANE_CSM,
-            n_obs=n_total)
-        self._blockwise_wilson(iters, not_conv, fallback, n_iter.cpu().numpy(), status.cpu().numpy())
-        return engine.to_host(out).reshape(self._kept_shape() + (N // 2 + 1, len(labels), len(labels))), labels
+        mem = self._memory(accum)
+        out, n_iter, status, summary = _stage_d.blockwise_granger(
+            mem, accum.shape[0] // n_freq, N, self._shape5[4], batches, len(labels), accum=accum, n_freq_accum=n_freq,
+            planes=_lib.PLANE_CSM, n_obs=n_total)
+        self._wilson_done(mem, "group-pair problems", summary, n_iter, status)
+        return mem.download(out).reshape(self._kept_shape() + (N // 2 + 1, len(labels), len(labels))), labels

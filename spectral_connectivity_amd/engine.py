@@ -10,7 +10,7 @@ from ctypes import byref, c_int64, c_void_p
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _stage_d
 from ._lib import SpectraDesc
 
 # connectivity.py:67-75 of the reference: which of (window, trial, taper) are averaged
@@ -364,7 +364,6 @@ def plane_slots(planes):
 
 
 MAX_KERNEL_SIGNALS = 256          # SC_MAX_SIGNALS of csrc/sc_common.h: what one launch of the stage-B kernels stages per observation row
-BLOCK_SIGNALS = 128               # channel block of the tiling beyond that (a multiple of the 16-channel record tile)
 
 
 def _channel_subset(spectra, cols):
@@ -383,15 +382,13 @@ def _channel_subset(spectra, cols):
 
 def _accumulate_blocked(spectra, expectation_type, planes, n_freq, mark, row_multiple):
     """Stage B for MORE signals than one launch of the kernels stages (256): the reference has no limit
-    (connectivity.py:447-526), a 306-channel MEG array is an ordinary input.  The channels are cut into blocks of 128; every pair
-    of blocks (a < b) is accumulated as a request of its own on the gathered spectra of the two blocks (<= 256 signals: the
-    ordinary kernels), and its 16 x 16 record tiles are copied to their places in the full record -- the cross tiles of (a, b)
-    from that pair, the tiles inside block a from the pair (a, a + 1) (the last block from the last pair).  Every entry of the
-    record is computed by the same kernels as for <= 256 signals; what the tiling costs is the tiles inside the blocks being
-    computed once per partner (about twice the arithmetic of an untiled triangle at three blocks) and one gathering copy of the
-    spectra per pair."""
+    (connectivity.py:447-526), a 306-channel MEG array is an ordinary input.  The channels are cut into blocks of
+    _lib.BLOCK_SIGNALS; every pair of blocks (a < b) is accumulated as a request of its own on the gathered spectra of the two
+    blocks (<= 256 signals: the ordinary kernels), and its 16 x 16 record tiles are copied to their places in the full record
+    (_lib.tile_plan: which tiles, where to).  Every entry of the record is computed by the same kernels as for <= 256 signals;
+    what the tiling costs is the tiles inside the blocks being computed once per partner (about twice the arithmetic of an
+    untiled triangle at three blocks) and one gathering copy of the spectra per pair."""
     C = spectra.C
-    n_blk = -(-C // BLOCK_SIGNALS)
     n_bins, fpb, _, n_obs = accum_layout(spectra, expectation_type, planes, n_freq)
     NB = -(-C // 16)
     n_tiles = NB * (NB + 1) // 2
@@ -400,37 +397,13 @@ def _accumulate_blocked(spectra, expectation_type, planes, n_freq, mark, row_mul
     full = _record_tensor(n_bins, fpb, dtype, spectra.device, row_multiple)
     full_v = full.view(n_bins, n_planes, n_tiles, 256)
     dev = spectra.device
-
-    def tile(bi, bj, nb):
-        return bi * nb - bi * (bi - 1) // 2 + (bj - bi)
-
-    per = BLOCK_SIGNALS // 16
-    for a in range(n_blk - 1):
-        for b in range(a + 1, n_blk):
-            ca = torch.arange(a * BLOCK_SIGNALS, (a + 1) * BLOCK_SIGNALS, device=dev)
-            cb = torch.arange(b * BLOCK_SIGNALS, min((b + 1) * BLOCK_SIGNALS, C), device=dev)
-            sub = _channel_subset(spectra, torch.cat([ca, cb]))
-            rec, _ = accumulate(sub, expectation_type, planes, n_freq=n_freq, mark=mark)
-            nb_s = -(-sub.C // 16)
-            rec_v = rec.view(n_bins, n_planes, nb_s * (nb_s + 1) // 2, 256)
-            src, dst = [], []
-            for ti in range(nb_s):
-                for tj in range(ti, nb_s):
-                    in_a_i, in_a_j = ti < per, tj < per
-                    if in_a_i and in_a_j:
-                        keep = b == a + 1                                   # inside block a: from its first partner
-                    elif not in_a_i and not in_a_j:
-                        keep = a == n_blk - 2 and b == n_blk - 1            # inside the last block: from the last pair
-                    else:
-                        keep = True                                         # cross tiles of (a, b)
-                    if keep:
-                        gi = a * per + ti if in_a_i else b * per + (ti - per)
-                        gj = a * per + tj if in_a_j else b * per + (tj - per)
-                        src.append(tile(ti, tj, nb_s))
-                        dst.append(tile(gi, gj, NB))
-            src_t, dst_t = torch.tensor(src, device=dev), torch.tensor(dst, device=dev)
-            full_v[:, :, dst_t] = rec_v[:, :, src_t]
-            del rec, sub
+    for _, _, cols, src, dst in _lib.tile_plan(C):
+        sub = _channel_subset(spectra, torch.as_tensor(cols, device=dev))
+        rec, _ = accumulate(sub, expectation_type, planes, n_freq=n_freq, mark=mark)
+        nb_s = -(-sub.C // 16)
+        rec_v = rec.view(n_bins, n_planes, nb_s * (nb_s + 1) // 2, 256)
+        full_v[:, :, torch.tensor(dst, device=dev)] = rec_v[:, :, torch.tensor(src, device=dev)]
+        del rec, sub
     return full, n_obs
 
 
@@ -567,7 +540,7 @@ def accumulate(spectra, expectation_type, planes, n_freq=None, mark=None, use_fu
 
 def rec_planes(accum, planes):
     """`planes` as the consumers of a record tensor want it: with SC_RECORD_F64 when the records are doubles."""
-    return (planes | _lib.RECORD_F64) if accum.dtype == torch.float64 else (planes & ~_lib.RECORD_F64)
+    return _lib.record_planes(planes, accum.dtype == torch.float64)
 
 
 def fold_parts(accum):
@@ -664,273 +637,109 @@ def measure_multi(accum, n_signals, planes, n_obs, which, wide=None, stacked=Fal
     return outs
 
 
-MAX_WILSON_ITERATIONS = 1024      # iterations the device kernels can log (WILSON_HIST / MV_HIST in csrc)
+# ---- stage D: the call sequences live in _stage_d.py (shared with the torch-free host); here are the memory adapter of this host
+# and the public functions, each one call into its driver ---------------------------------------------------------------------
+MAX_WILSON_ITERATIONS = _stage_d.MAX_WILSON_ITERATIONS
+check_max_iterations = _stage_d.check_max_iterations
+GRANGER_WORK_BYTES = _lib.GRANGER_WORK_BYTES      # (the bound the drivers read is _lib.GRANGER_WORK_BYTES)
+_TORCH_DTYPES = {np.dtype(np.uint8): torch.uint8, np.dtype(np.int32): torch.int32, np.dtype(np.float64): torch.float64,
+                 np.dtype(np.complex128): torch.complex128}
 
 
-def check_max_iterations(max_iterations):
-    """The reference takes any positive count (minimum_phase_decomposition.py:227-322); the device kernels log at most 1024."""
-    if not 1 <= int(max_iterations) <= MAX_WILSON_ITERATIONS:
-        raise ValueError(f"max_iterations must be between 1 and {MAX_WILSON_ITERATIONS} on the device path (got {max_iterations}); "
-                         "Wilson's iteration converges in tens of steps or not at all")
-    return int(max_iterations)
+class TorchMemory:
+    """The memory adapter of the stage-D drivers (_stage_d.py) on this host: tensors of ``device``, calls on the current stream."""
 
+    def __init__(self, device):
+        self.device = device
 
-GRANGER_WORK_BYTES = 8 << 30      # workspace bound of one sc_granger_pairwise_f64 call (160 bytes per problem and bin)
+    def empty(self, shape, dtype):
+        return torch.empty(shape, dtype=_TORCH_DTYPES[np.dtype(dtype)], device=self.device)
+
+    def zeros(self, shape, dtype):
+        return torch.zeros(shape, dtype=_TORCH_DTYPES[np.dtype(dtype)], device=self.device)
+
+    def upload(self, array):
+        return torch.from_numpy(np.ascontiguousarray(array)).to(self.device)
+
+    def ptr(self, t, first_row=0):
+        return c_void_p(t.data_ptr() + (first_row * t.stride(0) * t.element_size() if first_row else 0))
+
+    stream = staticmethod(_stream)
+    download = staticmethod(to_host)
+
+    def is_f64(self, record):
+        return record.dtype == torch.float64
+
+    def fill_nan(self, t):
+        t.fill_(float("nan"))
+
+    def read_int(self, t):
+        return int(t.item())
+
+    def hstack(self, chunks, n_rows):
+        return chunks[0] if len(chunks) == 1 else torch.cat([c.view(n_rows, -1) for c in chunks], dim=1).reshape(-1)
 
 
 def granger_pairwise(accum, n_groups, n_freq_accum, n_fft, n_signals, planes, n_obs, pairs,
                      tolerance=1e-8, max_iterations=60):
-    """Batched 2x2 Wilson + spectral Granger (sc_wilson.hip).  Returns (out, n_iter, status, summary) with
-    summary = (iterations run, problems not converged, problems started from the identity because their lag-0
-    covariance was not positive definite).  A long pair list is walked in chunks that bound the workspace; every
-    chunk writes its pairs into the same output."""
-    lib = _lib.load()
-    max_iterations = check_max_iterations(max_iterations)
-    dev = accum.device
-    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-    n_pairs = pairs.shape[0]
-    F = n_fft // 2 + 1
-    out = torch.empty((n_groups, F, n_signals, n_signals), dtype=torch.float64, device=dev)
-    n_iter = torch.empty((n_groups, n_pairs), dtype=torch.int32, device=dev)
-    status = torch.empty((n_groups, n_pairs), dtype=torch.int32, device=dev)
-    per_pair = n_groups * n_fft * 160
-    chunk = int(max(1, min(n_pairs, GRANGER_WORK_BYTES // per_pair)))
-    nbytes = ctypes.c_size_t()
-    _lib.check(lib.sc_granger_workspace_bytes(n_groups, chunk, n_fft, byref(nbytes)), "sc_granger_workspace_bytes")
-    work = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
-    iters = not_conv = fallback = 0
-    for p0 in range(0, n_pairs, chunk):
-        n = min(chunk, n_pairs - p0)
-        pairs_t = torch.from_numpy(pairs[p0:p0 + n]).to(dev)
-        it_c = torch.empty((n_groups * n,), dtype=torch.int32, device=dev)
-        st_c = torch.empty((n_groups * n,), dtype=torch.int32, device=dev)
-        summary = (ctypes.c_int32 * 3)(0, 0, 0)
-        _lib.check(lib.sc_granger_pairwise_f64(_ptr(accum), n_groups, n_freq_accum, n_fft, n_signals,
-                                               rec_planes(accum, planes), n_obs,
-                                               _ptr(pairs_t), n, tolerance, max_iterations, _ptr(work), nbytes.value,
-                                               _lib.GRANGER_KEEP_OUTPUT if p0 else 0, _ptr(out), _ptr(it_c),
-                                               _ptr(st_c), summary, _stream()), "sc_granger_pairwise_f64")
-        n_iter[:, p0:p0 + n] = it_c.view(n_groups, n)
-        status[:, p0:p0 + n] = st_c.view(n_groups, n)
-        iters = max(iters, summary[0])
-        not_conv += summary[1]
-        fallback += summary[2]
-    return out, n_iter.reshape(-1), status.reshape(-1), (iters, not_conv, fallback)
-
-
-def _mvar_workspace(n_groups, n_signals, n_fft, dev):
-    lib = _lib.load()
-    nbytes = ctypes.c_size_t()
-    _lib.check(lib.sc_mvar_workspace_bytes(n_groups, n_signals, n_fft, byref(nbytes)), "sc_mvar_workspace_bytes")
-    return torch.empty((nbytes.value,), dtype=torch.uint8, device=dev), nbytes.value
+    """Batched 2x2 Wilson + spectral Granger (sc_wilson.hip): _stage_d.granger_pairwise on device tensors.  Returns (out, n_iter,
+    status, summary), n_iter / status [n_groups, n_pairs] flattened."""
+    return _stage_d.granger_pairwise(TorchMemory(accum.device), accum, n_groups, n_freq_accum, n_fft, n_signals, planes, n_obs, pairs,
+                                     tolerance, max_iterations)
 
 
 def mvar_factor(n_groups, n_fft, n_signals, accum=None, n_freq_accum=0, planes=0, n_obs=1, spectra=None,
                 tolerance=1e-8, max_iterations=60):
     """Full C x C Wilson factor (sc_mvar.hip) of accumulator records or of a two-sided complex128 spectrum
     tensor [n_groups, n_fft, C, C].  Returns (G [n_groups, n_fft, C, C] complex128, n_iter, status, summary)."""
-    max_iterations = check_max_iterations(max_iterations)
-    lib = _lib.load()
     src = accum if accum is not None else spectra
-    dev = src.device
-    work, nbytes = _mvar_workspace(n_groups, n_signals, n_fft, dev)
-    G = torch.empty((n_groups, n_fft, n_signals, n_signals), dtype=torch.complex128, device=dev)
-    n_iter = torch.empty((n_groups,), dtype=torch.int32, device=dev)
-    status = torch.empty((n_groups,), dtype=torch.int32, device=dev)
-    summary = (ctypes.c_int32 * 3)(0, 0, 0)
-    _lib.check(lib.sc_mvar_factor_f64(_ptr(accum) if accum is not None else None,
-                                      _ptr(spectra) if spectra is not None else None, n_groups, n_freq_accum, n_fft,
-                                      n_signals, rec_planes(accum, planes) if accum is not None else planes, n_obs,
-                                      tolerance, max_iterations, _ptr(work), nbytes, _ptr(G),
-                                      _ptr(n_iter), _ptr(status), summary, _stream()), "sc_mvar_factor_f64")
-    return G, n_iter, status, (summary[0], summary[1], summary[2])
+    return _stage_d.mvar_factor(TorchMemory(src.device), n_groups, n_fft, n_signals, accum, n_freq_accum, planes, n_obs, spectra,
+                                tolerance, max_iterations)
 
 
 def conditional_granger(G, n_groups, n_fft, n_signals, accum=None, n_freq_accum=0, planes=0, n_obs=1, spectra=None,
                         tolerance=1e-8, max_iterations=60):
-    """Conditional spectral Granger prediction (sc_conditional.hip) from the cached full factor ``G`` [n_groups, n_fft, C, C]
-    and the records (or a two-sided complex128 spectrum tensor) it was factored from: one reduced (C - 1)-signal Wilson
-    factorisation per dropped signal, batched over the dropped signals of a chunk.  Returns (out [n_groups, n_fft/2+1, C, C]
-    float64, out[..., i, j] = j -> i given the rest, n_iter [C, n_groups], status [C, n_groups], summary) with summary =
-    (iterations run, reduced problems not converged, identity starts)."""
-    lib = _lib.load()
-    max_iterations = check_max_iterations(max_iterations)
-    C = n_signals
-    dev = G.device
-    F = n_fft // 2 + 1
-
-    def ws(n_dropped):
-        nbytes = ctypes.c_size_t()
-        _lib.check(lib.sc_conditional_granger_workspace_bytes(n_groups, C, n_fft, n_dropped, byref(nbytes)),
-                   "sc_conditional_granger_workspace_bytes")
-        return nbytes.value
-
-    chunk = _lib.conditional_chunk(n_groups, C, ws)
-    nbytes = ws(chunk)
-    work = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    out = torch.empty((n_groups, F, C, C), dtype=torch.float64, device=dev)
-    n_iter = torch.empty((C, n_groups), dtype=torch.int32, device=dev)
-    status = torch.empty((C, n_groups), dtype=torch.int32, device=dev)
-    dropped = torch.arange(C, dtype=torch.int32, device=dev)
-    iters = not_conv = fallback = 0
-    for j0 in range(0, C, chunk):
-        n = min(chunk, C - j0)
-        summary = (ctypes.c_int32 * 3)(0, 0, 0)
-        _lib.check(lib.sc_conditional_granger_f64(_ptr(accum) if accum is not None else None,
-                                                  _ptr(spectra) if spectra is not None else None, n_groups, n_freq_accum,
-                                                  n_fft, C, rec_planes(accum, planes) if accum is not None else planes, n_obs,
-                                                  _ptr(G), _ptr(dropped[j0:j0 + n]), n, tolerance, max_iterations, _ptr(work),
-                                                  nbytes, _lib.CONDITIONAL_KEEP_OUTPUT if j0 else 0, _ptr(out),
-                                                  _ptr(n_iter[j0:j0 + n]), _ptr(status[j0:j0 + n]), summary, _stream()),
-                   "sc_conditional_granger_f64")
-        iters = max(iters, summary[0])
-        not_conv += summary[1]
-        fallback += summary[2]
-    return out, n_iter, status, (iters, not_conv, fallback)
+    """Conditional spectral Granger prediction (sc_conditional.hip) from the cached full factor ``G``: _stage_d.conditional_granger.
+    Returns (out [n_groups, n_fft/2+1, C, C] float64, n_iter [C, n_groups], status [C, n_groups], summary)."""
+    return _stage_d.conditional_granger(TorchMemory(G.device), G, n_groups, n_fft, n_signals, accum, n_freq_accum, planes, n_obs,
+                                        spectra, tolerance, max_iterations)
 
 
 def blockwise_granger(n_groups, n_fft, n_signals, batches, n_blocks, accum=None, n_freq_accum=0, planes=0, n_obs=1, spectra=None,
                        tolerance=1e-8, max_iterations=60, device=None):
-    """Blockwise spectral Granger prediction (sc_blockwise.hip) from the records (or a two-sided complex128 spectrum tensor):
-    one m-signal Wilson factorisation per (block pair, group), the pairs of one size m batched under the workspace cap.
-    ``batches``: {m: (members [n, m], split [n], cell [n, 2])} int32 arrays (_lib.blockwise_batches).  Returns (out [n_groups,
-    n_fft/2+1, n_blocks, n_blocks] float64, out[..., a, b] = b -> a, NaN where no pair was computed, n_iter [pairs, n_groups],
-    status [pairs, n_groups] in the order of the batches, summary) with summary = (iterations run, problems not converged,
-    identity starts)."""
-    lib = _lib.load()
-    max_iterations = check_max_iterations(max_iterations)
+    """Blockwise spectral Granger prediction (sc_blockwise.hip): _stage_d.blockwise_granger.  Returns (out [n_groups, n_fft/2+1,
+    n_blocks, n_blocks] float64, n_iter [pairs, n_groups], status [pairs, n_groups] in the order of ``batches``, summary)."""
     dev = device if device is not None else (accum if accum is not None else spectra).device
-    F = n_fft // 2 + 1
-    total = sum(len(split) for _, split, _ in batches.values())
-    out = torch.empty((n_groups, F, n_blocks, n_blocks), dtype=torch.float64, device=dev)
-    n_iter = torch.zeros((total, n_groups), dtype=torch.int32, device=dev)
-    status = torch.zeros((total, n_groups), dtype=torch.int32, device=dev)
-    iters = not_conv = fallback = 0
-    row, flags = 0, 0              # the first call NaN-fills the output, the others keep it
-    for m, (members, split, cell) in batches.items():
-        n_pairs = len(split)
-
-        def ws(n, m=m):
-            nbytes = ctypes.c_size_t()
-            _lib.check(lib.sc_blockwise_granger_workspace_bytes(n_groups, m, n_fft, n, byref(nbytes)),
-                       "sc_blockwise_granger_workspace_bytes")
-            return nbytes.value
-
-        chunk = _lib.blockwise_chunk(n_groups, n_pairs, ws)
-        nbytes = ws(chunk)
-        work = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        d_members = torch.as_tensor(members, device=dev)
-        d_split = torch.as_tensor(split, device=dev)
-        d_cell = torch.as_tensor(cell, device=dev)
-        for q0 in range(0, n_pairs, chunk):
-            n = min(chunk, n_pairs - q0)
-            summary = (ctypes.c_int32 * 3)(0, 0, 0)
-            _lib.check(lib.sc_blockwise_granger_f64(_ptr(accum) if accum is not None else None,
-                                                    _ptr(spectra) if spectra is not None else None, n_groups, n_freq_accum, n_fft,
-                                                    n_signals, rec_planes(accum, planes) if accum is not None else planes, n_obs,
-                                                    _ptr(d_members[q0:q0 + n]), _ptr(d_split[q0:q0 + n]), _ptr(d_cell[q0:q0 + n]), n,
-                                                    m, n_blocks, tolerance, max_iterations, _ptr(work), nbytes,
-                                                    flags, _ptr(out), _ptr(n_iter[row + q0:row + q0 + n]),
-                                                    _ptr(status[row + q0:row + q0 + n]), summary, _stream()),
-                       "sc_blockwise_granger_f64")
-            iters = max(iters, summary[0])
-            not_conv += summary[1]
-            fallback += summary[2]
-            flags = _lib.BLOCKWISE_KEEP_OUTPUT
-        row += n_pairs
-        del work
-    if not flags:
-        out.fill_(float("nan"))
-    return out, n_iter, status, (iters, not_conv, fallback)
+    return _stage_d.blockwise_granger(TorchMemory(dev), n_groups, n_fft, n_signals, batches, n_blocks, accum, n_freq_accum, planes,
+                                      n_obs, spectra, tolerance, max_iterations)
 
 
 def mvar_measure(G, which):
     """A directed MVAR measure / model quantity (``_lib.MVAR_*``) from the minimum-phase factor G."""
-    lib = _lib.load()
-    n_groups, n_fft, C, _ = G.shape
-    F = n_fft // 2 + 1
-    work, nbytes = _mvar_workspace(n_groups, C, n_fft, G.device)
-    if which == _lib.MVAR_NOISE_COVARIANCE:
-        out = torch.empty((n_groups, C, C), dtype=torch.float64, device=G.device)
-    elif which in (_lib.MVAR_TRANSFER, _lib.MVAR_COEFFICIENTS):
-        out = torch.empty((n_groups, F, C, C), dtype=torch.complex128, device=G.device)
-    else:
-        out = torch.empty((n_groups, F, C, C), dtype=torch.float64, device=G.device)
-    _lib.check(lib.sc_mvar_measure_f64(_ptr(G), n_groups, n_fft, C, which, _ptr(out), _ptr(work), nbytes, _stream()),
-               "sc_mvar_measure_f64")
-    return out
+    return _stage_d.mvar_measure(TorchMemory(G.device), G, which)
 
 
 def global_coherence(accum, n_groups, n_freq_accum, n_fft, n_signals, planes, n_obs, max_rank, ascending):
     """Leading eigenpairs of the CSM per (window, two-sided bin) (sc_global.hip)."""
-    lib = _lib.load()
-    dev = accum.device
-    values = torch.empty((n_groups, n_fft, max_rank), dtype=torch.float64, device=dev)
-    vectors = torch.empty((n_groups, n_fft, n_signals, max_rank), dtype=torch.complex128, device=dev)
-    _lib.check(lib.sc_global_coherence_f64(_ptr(accum), n_groups, n_freq_accum, n_fft, n_signals,
-                                           rec_planes(accum, planes), n_obs,
-                                           max_rank, int(ascending), _ptr(values), _ptr(vectors), _stream()),
-               "sc_global_coherence_f64")
-    return values, vectors
+    return _stage_d.global_coherence(TorchMemory(accum.device), accum, n_groups, n_freq_accum, n_fft, n_signals, planes, n_obs,
+                                     max_rank, ascending)
 
 
 def canonical_coherence(accum, n_signals, planes, n_obs, groups):
     """groups: list of int arrays (channel indices per group).  Returns ([n_bins, G, G] float64, n_fail)."""
-    lib = _lib.load()
-    dev = accum.device
-    G = len(groups)
-    cmax = max(len(g) for g in groups)
-    stride = 16 if cmax <= 16 else (32 if cmax <= 32 else 128)      # member-table stride of the kernel that takes this size
-    members = np.full((G, stride), -1, dtype=np.int32)
-    for i, g in enumerate(groups):
-        members[i, : min(len(g), stride)] = np.asarray(g, dtype=np.int32)[:stride]
-    sizes = np.array([len(g) for g in groups], dtype=np.int32)
-    members_t, sizes_t = torch.from_numpy(members).to(dev), torch.from_numpy(sizes).to(dev)
-    n_bins = accum.shape[0]
-    out = torch.empty((n_bins, G, G), dtype=torch.float64, device=dev)
-    fail = torch.zeros((1,), dtype=torch.int32, device=dev)
-    _lib.check(lib.sc_canonical_coherence_f64(_ptr(accum), n_bins, n_signals, rec_planes(accum, planes), n_obs,
-                                              _ptr(members_t),
-                                              _ptr(sizes_t), G, int(cmax), _ptr(out), _ptr(fail), _stream()),
-               "sc_canonical_coherence_f64")
-    return out, int(fail.item())
+    return _stage_d.canonical_coherence(TorchMemory(accum.device), accum, n_signals, planes, n_obs, groups)
 
 
 def imaginary_interaction(accum, n_signals, planes, n_obs, members, sizes):
     """members / sizes: _lib.member_table of the groups.  Returns (MIC, MIM [n_bins, G, G] float64, n_fail)."""
-    lib = _lib.load()
-    dev = accum.device
-    G = len(sizes)
-    members_t, sizes_t = torch.from_numpy(members).to(dev), torch.from_numpy(sizes).to(dev)
-    n_bins = accum.shape[0]
-    mic = torch.empty((n_bins, G, G), dtype=torch.float64, device=dev)
-    mim = torch.empty((n_bins, G, G), dtype=torch.float64, device=dev)
-    fail = torch.zeros((1,), dtype=torch.int32, device=dev)
-    _lib.check(lib.sc_imaginary_interaction_f64(_ptr(accum), n_bins, n_signals, rec_planes(accum, planes), n_obs, _ptr(members_t),
-                                                _ptr(sizes_t), G, int(sizes.max()), _ptr(mic), _ptr(mim), _ptr(fail), _stream()),
-               "sc_imaginary_interaction_f64")
-    return mic, mim, int(fail.item())
+    return _stage_d.imaginary_interaction(TorchMemory(accum.device), accum, n_signals, planes, n_obs, members, sizes)
 
 
 def jackknife(spectra, expectation_type, total, planes, measures, over, n_units_total, n_freq=None, unit_range=None):
-    """Delete-one jackknife sums (sc_jackknife.hip): ONE pass over the complex64 / complex128 spectra for every measure of the mask
-    ``measures`` (_lib.JACKKNIFE_MEASURES) against the total CSM record ``total`` (any rank's sum).  ``over``: _lib.JACKKNIFE_OVER;
-    ``n_units_total``: delete units of the whole job; ``unit_range``: the units of these spectra to walk (default: all of them).
-    Returns (float64 device tensor laid out as _lib.jackknife_blocks says, n_bins)."""
-    lib = _lib.load()
-    total = fold_parts(total)
-    d = spectra.desc(expectation_type, n_freq)
-    n_bins, n_units, unit_size, n_out = c_int64(), c_int64(), c_int64(), c_int64()
-    _lib.check(lib.sc_jackknife_layout(byref(d), measures, over, byref(n_bins), byref(n_units), byref(unit_size), byref(n_out)),
-               "sc_jackknife_layout")
-    lo, hi = (0, n_units.value) if unit_range is None else unit_range
-    ws_bytes = int(lib.sc_jackknife_workspace_bytes(byref(d), measures, over, lo, hi))
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=spectra.device) if ws_bytes else None
-    out = torch.empty((n_out.value,), dtype=torch.float64, device=spectra.device)
-    fn = lib.sc_jackknife_f64 if spectra.f64 else lib.sc_jackknife_f32
-    _lib.check(fn(_ptr(spectra.X), byref(d), _ptr(total), rec_planes(total, planes), measures, over, lo, hi, n_units_total, _ptr(out),
-                  _ptr(ws) if ws is not None else None, ws_bytes, _stream()), "sc_jackknife")
-    return out, n_bins.value
+    """Delete-one jackknife sums (sc_jackknife.hip) of the spectra against the total CSM record ``total`` (partial records are
+    folded first): _stage_d.jackknife.  Returns (float64 device tensor laid out as _lib.jackknife_blocks says, n_bins)."""
+    return _stage_d.jackknife(TorchMemory(spectra.device), spectra, expectation_type, fold_parts(total), planes, measures, over,
+                              n_units_total, n_freq, unit_range)
 
 
 class GraphedMeasures:

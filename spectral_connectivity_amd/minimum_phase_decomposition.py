@@ -8,7 +8,6 @@ larger systems (up to ``sc_mvar_max_signals()`` = 512 signals) go through ``sc_m
 (register-resident Gauss-Jordan solves, one workgroup per window and frequency bin).  There is no CPU fallback.
 """
 import ctypes
-from ctypes import byref
 from logging import getLogger
 
 import numpy as np
@@ -29,7 +28,8 @@ def minimum_phase_decomposition(cross_spectral_matrix, tolerance=1e-8, max_itera
     import torch
 
     from . import _lib
-    from .engine import _ptr, _stream, check_max_iterations
+    from . import _stage_d
+    from .engine import TorchMemory, _ptr, _stream, check_max_iterations
     max_iterations = check_max_iterations(max_iterations)
     _lib.require_gpu()
     lib = _lib.load()
@@ -76,14 +76,12 @@ def minimum_phase_decomposition(cross_spectral_matrix, tolerance=1e-8, max_itera
     for p0 in range(0, P, step):
         n = min(step, P - p0)
         S_d = torch.from_numpy(S[p0:p0 + n]).to(dev)
-        nbytes = ctypes.c_size_t()
-        _lib.check(lib.sc_granger_workspace_bytes(1, n, N, byref(nbytes)), "sc_granger_workspace_bytes")
-        work = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
+        work, nbytes = _stage_d.granger_workspace(TorchMemory(dev), 1, n, N)
         G_d = torch.empty((n, 4, N), dtype=torch.complex128, device=dev)
         n_iter = torch.empty((n,), dtype=torch.int32, device=dev)
         status = torch.empty((n,), dtype=torch.int32, device=dev)
         summary = (ctypes.c_int32 * 3)(0, 0, 0)
-        _lib.check(lib.sc_wilson_factor_f64(_ptr(S_d), n, N, tolerance, max_iterations, _ptr(work), nbytes.value,
+        _lib.check(lib.sc_wilson_factor_f64(_ptr(S_d), n, N, tolerance, max_iterations, _ptr(work), nbytes,
                                             _ptr(G_d), _ptr(n_iter), _ptr(status), summary, _stream()),
                    "sc_wilson_factor_f64")
         if summary[2]:

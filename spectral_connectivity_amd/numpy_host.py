@@ -12,19 +12,20 @@ page-locked memory, copies and the stream come from the library's own ``sc_devic
                             n_time_samples_per_window=256, n_time_samples_per_step=128,
                             measures=("coherence_magnitude", "weighted_phase_lag_index"))
 
-Scope: the float32 engine's hot path -- stage A (fused transform, or tapered windows + rocFFT for the lengths the fused
-kernel does not take), stage B (every accumulator plane), the expectation-type measures of the reference
-(connectivity.py:612-1159), ``expectation_type`` as in the reference.  Results are float64 / complex128 NumPy arrays
-shaped like the reference's; plus, since round 4, stage D on float32 records: ``pairwise_spectral_granger_prediction`` (batched
-2 x 2 Wilson) and ``canonical_coherence``.  Everything else (full Wilson / MVAR measures, global coherence, the float64 engine,
-multi-GPU) lives on the PyTorch host.  One process uses one host: see _lib.load().
+Scope of the functional interface below: the float32 engine's hot path -- stage A (fused transform, or tapered windows + rocFFT
+for the lengths the fused kernel does not take), stage B (every accumulator plane), the expectation-type measures of the reference
+(connectivity.py:612-1159), ``expectation_type`` as in the reference -- and stage D on float32 records through the shared drivers
+of ``_stage_d.py``: ``pairwise_spectral_granger_prediction``, ``canonical_coherence``, ``mvar_measures`` (the full Wilson factor)
+and ``global_coherence``.  Results are float64 / complex128 NumPy arrays shaped like the reference's.  The float64 engine, the
+other stage-D measures and more than 256 signals are on this host too, through the public classes (``numpy_api``, SC_HIP_HOST=numpy);
+multi-GPU needs the PyTorch host.  One process uses one host: see _lib.load().
 """
 import ctypes
-from ctypes import byref, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import byref, c_int64, c_void_p
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _stage_d
 from ._lib import SpectraDesc
 
 EXPECTATION_AXES = _lib.EXPECTATION_AXES
@@ -76,6 +77,70 @@ class DeviceBuffer:
             self.free()
         except Exception:
             pass
+
+
+class DeviceArray:
+    """A DeviceBuffer that knows its shape and dtype: what this host holds where the PyTorch host holds a tensor (accumulator
+    records [n_bins][floats_per_bin], the arrays of the stage-D drivers).  The memory goes back with the buffer."""
+
+    def __init__(self, buf, shape, dtype):
+        self.buf, self.shape, self.dtype = buf, tuple(int(n) for n in shape), np.dtype(dtype)
+
+    @property
+    def f64(self):
+        return self.dtype == np.float64
+
+
+class NumpyMemory:
+    """The memory adapter of the stage-D drivers (_stage_d.py) on this host: DeviceArray over NumpyHost.alloc / upload / download."""
+
+    def __init__(self, host):
+        self.host = host
+
+    def empty(self, shape, dtype):
+        dtype = np.dtype(dtype)
+        return DeviceArray(self.host.alloc(int(np.prod(shape, dtype=np.int64)) * dtype.itemsize), shape, dtype)
+
+    def zeros(self, shape, dtype):
+        a = self.empty(shape, dtype)
+        if a.buf.n_bytes:
+            _lib.check(self.host.lib.sc_memset_zero(a.buf.ptr, a.buf.n_bytes, self.host.stream), "sc_memset_zero")
+        return a
+
+    def upload(self, array):
+        array = np.ascontiguousarray(array)
+        return DeviceArray(self.host.upload(array), array.shape, array.dtype)
+
+    def ptr(self, a, first_row=0):
+        """(``a``: a DeviceArray, or the raw DeviceBuffer of the spectra)"""
+        if not first_row:
+            return getattr(a, "buf", a).ptr
+        return c_void_p(a.buf.ptr.value + first_row * int(np.prod(a.shape[1:], dtype=np.int64)) * a.dtype.itemsize)
+
+    def stream(self):
+        return self.host.stream
+
+    def is_f64(self, record):
+        return record.f64
+
+    def fill_nan(self, a):
+        src = np.full(a.shape, np.nan, dtype=a.dtype)
+        _lib.check(self.host.lib.sc_memcpy_h2d(a.buf.ptr, src.ctypes.data_as(c_void_p), src.nbytes, self.host.stream), "sc_memcpy_h2d")
+        self.host.synchronize()
+
+    def read_int(self, a):
+        return int(self.download(a).ravel()[0])
+
+    def hstack(self, chunks, n_rows):
+        if len(chunks) == 1:
+            return chunks[0]
+        return self.upload(np.concatenate([self.download(c).reshape(n_rows, -1) for c in chunks], axis=1).reshape(-1))
+
+    def download(self, a):
+        """A NumPy array of its own (not the page-locked block, which goes back to the pool)."""
+        if not a.buf.n_bytes:
+            return np.zeros(a.shape, dtype=a.dtype)
+        return np.array(self.host.download(a.buf, a.shape, a.dtype))
 
 
 class PinnedArray(np.ndarray):
@@ -148,6 +213,9 @@ class NpSpectra(dict):
     def n_fft(self):
         return self["N"]
 
+    def desc(self, expectation_type, n_freq=None, padded=False):
+        return NumpyHost._desc(self, expectation_type, padded, n_freq)
+
     def free(self):
         for key in ("X", "P", "scale"):
             if self.get(key) is not None:
@@ -171,6 +239,7 @@ class NumpyHost:
         self.stream = s
         self._twiddles = {}
         self._free_blocks, self._released = {}, []      # DeviceBuffer's block cache: size class -> [address], and the not-yet-safe ones
+        self.memory = NumpyMemory(self)
 
     def close(self):
         if self.stream is not None:
@@ -445,8 +514,9 @@ class NumpyHost:
                        "sc_nonlinear_accumulate_f32")
         return accum, n_bins.value, n_obs.value
 
-    # ---- stage D through this host: pairwise spectral Granger, canonical coherence -------------------------------------
+    # ---- stage D through this host (the drivers of _stage_d.py on float32 records) ------------------------------------------------
     def _csm_records(self, time_series, expectation_type, multitaper_kwargs):
+        """(spectra geometry, CSM records as a DeviceArray, n_observations, kept axes) of a time series."""
         from .transforms import Multitaper
         if expectation_type not in EXPECTATION_AXES:
             raise ValueError(f"Invalid expectation_type '{expectation_type}'. Must be one of: "
@@ -455,19 +525,15 @@ class NumpyHost:
         if np.asarray(m.time_series).shape[2] > 256:      # (before anything is allocated on the device)
             raise ValueError(f"n_signals <= 256 through NumpyHost's functional interface (got {np.asarray(m.time_series).shape[2]}): "
                              "numpy_api.Connectivity (SC_HIP_HOST=numpy) tiles more signals into channel blocks")
-        planes = _lib.PLANE_CSM
         # (complex64 spectra, like Connectivity._csm_records of the PyTorch host: these consumers read every bin of the CSM once, at
         #  window lengths and channel counts where the planes format buys nothing)
         sp = self.spectra(m, planes_hint=None)
-        accum, n_bins, n_obs = self.accumulate(sp, expectation_type, planes)
-        for key in ("X", "P", "scale"):
-            if sp.get(key) is not None:
-                sp[key].free()
+        accum, n_bins, n_obs = self.accumulate(sp, expectation_type, _lib.PLANE_CSM)
+        sp.free()
         axes = EXPECTATION_AXES[expectation_type]
         kept = tuple(n for i, n in enumerate((sp["W"], sp["R"], sp["K"])) if i not in axes)
-        return m, sp, accum, n_bins, n_obs, kept
+        return sp, DeviceArray(accum, (n_bins, accum.n_bytes // (n_bins * 4)), np.float32), n_obs, kept
 
-    # ---- SURVEY 8(f) through this host: the full Wilson factor + the directed MVAR measures, global coherence ------------------
     MVAR_MEASURES = {"directed_transfer_function": _lib.MVAR_DTF, "directed_coherence": _lib.MVAR_DC,
                      "partial_directed_coherence": _lib.MVAR_PDC, "generalized_partial_directed_coherence": _lib.MVAR_GPDC,
                      "direct_directed_transfer_function": _lib.MVAR_DDTF}
@@ -481,106 +547,58 @@ class NumpyHost:
         unknown = [name for name in measures if name not in self.MVAR_MEASURES]
         if unknown:
             raise ValueError(f"unknown MVAR measures {unknown}; available: {sorted(self.MVAR_MEASURES)}")
-        if not 1 <= int(max_iterations) <= 1024:
-            raise ValueError("max_iterations must be in 1 ... 1024")
-        m, sp, accum, n_bins, n_obs, kept = self._csm_records(time_series, expectation_type, multitaper_kwargs)
-        lib, C, F, N = self.lib, sp["C"], sp["F"], sp["N"]
-        if C > lib.sc_mvar_max_signals():
-            accum.free()
-            raise ValueError(f"the full Wilson factorisation supports n_signals <= {lib.sc_mvar_max_signals()} (got {C})")
-        n_groups = n_bins // F
-        nbytes = ctypes.c_size_t()
-        _lib.check(lib.sc_mvar_workspace_bytes(n_groups, C, N, byref(nbytes)), "sc_mvar_workspace_bytes")
-        work = self.alloc(nbytes.value)
-        G = self.alloc(n_groups * N * C * C * 16)
-        n_iter, status = self.alloc(n_groups * 4), self.alloc(n_groups * 4)
-        summary = (ctypes.c_int32 * 3)(0, 0, 0)
-        _lib.check(lib.sc_mvar_factor_f64(accum.ptr, None, n_groups, F, N, C, _lib.PLANE_CSM, n_obs, tolerance, int(max_iterations),
-                                          work.ptr, nbytes.value, G.ptr, n_iter.ptr, status.ptr, summary, self.stream), "sc_mvar_factor_f64")
+        _stage_d.check_max_iterations(max_iterations)
+        sp, accum, n_obs, kept = self._csm_records(time_series, expectation_type, multitaper_kwargs)
+        C, F, N = sp["C"], sp["F"], sp["N"]
+        if C > self.lib.sc_mvar_max_signals():
+            raise ValueError(f"the full Wilson factorisation supports n_signals <= {self.lib.sc_mvar_max_signals()} (got {C})")
+        G, _, _, summary = _stage_d.mvar_factor(self.memory, accum.shape[0] // F, N, C, accum=accum, n_freq_accum=F,
+                                                planes=_lib.PLANE_CSM, n_obs=n_obs, tolerance=tolerance, max_iterations=max_iterations)
         self.last_wilson = dict(iterations=int(summary[0]), not_converged=int(summary[1]), cholesky_fallbacks=int(summary[2]))
-        out = {}
-        for name in measures:
-            dev = self.alloc(n_groups * F * C * C * 8)
-            _lib.check(lib.sc_mvar_measure_f64(G.ptr, n_groups, N, C, self.MVAR_MEASURES[name], dev.ptr, work.ptr, nbytes.value, self.stream),
-                       "sc_mvar_measure_f64")
-            out[name] = np.array(self.download(dev, kept + (F, C, C), np.float64))
-            dev.free()
-        for b in (work, G, n_iter, status, accum):
-            b.free()
-        return out
+        return {name: self.memory.download(_stage_d.mvar_measure(self.memory, G, self.MVAR_MEASURES[name])).reshape(kept + (F, C, C))
+                for name in measures}
 
     def global_coherence(self, time_series, max_rank=1, **multitaper_kwargs):
         """NumPy time series -> (values (n_time_windows, n_fft_samples, max_rank), vectors (n_time_windows, n_fft_samples, n_signals,
         max_rank)) like the reference's ``Connectivity.global_coherence`` (connectivity.py:822-895): the leading eigenpairs of the
         cross-spectral matrix of every (window, two-sided bin) (sc_global_coherence_f64); always over trials and tapers."""
-        m, sp, accum, n_bins, n_obs, kept = self._csm_records(time_series, "trials_tapers", multitaper_kwargs)
-        lib, C, F, N, W = self.lib, sp["C"], sp["F"], sp["N"], sp["W"]
+        sp, accum, n_obs, kept = self._csm_records(time_series, "trials_tapers", multitaper_kwargs)
+        C = sp["C"]
         max_rank = int(max_rank)
         if not 1 <= max_rank <= min(C, sp["R"] * sp["K"]):
-            accum.free()
             raise ValueError(f"max_rank must be between 1 and min(n_signals, n_trials * n_tapers) = {min(C, sp['R'] * sp['K'])}")
-        if C > lib.sc_global_coherence_max_signals():
-            accum.free()
-            raise ValueError(f"global_coherence supports n_signals <= {lib.sc_global_coherence_max_signals()}")
-        values, vectors = self.alloc(W * N * max_rank * 8), self.alloc(W * N * C * max_rank * 16)
-        _lib.check(lib.sc_global_coherence_f64(accum.ptr, W, F, N, C, _lib.PLANE_CSM, n_obs, max_rank, int(max_rank < C - 1), values.ptr,
-                                               vectors.ptr, self.stream), "sc_global_coherence_f64")
-        res = (np.array(self.download(values, (W, N, max_rank), np.float64)),
-               np.array(self.download(vectors, (W, N, C, max_rank), np.complex128)))
-        for b in (values, vectors, accum):
-            b.free()
-        return res
+        if C > self.lib.sc_global_coherence_max_signals():
+            raise ValueError(f"global_coherence supports n_signals <= {self.lib.sc_global_coherence_max_signals()}")
+        values, vectors = _stage_d.global_coherence(self.memory, accum, sp["W"], sp["F"], sp["N"], C, _lib.PLANE_CSM, n_obs, max_rank,
+                                                    ascending=max_rank < C - 1)
+        return self.memory.download(values), self.memory.download(vectors)
 
     def pairwise_spectral_granger_prediction(self, time_series, pairs=None, expectation_type="trials_tapers", tolerance=1e-8,
                                              max_iterations=60, **multitaper_kwargs):
         """NumPy time series -> the reference's ``Connectivity.pairwise_spectral_granger_prediction()`` (connectivity.py:
         1161-1213; out[..., i, j] = j -> i, NaN elsewhere) for all channel pairs or the listed ``pairs``: cross-spectral records
         on the device, batched 2 x 2 Wilson factorisations (sc_granger_pairwise_f64), one download."""
-        m, sp, accum, n_bins, n_obs, kept = self._csm_records(time_series, expectation_type, multitaper_kwargs)
-        lib, C, F, N = self.lib, sp["C"], sp["F"], sp["N"]
+        sp, accum, n_obs, kept = self._csm_records(time_series, expectation_type, multitaper_kwargs)
+        C, F, N = sp["C"], sp["F"], sp["N"]
         if pairs is None:
             pairs = [(i, j) for i in range(C) for j in range(i + 1, C)]
         pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
         if ((pairs < 0) | (pairs >= C)).any():
             raise IndexError("pair index outside the signals")
         pairs = pairs[pairs[:, 0] != pairs[:, 1]]
-        if not 1 <= int(max_iterations) <= 1024:
-            raise ValueError("max_iterations must be in 1 ... 1024")
-        n_groups = n_bins // F
-        out = self.alloc(n_groups * F * C * C * 8)
-        result_shape = kept + (F, C, C)
+        _stage_d.check_max_iterations(max_iterations)
         if len(pairs) == 0:
-            accum.free(); out.free()
-            return np.full(result_shape, np.nan)
-        per_pair = n_groups * N * 160                                   # workspace bytes per problem (sc_granger_workspace_bytes)
-        chunk = int(max(1, min(len(pairs), (8 << 30) // per_pair)))
-        nbytes = ctypes.c_size_t()
-        _lib.check(lib.sc_granger_workspace_bytes(n_groups, chunk, N, byref(nbytes)), "sc_granger_workspace_bytes")
-        work = self.alloc(nbytes.value)
-        not_converged = fallbacks = 0
-        for p0 in range(0, len(pairs), chunk):
-            n = min(chunk, len(pairs) - p0)
-            d_pairs = self.upload(pairs[p0:p0 + n])
-            it_c, st_c = self.alloc(n_groups * n * 4), self.alloc(n_groups * n * 4)
-            summary = (ctypes.c_int32 * 3)(0, 0, 0)
-            _lib.check(lib.sc_granger_pairwise_f64(accum.ptr, n_groups, F, N, C, _lib.PLANE_CSM, n_obs, d_pairs.ptr, n, tolerance,
-                                                   int(max_iterations), work.ptr, nbytes.value, _lib.GRANGER_KEEP_OUTPUT if p0 else 0,
-                                                   out.ptr, it_c.ptr, st_c.ptr, summary, self.stream), "sc_granger_pairwise_f64")
-            not_converged += summary[1]
-            fallbacks += summary[2]
-            for b in (d_pairs, it_c, st_c):
-                b.free()
-        res = np.array(self.download(out, result_shape, np.float64))
-        for b in (work, out, accum):
-            b.free()
-        self.last_wilson = dict(not_converged=int(not_converged), cholesky_fallbacks=int(fallbacks))
-        return res
+            return np.full(kept + (F, C, C), np.nan)
+        out, _, _, summary = _stage_d.granger_pairwise(self.memory, accum, accum.shape[0] // F, F, N, C, _lib.PLANE_CSM, n_obs, pairs,
+                                                       tolerance, max_iterations)
+        self.last_wilson = dict(not_converged=int(summary[1]), cholesky_fallbacks=int(summary[2]))
+        return self.memory.download(out).reshape(kept + (F, C, C))
 
     def canonical_coherence(self, time_series, group_labels, **multitaper_kwargs):
         """NumPy time series -> (array (n_time_windows, n_frequencies, n_groups, n_groups), sorted labels) like the reference's
         ``Connectivity.canonical_coherence(group_labels)`` (connectivity.py:745-820, 1953-2032; always over trials and tapers)."""
-        m, sp, accum, n_bins, n_obs, kept = self._csm_records(time_series, "trials_tapers", multitaper_kwargs)
-        lib, C, F = self.lib, sp["C"], sp["F"]
+        sp, accum, n_obs, kept = self._csm_records(time_series, "trials_tapers", multitaper_kwargs)
+        C, F, n_bins = sp["C"], sp["F"], accum.shape[0]
         group_labels = np.asarray(group_labels)
         if group_labels.shape != (C,):
             raise ValueError(f"group_labels needs one label per signal ({C}), got shape {group_labels.shape}")
@@ -591,27 +609,13 @@ class NumpyHost:
         res[:, np.arange(n_g), np.arange(n_g)] = np.nan
         # (a group with at least as many channels as observations spans the observation space: coherence 1 with every other group)
         small = [k for k, g in enumerate(groups) if len(g) < n_obs]
-        max_group = int(lib.sc_canonical_max_group())
+        max_group = int(self.lib.sc_canonical_max_group())
         if any(len(groups[k]) > max_group for k in small):
             raise ValueError(f"canonical_coherence: the whitening kernel takes up to {max_group} channels per group")
         if len(small) >= 2:
-            cmax = max(len(groups[k]) for k in small)
-            stride = 16 if cmax <= 16 else (32 if cmax <= 32 else 128)
-            members = np.full((len(small), stride), -1, dtype=np.int32)
-            for i, k in enumerate(small):
-                members[i, :len(groups[k])] = groups[k]
-            sizes = np.array([len(groups[k]) for k in small], dtype=np.int32)
-            d_members, d_sizes = self.upload(members), self.upload(sizes)
-            out, fail = self.alloc(n_bins * len(small) * len(small) * 8), self.alloc(4)
-            _lib.check(lib.sc_memset_zero(fail.ptr, 4, self.stream), "sc_memset_zero")
-            _lib.check(lib.sc_canonical_coherence_f64(accum.ptr, n_bins, C, _lib.PLANE_CSM, n_obs, d_members.ptr, d_sizes.ptr, len(small),
-                                                      int(cmax), out.ptr, fail.ptr, self.stream), "sc_canonical_coherence_f64")
-            sub = np.array(self.download(out, (n_bins, len(small), len(small)), np.float64))
-            self.last_canonical_failures = int(self.download(fail, (1,), np.int32)[0])
-            res[np.ix_(np.arange(n_bins), small, small)] = sub
-            for b in (d_members, d_sizes, out, fail):
-                b.free()
-        accum.free()
+            sub, self.last_canonical_failures = _stage_d.canonical_coherence(self.memory, accum, C, _lib.PLANE_CSM, n_obs,
+                                                                             [groups[k] for k in small])
+            res[np.ix_(np.arange(n_bins), small, small)] = self.memory.download(sub)
         return res.reshape(sp["W"], F, n_g, n_g), labels
 
     def _planes_expectation(self, m, expectation_type, planes):

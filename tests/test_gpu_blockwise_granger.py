@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import blockwise_granger_ref as bref
+import chunked_calls
 import conditional_granger_ref as cref
 from conftest import granger_close
 
@@ -24,7 +25,8 @@ pytestmark = pytest.mark.gpu
 SC_PRECISIONS = ("float32", "float32+planes", "dtype")
 SC_PRECISIONS_TESTS = ("test_two_blocks", "test_three_uneven_blocks_string_labels", "test_four_blocks_of_eight",
                        "test_large_pairs", "test_more_than_512_signals", "test_singletons_equal_pairwise_on_estimated_spectra",
-                       "test_invariance_on_device", "test_torch_free_host_gives_the_same_values")
+                       "test_invariance_on_device", "test_torch_free_host_gives_the_same_values", "test_block_pairs_in_chunks",
+                       "test_block_pairs_in_chunks_on_the_torch_free_host")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -237,3 +239,54 @@ print("numpy host OK")
         assert out.returncode == 0 and "numpy host OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
         other = np.load(op)
     np.testing.assert_allclose(other, got, rtol=1e-9, atol=1e-12, equal_nan=True)
+
+
+CHUNK_LABELS = np.array([0, 0, 1, 1, 2, 2, 3])          # groups of 2, 2, 2, 1: three pairs of m = 4 and three of m = 3
+
+
+def chunked_and_whole(S):
+    """The measure of ONE object with the default workspace bound and with the bound lowered to two block pairs per call, on
+    whichever host the process runs: the two results, the statuses of the chunked run and (pairs, m) of each
+    sc_blockwise_granger_f64 call it made.  The workspace of a pair grows with m, and no single bound gives two pairs per call at
+    both m = 3 and m = 4 (at 32 bins the queries are 50944 / 73984 bytes for two / three pairs of m = 3, 86784 for two of m = 4),
+    so _lib.CONDITIONAL_WORK_BYTES -- read when a batch is cut -- is lowered per batch, to the library's own query for two
+    pairs of that batch's m."""
+    from spectral_connectivity_amd import _lib
+    c = device(S)
+    whole, _ = c.blockwise_spectral_granger_prediction(CHUNK_LABELS)
+    lib, real_chunk = _lib._handle(), _lib.blockwise_chunk
+
+    def two_per_call(n_groups, n_pairs, workspace_bytes, cap=None):
+        _lib.CONDITIONAL_WORK_BYTES = workspace_bytes(2)
+        return real_chunk(n_groups, n_pairs, workspace_bytes, cap)
+
+    with chunked_calls.replaced(_lib, "CONDITIONAL_WORK_BYTES", _lib.CONDITIONAL_WORK_BYTES), \
+            chunked_calls.replaced(_lib, "blockwise_chunk", two_per_call), \
+            chunked_calls.spied(lib, "sc_blockwise_granger_f64", 11, 12) as calls:
+        chunked, _ = c.blockwise_spectral_granger_prediction(CHUNK_LABELS)
+    return dict(chunked=squeeze(chunked), whole=squeeze(whole), status=c._last_wilson["status"], calls=np.array(calls))
+
+
+def check_chunked(r, S, precision, host):
+    """Four calls across the two batches into one output: against the reference and against the unchunked run of the same
+    object, both within bounds(); statuses [6 pairs, 1 group]."""
+    assert r["calls"].tolist() == [[2, 3], [1, 3], [2, 4], [1, 4]], r["calls"]
+    assert r["status"].shape == (6, 1) and (r["status"] == 1).all()
+    print(f"blockwise Granger, {host} host, {precision}: chunked == unchunked bit for bit:",
+          np.array_equal(r["chunked"], r["whole"], equal_nan=True))
+    ref, _ = bref.blockwise_granger(S, CHUNK_LABELS)
+    assert_close(r["chunked"], ref, *bounds(precision), what="chunked vs reference")
+    assert_close(r["chunked"], r["whole"], *bounds(precision), what="chunked vs unchunked")
+
+
+def test_block_pairs_in_chunks(_engine_precision):
+    """Seven signals in groups of 2, 2, 2, 1 whose block pairs go two per call: BLOCKWISE_KEEP_OUTPUT across calls and batches and
+    the offsets of the member / split / cell lists and of n_iter / status, which the 4 GB default bound never exercises."""
+    S = cref.var_spectrum(*random_var(7, 22), 32)
+    check_chunked(chunked_and_whole(S), S, _engine_precision, "PyTorch")
+
+
+def test_block_pairs_in_chunks_on_the_torch_free_host(_engine_precision):
+    S = cref.var_spectrum(*random_var(7, 22), 32)
+    r = chunked_calls.on_torch_free_host("test_gpu_blockwise_granger", "chunked_and_whole", _engine_precision, S=S)
+    check_chunked(r, S, _engine_precision, "torch-free")

@@ -16,6 +16,7 @@ import sys
 import numpy as np
 import pytest
 
+import chunked_calls
 import conditional_granger_ref as cref
 from conftest import granger_close
 from oracle import spectral_oracle as so
@@ -214,3 +215,46 @@ print("numpy host OK")
         assert out.returncode == 0 and "numpy host OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
         other = squeeze(np.load(op))
     np.testing.assert_allclose(other, got, rtol=1e-9, atol=1e-12, equal_nan=True)
+
+
+def chunked_and_whole(S):
+    """The measure of ONE object with the default workspace bound and with _lib.CONDITIONAL_WORK_BYTES lowered to the library's own
+    workspace query for two dropped signals (_lib.conditional_chunk then returns 2), on whichever host the process runs: the two
+    results, the statuses of the chunked run and the dropped signals of each sc_conditional_granger_f64 call it made."""
+    import ctypes
+
+    from spectral_connectivity_amd import _lib
+    c = device(S)
+    whole = squeeze(c.conditional_spectral_granger_prediction())
+    lib = _lib._handle()
+    nbytes = ctypes.c_size_t()
+    _lib.check(lib.sc_conditional_granger_workspace_bytes(1, S.shape[-1], S.shape[0], 2, ctypes.byref(nbytes)),
+               "sc_conditional_granger_workspace_bytes")
+    with chunked_calls.replaced(_lib, "CONDITIONAL_WORK_BYTES", nbytes.value), \
+            chunked_calls.spied(lib, "sc_conditional_granger_f64", 10) as calls:
+        chunked = squeeze(c.conditional_spectral_granger_prediction())
+    return dict(chunked=chunked, whole=whole, status=c._last_wilson["status"], calls=np.array(calls))
+
+
+def check_chunked(r, S, precision, host):
+    """Three calls of 2, 2, 1 dropped signals into one output: against the reference and against the one-call run of the same
+    object, both within bounds(); statuses [5 dropped signals, 1 group], all converged."""
+    assert list(r["calls"]) == [2, 2, 1], r["calls"]
+    assert r["status"].shape == (5, 1) and (r["status"] == 1).all()
+    print(f"conditional Granger, {host} host, {precision}: chunked == one call bit for bit:",
+          np.array_equal(r["chunked"], r["whole"], equal_nan=True))
+    assert_close(r["chunked"], cref.conditional_granger_closed(S), *bounds(precision), what="chunked vs reference")
+    assert_close(r["chunked"], r["whole"], *bounds(precision), what="chunked vs one call")
+
+
+def test_dropped_signals_in_chunks(_engine_precision):
+    """Five signals whose dropped signals go in chunks of two: CONDITIONAL_KEEP_OUTPUT and the offsets of the dropped-signal list
+    and of n_iter / status, which the 4 GB default bound never exercises."""
+    S = cref.var_spectrum(*random_var(5, 15), 32)
+    check_chunked(chunked_and_whole(S), S, _engine_precision, "PyTorch")
+
+
+def test_dropped_signals_in_chunks_on_the_torch_free_host(_engine_precision):
+    S = cref.var_spectrum(*random_var(5, 15), 32)
+    r = chunked_calls.on_torch_free_host("test_gpu_conditional_granger", "chunked_and_whole", _engine_precision, S=S)
+    check_chunked(r, S, _engine_precision, "torch-free")

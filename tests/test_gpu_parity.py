@@ -7,6 +7,7 @@ an absolute error of 1e-5 of that scale (they are sums of O(scale) terms in fp32
 import numpy as np
 import pytest
 
+import chunked_calls
 from conftest import granger_close
 from oracle import spectral_oracle as so
 
@@ -25,6 +26,7 @@ SC_PRECISIONS_TESTS = {
     "test_nonfinite_sample_spoils_only_its_own_channel", "test_f13_canonical_coherence_with_fewer_observations_than_channels",
     "test_global_coherence_any_rank_beyond_64_signals", "test_global_coherence_degenerate_eigenvalues_and_the_jacobi_cross_check",
     "test_f14_complex_valued_time_series", "test_silent_and_constant_channels_give_exact_zero_spectra",
+    "test_granger_pairs_in_chunks", "test_granger_pairs_in_chunks_on_the_torch_free_host",
 }
 
 RTOL = 1e-5
@@ -365,6 +367,69 @@ def test_f5_granger_vs_reference(sc, golden, tag, kw):
     sub = c.subset_pairwise_spectral_granger_prediction([(0, 1)])
     np.testing.assert_allclose(sub[..., 0, 1], got[..., 0, 1], rtol=1e-12, equal_nan=True)
     np.testing.assert_allclose(sub[..., 1, 0], got[..., 1, 0], rtol=1e-12, equal_nan=True)
+
+
+CHUNK_PAIRS = [(0, 1), (0, 2), (0, 3), (1, 2), (2, 3)]          # five of the six pairs of four signals
+
+
+def chunk_series():
+    rng = np.random.default_rng(64)
+    x = rng.standard_normal((128 + 16, 6, 4))
+    for t in range(1, len(x)):
+        x[t] += 0.4 * x[t - 1]
+        x[t, :, 1:] += 0.35 * x[t - 1, :, :-1]
+    return x[16:]
+
+
+def granger_chunked_and_whole(x):
+    """The listed pairs of ONE object (two windows of 64 samples: n_groups = 2) in one library call and with
+    _lib.GRANGER_WORK_BYTES lowered to two pairs per call, on whichever host the process runs: the two results, n_iter / status of
+    both runs and the pairs of each sc_granger_pairwise_f64 call of the chunked one."""
+    import spectral_connectivity_amd as pkg
+    from spectral_connectivity_amd import _lib
+    N, n_groups, res = 64, 2, {}
+    c = pkg.Connectivity.from_multitaper(pkg.Multitaper(x, sampling_frequency=200.0, time_halfbandwidth_product=2,
+                                                        n_time_samples_per_window=N))
+    res["whole"] = c.subset_pairwise_spectral_granger_prediction(CHUNK_PAIRS)
+    res["whole_n_iter"], res["whole_status"] = c._last_wilson["n_iter"], c._last_wilson["status"]
+    with chunked_calls.replaced(_lib, "GRANGER_WORK_BYTES", 2 * n_groups * N * 160), \
+            chunked_calls.spied(_lib._handle(), "sc_granger_pairwise_f64", 8) as calls:
+        res["chunked"] = c.subset_pairwise_spectral_granger_prediction(CHUNK_PAIRS)
+    res["n_iter"], res["status"], res["calls"] = c._last_wilson["n_iter"], c._last_wilson["status"], np.array(calls)
+    return res
+
+
+def check_granger_chunked(r, x, precision, host):
+    """Calls of 2, 2, 1 pairs into one output: against the oracle on the listed pairs and against the one-call run of the same
+    object (the tolerance of test_granger_resident_kernel_equals_the_batched_kernels for the engine); n_iter / status are
+    [n_groups, n_pairs] whatever the chunking."""
+    assert list(r["calls"]) == [2, 2, 1], r["calls"]
+    for key in ("n_iter", "status"):
+        assert r[key].size == 2 * len(CHUNK_PAIRS)
+        assert np.array_equal(r[key].reshape(2, len(CHUNK_PAIRS)), r["whole_" + key].reshape(2, len(CHUNK_PAIRS))), key
+    print(f"pairwise Granger, {host} host, {precision}: chunked == one call bit for bit:",
+          np.array_equal(r["chunked"], r["whole"], equal_nan=True))
+    ref = so.pairwise_spectral_granger_prediction(so.multitaper_fft(x, fs=200.0, NW=2, n_time_samples_per_window=64)[0])
+    listed = np.zeros(ref.shape[-2:], dtype=bool)
+    for i, j in CHUNK_PAIRS:
+        listed[i, j] = listed[j, i] = True
+    ref = np.where(listed, ref, np.nan)
+    tol = 2e-5 if precision == "float32" else 1e-8
+    granger_close(r["chunked"], ref, tol, what="chunked vs the oracle")
+    granger_close(r["chunked"], r["whole"], tol, what="chunked vs one call")
+
+
+def test_granger_pairs_in_chunks(sc, _engine_precision):
+    """Five pairs, two windows, two pairs per call: GRANGER_KEEP_OUTPUT, the offset of the pair list and the [n_groups, n_pairs]
+    layout of n_iter / status over the chunks, which the 8 GB default bound never exercises."""
+    x = chunk_series()
+    check_granger_chunked(granger_chunked_and_whole(x), x, _engine_precision, "PyTorch")
+
+
+def test_granger_pairs_in_chunks_on_the_torch_free_host(sc, _engine_precision):
+    x = chunk_series()
+    r = chunked_calls.on_torch_free_host("test_gpu_parity", "granger_chunked_and_whole", _engine_precision, x=x)
+    check_granger_chunked(r, x, _engine_precision, "torch-free")
 
 
 def test_granger_from_uploaded_two_sided_coefficients(sc, golden):

@@ -376,3 +376,108 @@ def test_public_api_surface_matches_the_reference():
                 if mine != want:
                     problems.append(f"{module}.{name}: {mine} != {want}")
     assert not problems, "\\n".join(problems)
+
+
+@pytest.mark.parametrize("n_signals", [257, 300, 306, 384, 385, 512, 1024])
+def test_tile_plan_covers_the_full_record_once(n_signals):
+    """_lib.tile_plan (the channel-block tiling of more than 256 signals, both hosts): over all block pairs every tile of the full
+    record is written exactly once, and every (src, dst) names the same 16 x 16 channel tile -- recomputed here from the pair's
+    channel columns, not through the plan's own index arithmetic."""
+    from spectral_connectivity_amd import _lib
+    NB = -(-n_signals // 16)
+    written = []
+    for a, b, cols, src, dst in _lib.tile_plan(n_signals):
+        assert a < b and len(cols) <= 256 and len(src) == len(dst)
+        nb_s = -(-len(cols) // 16)
+        upper = [(ti, tj) for ti in range(nb_s) for tj in range(ti, nb_s)]          # tile index -> (row, column) of the pair's record
+        for s, d in zip(src, dst):
+            ti, tj = upper[s]
+            gi, gj = cols[16 * ti] // 16, cols[16 * tj] // 16
+            assert gi <= gj
+            assert d == sum(NB - r for r in range(gi)) + (gj - gi), (n_signals, a, b, s, d)
+        written += list(dst)
+    assert sorted(written) == list(range(NB * (NB + 1) // 2))
+
+
+def test_blockwise_granger_call_sequence(monkeypatch):
+    """_stage_d.blockwise_granger against a library stub that records its arguments, on plain NumPy memory: two batch sizes m of
+    three pairs each under a bound of two pairs per call -- calls of (2, 1, 2, 1) pairs, the output kept on every call but the
+    first, the list and n_iter / status pointers advanced per chunk, the summaries combined as max, sum, sum."""
+    import ctypes
+
+    from spectral_connectivity_amd import _lib, _stage_d
+
+    class Memory:
+        def empty(self, shape, dtype):
+            return np.empty(shape, dtype)
+
+        zeros = staticmethod(np.zeros)
+        upload = staticmethod(np.array)
+
+        def ptr(self, a, first_row=0):
+            return ctypes.c_void_p(a.ctypes.data + first_row * (a.strides[0] if a.ndim else 0))
+
+        def stream(self):
+            return None
+
+        def is_f64(self, record):
+            return record.dtype == np.float64
+
+        def fill_nan(self, a):
+            a.fill(np.nan)
+
+    class Library:
+        calls = []
+
+        @staticmethod
+        def sc_blockwise_granger_workspace_bytes(n_groups, m, n_fft, n, nbytes):
+            nbytes._obj.value = 1000 + 100 * n
+            return 0
+
+        @classmethod
+        def sc_blockwise_granger_f64(cls, accum, spectra, n_groups, n_freq, n_fft, n_signals, planes, n_obs, members, split, cell, n, m,
+                                     n_blocks, tolerance, max_iterations, work, nbytes, flags, out, n_iter, status, summary, stream):
+            cls.calls.append(dict(n=n, m=m, flags=flags, planes=planes, nbytes=nbytes, members=members.value, split=split.value,
+                                  cell=cell.value, out=out.value, n_iter=n_iter.value, status=status.value))
+            summary[0], summary[1], summary[2] = 10 * len(cls.calls), len(cls.calls), 2
+            return 0
+
+    monkeypatch.setattr(_lib, "_lib", Library)
+    monkeypatch.setattr(_lib, "CONDITIONAL_WORK_BYTES", 1000 + 100 * 2)
+    n_groups, held = 3, []
+    mem = Memory()
+    mem.upload = lambda a: held.append(np.array(a)) or held[-1]          # (the test reads the uploaded arrays' addresses)
+    mem.zeros = lambda shape, dtype: held.append(np.zeros(shape, dtype)) or held[-1]
+    batches = {m: (np.zeros((3, m), np.int32), np.zeros(3, np.int32), np.zeros((3, 2), np.int32)) for m in (3, 4)}
+    accum = np.zeros((n_groups * 5, 8), np.float64)
+    out, n_iter, status, summary = _stage_d.blockwise_granger(mem, n_groups, 8, 7, batches, 4, accum=accum, n_freq_accum=5,
+                                                              planes=_lib.PLANE_CSM, n_obs=9)
+    calls = Library.calls
+    assert [c["n"] for c in calls] == [2, 1, 2, 1] and [c["m"] for c in calls] == [3, 3, 4, 4]
+    assert [c["flags"] for c in calls] == [0] + [_lib.BLOCKWISE_KEEP_OUTPUT] * 3
+    assert all(c["planes"] == _lib.PLANE_CSM | _lib.RECORD_F64 and c["nbytes"] == 1200 and c["out"] == out.ctypes.data for c in calls)
+    d_n_iter, d_status = held[0], held[1]
+    assert n_iter is d_n_iter and status is d_status and n_iter.shape == (6, n_groups) and out.shape == (n_groups, 5, 4, 4)
+    for k, c in enumerate(calls):
+        members, split, cell = held[2 + 3 * (k // 2):5 + 3 * (k // 2)]
+        q0, row, m = 2 * (k % 2), 3 * (k // 2), c["m"]
+        assert c["members"] == members.ctypes.data + 4 * q0 * m
+        assert c["split"] == split.ctypes.data + 4 * q0
+        assert c["cell"] == cell.ctypes.data + 8 * q0
+        assert c["n_iter"] == d_n_iter.ctypes.data + 4 * (row + q0) * n_groups
+        assert c["status"] == d_status.ctypes.data + 4 * (row + q0) * n_groups
+    assert summary == (40, 1 + 2 + 3 + 4, 8)
+    # no batch at all (every pair rank deficient): no call, the output NaN-filled by the host
+    del calls[:]
+    out, n_iter, status, summary = _stage_d.blockwise_granger(mem, n_groups, 8, 7, {}, 4, accum=accum, n_freq_accum=5,
+                                                              planes=_lib.PLANE_CSM, n_obs=9)
+    assert not calls and np.isnan(out).all() and n_iter.shape == (0, n_groups) and summary == (0, 0, 0)
+
+
+def test_max_iterations_is_checked_by_every_stage_d_path():
+    from spectral_connectivity_amd import _stage_d, engine
+    assert engine.check_max_iterations is _stage_d.check_max_iterations
+    for bad in (0, 1025):
+        with pytest.raises(ValueError, match="max_iterations must be between 1 and 1024"):
+            _stage_d.check_max_iterations(bad)
+    assert _stage_d.check_max_iterations(60) == 60
