@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _lib
 
-MAX_WILSON_ITERATIONS = 1024      # iterations the device kernels can log (WILSON_HIST / MV_HIST in csrc)
+MAX_WILSON_ITERATIONS = 1024      # iterations the device kernels can log (WILSON_HIST in csrc/sc_wilson_loop.h)
 
 
 def check_max_iterations(max_iterations):

@@ -22,7 +22,6 @@
 #include <vector>
 #include "sc_common.h"
 
-typedef double2 cd;
 
 #define BW_LDS_BLOCK 64          // blocks of up to this many signals are factored in LDS by the epilogue, larger ones in place
 #define BW_LDS_NULLSPACE 64      // problems of up to this many signals keep Psi0 in LDS in bw_nullspace
@@ -177,10 +176,6 @@ __global__ void __launch_bounds__(256) bw_epilogue(cd* __restrict__ S2, const cd
     }
 }
 
-__global__ void bw_fill_nan(double* __restrict__ out, int64_t n) {
-    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k < n) out[k] = nan("");
-}
 
 // Workspace of one call with P = n_pairs G problems of m signals:
 //   S2 and Psi [P][N][m][m] (complex128); then either the factorisation's own workspace or, once it has returned,
@@ -246,10 +241,7 @@ extern "C" int sc_blockwise_granger_f64(const void* d_accum, const void* d_S, in
     char* tail = w;
     size_t mvar = 0;
     sc_mvar_workspace_bytes(P, m, N, &mvar);
-    if (!(flags & SC_BLOCKWISE_KEEP_OUTPUT)) {
-        const int64_t n = G * F * n_blocks * n_blocks;
-        hipLaunchKernelGGL(bw_fill_nan, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_out, n);
-    }
+    if (!(flags & SC_BLOCKWISE_KEEP_OUTPUT)) sc_internal_fill_nan(d_out, G * F * n_blocks * n_blocks, st);
     BwDims d = {};
     d.G = G; d.N = N; d.C = (int)C; d.m = (int)m;
     if (d_accum && (rc = sc_csm_view(planes, n_freq_accum, N, C, n_obs, &d.v)) != SC_OK) return rc;

@@ -22,35 +22,21 @@
 #include "sc_common.h"
 #include "sc_jacobi.h"
 
-typedef double2 cd;
-__device__ inline cd zmul(cd a, cd b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ inline cd zmulc(cd a, cd b) { return make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }  // a conj(b)
-
 struct CanonArgs {
     ScRec accum;
     const int32_t* members;   // [G][CMAX] channel indices, -1 padded
     const int32_t* sizes;     // [G]
     double* out;              // [n_bins][G][G]
     int32_t* fail;            // [1] count of non positive-definite group blocks
-    int64_t n_bins, floats_per_bin;
-    int G, n_gpairs, NB, n_tiles, p_csm;
+    ScCsmView v;              // the records (single bins: N = F = n_bins)
+    int64_t n_bins;
+    int G, n_gpairs;
     int mstride;              // row length of `members` for the workgroup-per-problem kernels (32 or CBIG_C)
     double jtol;
-    double n_obs;
     double* out_mim;          // interaction view: [n_bins][G][G] MIM (`out` then holds MIC)
 };
 
-__device__ inline cd csm_read(ScRec rec, const CanonArgs& a, int i, int j) {
-    int ti = i >> 4, tj = j >> 4, ii = i & 15, jj = j & 15;
-    const bool m = (ti > tj) || (ti == tj && ii > jj);
-    if (m) { int t = ti; ti = tj; tj = t; t = ii; ii = jj; jj = t; }
-    const int64_t off = ((int64_t)sc_tile_index(ti, tj, a.NB)) * SC_TILE_ELEMS + ii * 16 + jj;
-    const double re = (double)rec[(int64_t)a.p_csm * a.n_tiles * SC_TILE_ELEMS + off] / a.n_obs;
-    double im = (double)rec[(int64_t)(a.p_csm + 1) * a.n_tiles * SC_TILE_ELEMS + off] / a.n_obs;
-    if (m) im = -im;
-    if (i == j) im = 0.0;
-    return make_double2(re, im);
-}
+__device__ inline cd csm_read(ScRec rec, const CanonArgs& a, int i, int j) { return sc_csm_entry(rec, a.v, i, j); }
 
 // the records as the kernels read them: S (IM = false: canonical coherence) or the interaction view (IM = true) -- a group
 // block entry as (Re S_ij, 0), a cross block entry as (0, Im S_ij)
@@ -89,7 +75,7 @@ __device__ inline bool cholesky(cd (*L)[CMAX], int n) {
         L[j][j] = make_double2(ljj, 0.0);
         for (int i = j + 1; i < n; ++i) {
             cd s = L[i][j];
-            for (int k = 0; k < j; ++k) { const cd t = zmulc(L[i][k], L[j][k]); s.x -= t.x; s.y -= t.y; }
+            for (int k = 0; k < j; ++k) { const cd t = zmul_conj(L[i][k], L[j][k]); s.x -= t.x; s.y -= t.y; }
             L[i][j] = make_double2(s.x / ljj, s.y / ljj);
         }
     }
@@ -108,7 +94,7 @@ __global__ void __launch_bounds__(64) canonical_kernel(CanonArgs a) {
     const int na = a.sizes[ga], nb = a.sizes[gb];
     const int32_t* ma = a.members + ga * CMAX;
     const int32_t* mb = a.members + gb * CMAX;
-    const ScRec rec = a.accum + bin * a.floats_per_bin;
+    const ScRec rec = a.accum + bin * a.v.floats_per_bin;
 
     cd La[CMAX][CMAX], Lb[CMAX][CMAX], M[CMAX][CMAX];
     for (int i = 0; i < na; ++i)
@@ -131,7 +117,7 @@ __global__ void __launch_bounds__(64) canonical_kernel(CanonArgs a) {
     for (int i = 0; i < na; ++i)
         for (int j = 0; j < nb; ++j) {
             cd s = M[i][j];
-            for (int k = 0; k < j; ++k) { const cd t = zmulc(M[i][k], Lb[j][k]); s.x -= t.x; s.y -= t.y; }
+            for (int k = 0; k < j; ++k) { const cd t = zmul_conj(M[i][k], Lb[j][k]); s.x -= t.x; s.y -= t.y; }
             const double d = Lb[j][j].x;
             M[i][j] = make_double2(s.x / d, s.y / d);
         }
@@ -139,7 +125,7 @@ __global__ void __launch_bounds__(64) canonical_kernel(CanonArgs a) {
     for (int i = 0; i < na; ++i)
         for (int j = 0; j <= i; ++j) {
             cd s = make_double2(0.0, 0.0);
-            for (int k = 0; k < nb; ++k) { const cd t = zmulc(M[i][k], M[j][k]); s.x += t.x; s.y += t.y; }
+            for (int k = 0; k < nb; ++k) { const cd t = zmul_conj(M[i][k], M[j][k]); s.x += t.x; s.y += t.y; }
             La[i][j] = s;
             La[j][i] = make_double2(s.x, -s.y);
         }
@@ -229,7 +215,7 @@ __global__ void __launch_bounds__(64 * CB_WAVES) canonical_factor_kernel(CanonAr
     cd* Ls = reinterpret_cast<cd*>(cb_smem);                                   // [wave][16][16]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int64_t bin = blockIdx.x;
-    const ScRec rec = a.accum + bin * a.floats_per_bin;
+    const ScRec rec = a.accum + bin * a.v.floats_per_bin;
 
     // phase 1: L_g for every group (a wave per group, left-looking Cholesky, a lane per row)
     for (int g = wave; g < G; g += CB_WAVES) {
@@ -251,7 +237,7 @@ __global__ void __launch_bounds__(64 * CB_WAVES) canonical_factor_kernel(CanonAr
             cd s = make_double2(0.0, 0.0);
             if (i < n) {
                 s = L[i * CB_C + j];
-                for (int k = 0; k < j; ++k) { const cd t = zmulc(L[i * CB_C + k], L[j * CB_C + k]); s.x -= t.x; s.y -= t.y; }
+                for (int k = 0; k < j; ++k) { const cd t = zmul_conj(L[i * CB_C + k], L[j * CB_C + k]); s.x -= t.x; s.y -= t.y; }
             }
             CB_WSYNC();
             if (lane == 0) L[j * CB_C + j] = make_double2(ljj, 0.0);
@@ -299,7 +285,7 @@ __global__ void __launch_bounds__(64 * CB_WAVES) canonical_pair_kernel(CanonArgs
     const int n_chunks = (a.n_gpairs + CB_WAVES - 1) / CB_WAVES;
     const int64_t bin = blockIdx.x / n_chunks;
     const int chunk = blockIdx.x % n_chunks;
-    const ScRec rec = a.accum + bin * a.floats_per_bin;
+    const ScRec rec = a.accum + bin * a.v.floats_per_bin;
     const cd* Ls = Lg + (size_t)bin * G * CB_C * CB_C;
     const int* okg = okb + bin * G;
     cd* M = scratch + (size_t)wave * 2 * CB_C * CB_C;
@@ -343,7 +329,7 @@ __global__ void __launch_bounds__(64 * CB_WAVES) canonical_pair_kernel(CanonArgs
             for (int k = 0; k < CB_C; ++k) lb[k] = Lb[j * CB_C + k];
             cd sv = make_double2(0.0, 0.0);
 #pragma unroll
-            for (int k = 0; k < CB_C; ++k) { const cd t = zmulc(B[i * CB_C + k], lb[k]); sv.x += t.x; sv.y += t.y; }
+            for (int k = 0; k < CB_C; ++k) { const cd t = zmul_conj(B[i * CB_C + k], lb[k]); sv.x += t.x; sv.y += t.y; }
             M[e] = sv;
         }
         CB_WSYNC();
@@ -352,7 +338,7 @@ __global__ void __launch_bounds__(64 * CB_WAVES) canonical_pair_kernel(CanonArgs
             cd sv = make_double2(0.0, 0.0);
             if (i < na && j < na) {
 #pragma unroll
-                for (int k = 0; k < CB_C; ++k) { const cd t = zmulc(M[i * CB_C + k], M[j * CB_C + k]); sv.x += t.x; sv.y += t.y; }
+                for (int k = 0; k < CB_C; ++k) { const cd t = zmul_conj(M[i * CB_C + k], M[j * CB_C + k]); sv.x += t.x; sv.y += t.y; }
                 if (i == j) sv.y = 0.0;
             }
             B[e] = sv;
@@ -525,7 +511,7 @@ __device__ double cb_top_eigenvalue(cd (&a)[4], cd* vb, int lane) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const cd wc = vb[16 + 4 * jq + c];
-            const cd u0 = zmulc(vi, wc), u1 = zmulc(w, vc[c]);
+            const cd u0 = zmul_conj(vi, wc), u1 = zmul_conj(w, vc[c]);
             a[c].x -= u0.x + u1.x;
             a[c].y -= u0.y + u1.y;
         }
@@ -579,7 +565,7 @@ __global__ void __launch_bounds__(64 * CB_WAVES) canonical_pair_hh_kernel(CanonA
     const int n_chunks = (a.n_gpairs + CB_WAVES - 1) / CB_WAVES;
     const int64_t bin = blockIdx.x / n_chunks;
     const int chunk = blockIdx.x % n_chunks;
-    const ScRec rec = a.accum + bin * a.floats_per_bin;
+    const ScRec rec = a.accum + bin * a.v.floats_per_bin;
     const cd* Ls = Lg + (size_t)bin * G * CB_C * CB_C;
     const int* okg = okb + bin * G;
     cd* M = scratch + (size_t)wave * (2 * CB_C * CB_C + 32);
@@ -620,7 +606,7 @@ __global__ void __launch_bounds__(64 * CB_WAVES) canonical_pair_hh_kernel(CanonA
         for (int k = 0; k < CB_C; ++k) lb[k] = Lb[j * CB_C + k];
         cd sv = make_double2(0.0, 0.0);
 #pragma unroll
-        for (int k = 0; k < CB_C; ++k) { const cd t = zmulc(T[i * CB_C + k], lb[k]); sv.x += t.x; sv.y += t.y; }
+        for (int k = 0; k < CB_C; ++k) { const cd t = zmul_conj(T[i * CB_C + k], lb[k]); sv.x += t.x; sv.y += t.y; }
         M[e] = sv;
     }
     CB_WSYNC();
@@ -634,7 +620,7 @@ __global__ void __launch_bounds__(64 * CB_WAVES) canonical_pair_hh_kernel(CanonA
             cd sv = make_double2(0.0, 0.0);
             if (i < na && j < na) {
 #pragma unroll
-                for (int k = 0; k < CB_C; ++k) { const cd t = zmulc(M[i * CB_C + k], M[j * CB_C + k]); sv.x += t.x; sv.y += t.y; }
+                for (int k = 0; k < CB_C; ++k) { const cd t = zmul_conj(M[i * CB_C + k], M[j * CB_C + k]); sv.x += t.x; sv.y += t.y; }
                 if (i == j) sv.y = 0.0;
             }
             breg[c] = sv;
@@ -661,11 +647,6 @@ __global__ void __launch_bounds__(64 * CB_WAVES) canonical_pair_hh_kernel(CanonA
     }
 }
 
-__global__ void canon_fill_nan(double* out, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < total) out[i] = nan("");
-}
-
 // ---- groups of 33 ... 128 channels: a workgroup per (bin, group pair) -------------------------------------------------
 // Three C x C matrices per problem no longer fit a lane's scratch (or the LDS): the group blocks S_aa, S_bb and the cross
 // block S_ab of a problem live in a per-workgroup global scratch (L2-resident: 3 x 256 KB at 128 channels), factored and
@@ -675,38 +656,6 @@ __global__ void canon_fill_nan(double* out, int64_t total) {
 // is the squared canonical coherence.  Persistent workgroups (one per CU) walk the (bin, pair) list.
 #define CBIG_C 128
 #define CBIG_SWEEPS 14
-
-// in-place lower Cholesky of the n x n Hermitian matrix L (row-major, stride CBIG_C, lower triangle valid), all 256 threads
-__device__ inline bool cbig_cholesky(cd* L, int n, int* bad) {
-    const int tid = threadIdx.x;
-    for (int k = 0; k < n; ++k) {
-        if (tid == 0) {
-            const double d = L[k * CBIG_C + k].x;
-            if (!(d > 0.0)) *bad = 1;
-            L[k * CBIG_C + k] = make_double2(sqrt(d > 0.0 ? d : 1.0), 0.0);
-        }
-        __syncthreads();
-        const double dk = L[k * CBIG_C + k].x;
-        for (int i = k + 1 + tid; i < n; i += 256) {
-            const cd v = L[i * CBIG_C + k];
-            L[i * CBIG_C + k] = make_double2(v.x / dk, v.y / dk);
-        }
-        __syncthreads();
-        // trailing update of the lower triangle: L[i][j] -= L[i][k] conj(L[j][k]), k < j <= i
-        const int m = n - k - 1;
-        for (int e = tid; e < m * m; e += 256) {
-            const int i = k + 1 + e / m, j = k + 1 + e % m;
-            if (j <= i) {
-                const cd t = zmulc(L[i * CBIG_C + k], L[j * CBIG_C + k]);
-                cd v = L[i * CBIG_C + j];
-                v.x -= t.x; v.y -= t.y;
-                L[i * CBIG_C + j] = v;
-            }
-        }
-        __syncthreads();
-    }
-    return *bad == 0;
-}
 
 __global__ void __launch_bounds__(256) canonical_big_kernel(CanonArgs a, cd* scratch, int64_t n_items) {
     extern __shared__ __align__(16) unsigned char cb_smem[];
@@ -736,14 +685,14 @@ __global__ void __launch_bounds__(256) canonical_big_kernel(CanonArgs a, cd* scr
         const int na = a.sizes[ga], nb = a.sizes[gb];
         const int32_t* ma = a.members + ga * a.mstride;
         const int32_t* mb = a.members + gb * a.mstride;
-        const ScRec rec = a.accum + bin * a.floats_per_bin;
+        const ScRec rec = a.accum + bin * a.v.floats_per_bin;
         if (tid == 0) bad = 0;
         for (int e = tid; e < na * na; e += 256) { const int i = e / na, j = e % na; if (j <= i) La[i * CBIG_C + j] = csm_read(rec, a, ma[i], ma[j]); }
         for (int e = tid; e < nb * nb; e += 256) { const int i = e / nb, j = e % nb; if (j <= i) Lb[i * CBIG_C + j] = csm_read(rec, a, mb[i], mb[j]); }
         for (int e = tid; e < na * nb; e += 256) { const int i = e / nb, j = e % nb; M[i * CBIG_C + j] = csm_read(rec, a, ma[i], mb[j]); }
         __syncthreads();
-        cbig_cholesky(La, na, &bad);
-        cbig_cholesky(Lb, nb, &bad);
+        sc_wg_cholesky(La, CBIG_C, na, &bad);
+        sc_wg_cholesky(Lb, CBIG_C, nb, &bad);
         // M <- La^-1 M: thread j owns column j (forward substitution down the rows)
         for (int j = tid; j < nb; j += 256)
             for (int i = 0; i < na; ++i) {
@@ -757,7 +706,7 @@ __global__ void __launch_bounds__(256) canonical_big_kernel(CanonArgs a, cd* scr
         for (int i = tid; i < na; i += 256)
             for (int j = 0; j < nb; ++j) {
                 cd sacc = M[i * CBIG_C + j];
-                for (int k = 0; k < j; ++k) { const cd t = zmulc(M[i * CBIG_C + k], Lb[j * CBIG_C + k]); sacc.x -= t.x; sacc.y -= t.y; }
+                for (int k = 0; k < j; ++k) { const cd t = zmul_conj(M[i * CBIG_C + k], Lb[j * CBIG_C + k]); sacc.x -= t.x; sacc.y -= t.y; }
                 const double d = Lb[j * CBIG_C + j].x;
                 M[i * CBIG_C + j] = make_double2(sacc.x / d, sacc.y / d);
             }
@@ -767,7 +716,7 @@ __global__ void __launch_bounds__(256) canonical_big_kernel(CanonArgs a, cd* scr
             const int i = e / na, j = e % na;
             if (i > j) continue;
             cd sacc = make_double2(0.0, 0.0);
-            for (int k = 0; k < nb; ++k) { const cd t = zmulc(M[i * CBIG_C + k], M[j * CBIG_C + k]); sacc.x += t.x; sacc.y += t.y; }
+            for (int k = 0; k < nb; ++k) { const cd t = zmul_conj(M[i * CBIG_C + k], M[j * CBIG_C + k]); sacc.x += t.x; sacc.y += t.y; }
             if (i == j) sacc.y = 0.0;
             B[gc_tri(i, j, na)] = sacc;
         }
@@ -833,7 +782,7 @@ __global__ void __launch_bounds__(256) canonical_big_hh_kernel(CanonArgs a, cd* 
         const int na = a.sizes[ga], nb = a.sizes[gb];
         const int32_t* ma = a.members + ga * a.mstride;
         const int32_t* mb = a.members + gb * a.mstride;
-        const ScRec rec = a.accum + bin * a.floats_per_bin;
+        const ScRec rec = a.accum + bin * a.v.floats_per_bin;
         // Pairs of groups of at most CBH_SMALL channels stay in LDS from the records to lambda_max: one factor block at a time (L_b takes
         // L_a's place once M is multiplied by L_a^-1, B takes L_b's) beside M; larger pairs keep the three blocks in the global scratch.
         // (small_n: CBH_SMALL, or the largest group when no group is larger -- the launch then asks for 2 small_n small_ld elements of LDS
@@ -874,7 +823,7 @@ __global__ void __launch_bounds__(256) canonical_big_hh_kernel(CanonArgs a, cd* 
             const int cols = nb - k - 1;
             for (int e = tid; e < na * cols; e += 256) {
                 const int i = e / cols, j = k + 1 + e % cols;
-                const cd t = zmulc(PM[i * ld + k], PB[j * ld + k]);
+                const cd t = zmul_conj(PM[i * ld + k], PB[j * ld + k]);
                 cd v = PM[i * ld + j];
                 v.x -= t.x; v.y -= t.y;
                 PM[i * ld + j] = v;
@@ -886,7 +835,7 @@ __global__ void __launch_bounds__(256) canonical_big_hh_kernel(CanonArgs a, cd* 
         for (int e = tid; e < na * na; e += 256) {
             const int i = e % na, j = e / na;
             cd sacc = make_double2(0.0, 0.0);
-            for (int k = 0; k < nb; ++k) { const cd t = zmulc(PM[i * ld + k], PM[j * ld + k]); sacc.x += t.x; sacc.y += t.y; }
+            for (int k = 0; k < nb; ++k) { const cd t = zmul_conj(PM[i * ld + k], PM[j * ld + k]); sacc.x += t.x; sacc.y += t.y; }
             if (i == j) sacc.y = 0.0;
             B[(size_t)j * na + i] = sacc;
         }
@@ -1015,28 +964,23 @@ template <bool IM>
 static int canonical_launch(const char* what, const void* d_accum, int64_t n_bins, int64_t n_signals, uint32_t planes,
                             int64_t n_observations, const int32_t* d_members, const int32_t* d_sizes, int n_groups,
                             int max_group_size, double* d_out, double* d_out_mim, int32_t* d_fail, void* stream) {
-    SC_REQUIRE(planes & SC_PLANE_CSM, "accumulator record must contain SC_PLANE_CSM");
+    CanonArgs a;
+    const int rcv = sc_csm_view(planes, n_bins, n_bins, n_signals, n_observations, &a.v);
+    if (rcv != SC_OK) return rcv;
     SC_REQUIRE(n_groups >= 1 && n_bins >= 1, "empty problem");
     if (max_group_size > CBIG_C) {
         sc_set_error("%s supports groups of at most %d channels (got %d)", what, CBIG_C, max_group_size);
         return SC_EUNSUPPORTED;
     }
     hipStream_t st = (hipStream_t)stream;
-    CanonArgs a;
     a.accum = sc_rec(d_accum, planes); a.members = d_members; a.sizes = d_sizes; a.out = d_out; a.fail = d_fail;
     a.out_mim = d_out_mim;
     a.n_bins = n_bins; a.G = n_groups; a.n_gpairs = n_groups * (n_groups - 1) / 2;
-    a.NB = sc_n_blocks(n_signals); a.n_tiles = sc_n_tiles(a.NB);
-    a.floats_per_bin = (int64_t)sc_plane_count(planes) * a.n_tiles * SC_TILE_ELEMS;
-    a.p_csm = sc_plane_offset(planes, SC_PLANE_CSM);
-    a.n_obs = (double)n_observations;
     a.mstride = max_group_size <= 32 ? 32 : CBIG_C;      // (the member table's row length is the caller's: sc_hip.h)
     a.jtol = 1e-24;          // off^2 <= jtol dia^2: eigenvalues to ~1e-12 relative (quadratic convergence)
     const int64_t total_out = n_bins * n_groups * n_groups;
-    hipLaunchKernelGGL(canon_fill_nan, dim3((unsigned)((total_out + 255) / 256)), dim3(256), 0, st, d_out, total_out);
-    if (IM) {
-        hipLaunchKernelGGL(canon_fill_nan, dim3((unsigned)((total_out + 255) / 256)), dim3(256), 0, st, d_out_mim, total_out);
-    }
+    sc_internal_fill_nan(d_out, total_out, st);
+    if (IM) sc_internal_fill_nan(d_out_mim, total_out, st);
     (void)hipMemsetAsync(d_fail, 0, 4, st);
     const int64_t threads = n_bins * a.n_gpairs;
     // (SC_CANON_EIG=jacobi: the parallel Jacobi kernels of rounds 1-4, every eigenvalue of B -- canonical coherence only, A/B and

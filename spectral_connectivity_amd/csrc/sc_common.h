@@ -4,8 +4,11 @@
 #include <stdint.h>
 #include <stdio.h>
 #include "../../include/sc_hip.h"
+#include "sc_complex.h"
 
 void sc_set_error(const char* fmt, ...);
+struct ScRec;         // (accumulator records and their CSM view: below)
+struct ScCsmView;
 
 // Diagnostic switches (ablation / A-B tools, tests of alternative kernels): environment variables read ONCE when the library is
 // loaded and again whenever the host calls sc_debug_reload_env() -- no getenv on a launch path.  sc_switch(id) is the value
@@ -52,10 +55,19 @@ int sc_internal_causal_fft_pair(void* d_A, const int32_t* d_status, int64_t n_pr
 
 // sc_wilson_pair.hip: pairwise Granger with the 2 x 2 Wilson iteration of a pair resident on one compute unit
 bool sc_internal_granger_resident_applies(int64_t n_freq_accum, int64_t N);
-int sc_internal_granger_resident(const void* d_accum, int64_t n_groups, int64_t N, int64_t C, uint32_t planes, int64_t n_obs,
+int sc_internal_granger_resident(const void* d_accum, int64_t n_groups, const ScCsmView& v, int64_t C, uint32_t planes,
                                  const int32_t* d_pairs, int64_t n_pairs, double tol, int max_iter, void* d_work, size_t work_bytes,
                                  int keep_output, double* d_out, int32_t* d_n_iter, int32_t* d_status, int32_t* h_summary,
                                  hipStream_t st);
+
+// sc_memory.hip: d_out[0 .. n) = NaN (the default of every stage-D output that is not KEEP_OUTPUT)
+void sc_internal_fill_nan(double* d_out, int64_t n, hipStream_t st);
+
+// sc_wilson.hip: the epilogue of pairwise Granger on factors G [P][4][g_stride] (lam, Hinv, rot per pair from d_h0 [P][4], then the
+// prediction on the bins f <= N/2 into d_out); queued on st, not synchronised.  d_hinv, d_rot: [P][4] scratch.
+void sc_internal_granger_epilogue(const void* d_G, int64_t g_stride, const double* d_h0, double* d_hinv, double* d_rot,
+                                  ScRec accum, const ScCsmView& v, const int32_t* d_pairs, int64_t n_groups,
+                                  int64_t n_pairs, int64_t C, double* d_out, hipStream_t st);
 
 // sc_mvar.hip: the explicit inverse and the matrix-core product of the full Wilson factorisation on caller buffers
 // (natural-layout C x C complex128 matrices; see there)
@@ -137,9 +149,9 @@ __host__ __device__ inline int sc_tile_index(int bi, int bj, int nb) {
     return bi * nb - bi * (bi - 1) / 2 + (bj - bi);
 }
 
-// CSM records as the consumers of a C x C two-sided spectrum read them (sc_conditional.hip, sc_blockwise.hip): F = N or N/2+1
-// bins per group (N/2+1: real input, S(-f) = conj S(f) completes the bins past N/2), upper-triangular 16 x 16 tiles of
-// un-normalised sums divided by n_obs.  sc_csm_view: from the arguments of an entry point (d_accum non-NULL).
+// CSM records as every stage-D consumer reads them: F = N or N/2+1 bins per group (N/2+1: real input, S(-f) = conj S(f)
+// completes the bins past N/2), upper-triangular 16 x 16 tiles of un-normalised sums divided by n_obs.  sc_csm_view: from the
+// arguments of an entry point (d_accum non-NULL); consumers of single bins (sc_canonical.hip) pass N = F = their bin count.
 struct ScCsmView {
     int64_t N, F, floats_per_bin;
     int NB, n_tiles, p_csm, two_sided;
@@ -157,12 +169,9 @@ inline int sc_csm_view(uint32_t planes, int64_t n_freq_accum, int64_t N, int64_t
     v->n_obs = (double)n_obs;
     return SC_OK;
 }
-// S_g(n)[i][j] (two-sided bin n of group g)
-__device__ inline double2 sc_csm_two_sided(ScRec accum, const ScCsmView& v, int64_t g, int64_t n, int i, int j) {
-    int64_t bin = n;
-    bool conj = false;
-    if (!v.two_sided && n > v.N / 2) { bin = v.N - n; conj = true; }
-    const ScRec rec = accum + (g * v.F + bin) * v.floats_per_bin;
+// Hermitian entry (i, j) of the bin record `rec` (conj: of its complex conjugate, the record of the mirrored bin): the stored
+// upper triangle mirrored, the diagonal exactly real
+__device__ inline double2 sc_csm_entry(ScRec rec, const ScCsmView& v, int i, int j, bool conj = false) {
     int ti = i >> 4, tj = j >> 4, ii = i & 15, jj = j & 15;
     const bool m = (ti > tj) || (ti == tj && ii > jj);
     if (m) { int t = ti; ti = tj; tj = t; t = ii; ii = jj; jj = t; }
@@ -173,6 +182,29 @@ __device__ inline double2 sc_csm_two_sided(ScRec accum, const ScCsmView& v, int6
     if (conj) im = -im;
     if (i == j) im = 0.0;
     return make_double2(re, im);
+}
+// the record of accumulated bin `bin` of group g
+__device__ inline ScRec sc_csm_record(ScRec accum, const ScCsmView& v, int64_t g, int64_t bin) {
+    return accum + (g * v.F + bin) * v.floats_per_bin;
+}
+// S_g(n)[i][j] (two-sided bin n of group g)
+__device__ inline double2 sc_csm_two_sided(ScRec accum, const ScCsmView& v, int64_t g, int64_t n, int i, int j) {
+    int64_t bin = n;
+    bool conj = false;
+    if (!v.two_sided && n > v.N / 2) { bin = v.N - n; conj = true; }   // real input: S(-f) = conj S(f)
+    return sc_csm_entry(sc_csm_record(accum, v, g, bin), v, i, j, conj);
+}
+
+// Lower Cholesky factor [[l00, 0], [l10, l11]] of the 2 x 2 lag-0 covariance [[r00, r01], [r01, r11]] of a pairwise Wilson problem;
+// a covariance that is not positive definite gives the identity and (flag non-NULL) flags its batch: see k_init in sc_wilson.hip.
+__device__ __forceinline__ void sc_lag0_cholesky2(double r00, double r11, double r01, double& l00, double& l10, double& l11,
+                                                  int32_t* flag) {
+    l00 = sqrt(r00); l10 = r01 / l00;
+    const double t = r11 - l10 * l10;
+    l11 = sqrt(t);
+    const bool bad = !(r00 > 0.0) || !(t > 0.0);
+    if (bad) { l00 = 1.0; l10 = 0.0; l11 = 1.0; }
+    if (bad && flag) atomicOr(flag, 1);
 }
 
 // Workgroup-wide helpers of 256-thread kernels (sc_canonical.hip, sc_blockwise.hip).

@@ -21,7 +21,6 @@
 #include <math.h>
 #include "sc_common.h"
 
-typedef double2 cd;
 
 struct CgDims {
     int64_t G, N;        // groups, two-sided length
@@ -112,10 +111,6 @@ __global__ void __launch_bounds__(256) cg_epilogue(const cd* __restrict__ K, con
     }
 }
 
-__global__ void cg_fill_nan(double* __restrict__ out, int64_t n) {
-    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k < n) out[k] = nan("");
-}
 
 // Workspace of one call with D dropped signals:
 //   fixed  Psi0^T [G][C][C] and M [G][F][C][C] (complex128), one double 0 (the Tikhonov term of the small inverse)
@@ -168,10 +163,7 @@ extern "C" int sc_conditional_granger_f64(const void* d_accum, const void* d_S, 
     char* tail = w;
     size_t mvar = 0;
     sc_mvar_workspace_bytes(P, Cr, N, &mvar);
-    if (!(flags & SC_CONDITIONAL_KEEP_OUTPUT)) {
-        const int64_t n = G * F * E;
-        hipLaunchKernelGGL(cg_fill_nan, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_out, n);
-    }
+    if (!(flags & SC_CONDITIONAL_KEEP_OUTPUT)) sc_internal_fill_nan(d_out, G * F * E, st);
     SC_CHECK_HIP(hipMemsetAsync(zero, 0, 256, st));
     // reduced spectra
     CgDims d = {};

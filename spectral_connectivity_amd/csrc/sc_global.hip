@@ -13,7 +13,6 @@
 #include "sc_common.h"
 #include "sc_jacobi.h"
 
-typedef double2 cd;
 
 #define GC_CMAX 64
 #define GC_EIGH_MIN 32       // beyond: Householder + bisection + inverse iteration (global_coherence_eigh_kernel)
@@ -22,9 +21,8 @@ struct GcArgs {
     ScRec accum;
     double* values;        // [P][N][max_rank]
     cd* vectors;           // [P][N][C][max_rank]
-    int64_t N, F, floats_per_bin;
-    int C, NB, n_tiles, p_csm, two_sided, max_rank, ascending;
-    double n_obs;
+    ScCsmView v;           // the records: N two-sided bins per group from F = N or N/2+1 accumulated ones
+    int C, max_rank, ascending;
 };
 
 __global__ void __launch_bounds__(256) global_coherence_kernel(GcArgs a) {
@@ -41,22 +39,9 @@ __global__ void __launch_bounds__(256) global_coherence_kernel(GcArgs a) {
     __shared__ int done;
     const int tid = threadIdx.x;
     const int64_t n = blockIdx.x, p = blockIdx.y;
-    int64_t bin = n;
-    bool conj = false;
-    if (!a.two_sided && n > a.N / 2) { bin = a.N - n; conj = true; }   // real input: S(-f) = conj S(f)
-    const ScRec rec = a.accum + (p * a.F + bin) * a.floats_per_bin;
     for (int e = tid; e < C * C; e += 256) {
         const int i = e / C, j = e % C;
-        int ti = i >> 4, tj = j >> 4, ii = i & 15, jj = j & 15;
-        const bool m = (ti > tj) || (ti == tj && ii > jj);
-        if (m) { int t = ti; ti = tj; tj = t; t = ii; ii = jj; jj = t; }
-        const int64_t off = (int64_t)sc_tile_index(ti, tj, a.NB) * SC_TILE_ELEMS + ii * 16 + jj;
-        const double re = (double)rec[(int64_t)a.p_csm * a.n_tiles * SC_TILE_ELEMS + off] / a.n_obs;
-        double im = (double)rec[(int64_t)(a.p_csm + 1) * a.n_tiles * SC_TILE_ELEMS + off] / a.n_obs;
-        if (m) im = -im;
-        if (conj) im = -im;
-        if (i == j) im = 0.0;
-        A[e] = make_double2(re, im);
+        A[e] = sc_csm_two_sided(a.accum, a.v, p, n, i, j);
         V[e] = make_double2(i == j ? 1.0 : 0.0, 0.0);
     }
     __syncthreads();
@@ -111,13 +96,13 @@ __global__ void __launch_bounds__(256) global_coherence_kernel(GcArgs a) {
                 const cd se = rs[pr], sec = make_double2(se.x, -se.y);
                 {
                     const cd cp = A[k * C + pi], cq = A[k * C + qi];
-                    const cd t1 = g_mul(sec, cq), t2 = g_mul(se, cp);
+                    const cd t1 = zmul(sec, cq), t2 = zmul(se, cp);
                     A[k * C + pi] = make_double2(c * cp.x - t1.x, c * cp.y - t1.y);
                     A[k * C + qi] = make_double2(t2.x + c * cq.x, t2.y + c * cq.y);
                 }
                 {
                     const cd cp = V[k * C + pi], cq = V[k * C + qi];
-                    const cd t1 = g_mul(sec, cq), t2 = g_mul(se, cp);
+                    const cd t1 = zmul(sec, cq), t2 = zmul(se, cp);
                     V[k * C + pi] = make_double2(c * cp.x - t1.x, c * cp.y - t1.y);
                     V[k * C + qi] = make_double2(t2.x + c * cq.x, t2.y + c * cq.y);
                 }
@@ -131,7 +116,7 @@ __global__ void __launch_bounds__(256) global_coherence_kernel(GcArgs a) {
                 const double c = rc[pr];
                 const cd se = rs[pr], sec = make_double2(se.x, -se.y);
                 const cd r1 = A[pi * C + k], r2 = A[qi * C + k];
-                const cd t1 = g_mul(se, r2), t2 = g_mul(sec, r1);
+                const cd t1 = zmul(se, r2), t2 = zmul(sec, r1);
                 A[pi * C + k] = make_double2(c * r1.x - t1.x, c * r1.y - t1.y);
                 A[qi * C + k] = make_double2(t2.x + c * r2.x, t2.y + c * r2.y);
             }
@@ -148,8 +133,8 @@ __global__ void __launch_bounds__(256) global_coherence_kernel(GcArgs a) {
     }
     __syncthreads();
     const int K = a.max_rank;
-    double* val = a.values + (p * a.N + n) * K;
-    cd* vec = a.vectors + (p * a.N + n) * (int64_t)C * K;
+    double* val = a.values + (p * a.v.N + n) * K;
+    cd* vec = a.vectors + (p * a.v.N + n) * (int64_t)C * K;
     for (int k = tid; k < K; k += 256) {
         const int src = a.ascending ? order[K - 1 - k] : order[k];     // svds returns the K largest, smallest first
         const double v = ev[src];
@@ -171,7 +156,7 @@ __global__ void __launch_bounds__(256) global_coherence_kernel(GcArgs a) {
             phase = ab > 0.0 ? make_double2(b.x / ab, -b.y / ab) : make_double2(1.0, 0.0);
         }
         __syncthreads();
-        for (int i = tid; i < C; i += 256) vec[(int64_t)i * K + k] = g_mul(V[i * C + src], phase);
+        for (int i = tid; i < C; i += 256) vec[(int64_t)i * K + k] = zmul(V[i * C + src], phase);
         __syncthreads();
     }
 }
@@ -222,19 +207,19 @@ __global__ void __launch_bounds__(NT) global_coherence_big_kernel(GcBigArgs b) {
     double* mylog = b.log + (size_t)blockIdx.x * GC_BIG_SWEEPS * (M - 1) * H * 3;
     gc_block_table<NT>(blk_u, blk_v, H, tid);           // once per workgroup
     for (int item = blockIdx.x; item < b.n_bins_total; item += gridDim.x) {
-        const int64_t p = item / a.N, n = item - p * a.N;
+        const int64_t p = item / a.v.N, n = item - p * a.v.N;
         int64_t bin = n;
         bool conj = false;
-        if (!a.two_sided && n > a.N / 2) { bin = a.N - n; conj = true; }
-        const ScRec rec = a.accum + (p * a.F + bin) * a.floats_per_bin;
+        if (!a.v.two_sided && n > a.v.N / 2) { bin = a.v.N - n; conj = true; }
+        const ScRec rec = sc_csm_record(a.accum, a.v, p, bin);
         __syncthreads();
         for (int e = tid; e < C * C; e += NT) {
             const int i = e / C, j = e % C;
             if (i > j) continue;
             const int ti = i >> 4, tj = j >> 4, ii = i & 15, jj = j & 15;      // i <= j: upper triangle, no mirror
-            const int64_t off = (int64_t)sc_tile_index(ti, tj, a.NB) * SC_TILE_ELEMS + ii * 16 + jj;
-            const double re = (double)rec[(int64_t)a.p_csm * a.n_tiles * SC_TILE_ELEMS + off] / a.n_obs;
-            double im = (double)rec[(int64_t)(a.p_csm + 1) * a.n_tiles * SC_TILE_ELEMS + off] / a.n_obs;
+            const int64_t off = (int64_t)sc_tile_index(ti, tj, a.v.NB) * SC_TILE_ELEMS + ii * 16 + jj;
+            const double re = (double)rec[(int64_t)a.v.p_csm * a.v.n_tiles * SC_TILE_ELEMS + off] / a.v.n_obs;
+            double im = (double)rec[(int64_t)(a.v.p_csm + 1) * a.v.n_tiles * SC_TILE_ELEMS + off] / a.v.n_obs;
             if (conj) im = -im;
             if (i == j) im = 0.0;
             A[gc_tri(i, j, C)] = make_double2(re, im);
@@ -251,8 +236,8 @@ __global__ void __launch_bounds__(NT) global_coherence_big_kernel(GcBigArgs b) {
         }
         __syncthreads();
         const int K = a.max_rank;
-        double* val = a.values + (p * a.N + n) * K;
-        cd* vec = a.vectors + (p * a.N + n) * (int64_t)C * K;
+        double* val = a.values + (p * a.v.N + n) * K;
+        cd* vec = a.vectors + (p * a.v.N + n) * (int64_t)C * K;
         for (int k = tid; k < K; k += NT) {
             const int src = a.ascending ? order[K - 1 - k] : order[k];
             val[k] = ev[src] > 0.0 ? ev[src] : 0.0;
@@ -281,7 +266,7 @@ __global__ void __launch_bounds__(NT) global_coherence_big_kernel(GcBigArgs b) {
                     const double c = lg[0];
                     const cd se = make_double2(lg[1], lg[2]), sec = make_double2(lg[1], -lg[2]);
                     const cd xp = xv[k * C + pi], xq = xv[k * C + qi];
-                    const cd t1 = g_mul(se, xq), t2 = g_mul(sec, xp);
+                    const cd t1 = zmul(se, xq), t2 = zmul(sec, xp);
                     xv[k * C + pi] = make_double2(c * xp.x + t1.x, c * xp.y + t1.y);
                     xv[k * C + qi] = make_double2(c * xq.x - t2.x, c * xq.y - t2.y);
                 }
@@ -303,7 +288,7 @@ __global__ void __launch_bounds__(NT) global_coherence_big_kernel(GcBigArgs b) {
             __syncthreads();
             for (int e = tid; e < kb * C; e += NT) {
                 const int k = e / C, i = e % C;
-                vec[(int64_t)i * K + k0 + k] = g_mul(xv[k * C + i], phase[k]);
+                vec[(int64_t)i * K + k0 + k] = zmul(xv[k * C + i], phase[k]);
             }
             __syncthreads();
         }
@@ -368,24 +353,11 @@ __global__ void __launch_bounds__(GE_NT) global_coherence_eigh_kernel(GcEighArgs
     double* W = b.work + (size_t)blockIdx.x * 8 * C * KS;
     auto WK = [&](int arr, int i, int t) -> double& { return W[((size_t)arr * C + i) * KS + t]; };
     for (int item = blockIdx.x; item < b.n_bins_total; item += gridDim.x) {
-        const int64_t p = item / a.N, n = item - p * a.N;
-        int64_t bin = n;
-        bool conj = false;
-        if (!a.two_sided && n > a.N / 2) { bin = a.N - n; conj = true; }
-        const ScRec rec = a.accum + (p * a.F + bin) * a.floats_per_bin;
+        const int64_t p = item / a.v.N, n = item - p * a.v.N;
         __syncthreads();
         for (int el = tid; el < C * C; el += GE_NT) {
             const int i = el % C, j = el / C;              // column-major: consecutive threads walk down a column
-            int ti = i >> 4, tj = j >> 4, ii = i & 15, jj = j & 15;
-            const bool m = (ti > tj) || (ti == tj && ii > jj);
-            if (m) { int t = ti; ti = tj; tj = t; t = ii; ii = jj; jj = t; }
-            const int64_t off = (int64_t)sc_tile_index(ti, tj, a.NB) * SC_TILE_ELEMS + ii * 16 + jj;
-            const double re = (double)rec[(int64_t)a.p_csm * a.n_tiles * SC_TILE_ELEMS + off] / a.n_obs;
-            double im = (double)rec[(int64_t)(a.p_csm + 1) * a.n_tiles * SC_TILE_ELEMS + off] / a.n_obs;
-            if (m) im = -im;
-            if (conj) im = -im;
-            if (i == j) im = 0.0;
-            A[el] = make_double2(re, im);
+            A[el] = sc_csm_two_sided(a.accum, a.v, p, n, i, j);
         }
         __syncthreads();
         // ---- tridiagonalisation (zhetd2, lower) ----
@@ -411,7 +383,7 @@ __global__ void __launch_bounds__(GE_NT) global_coherence_eigh_kernel(GcEighArgs
                 const double dr = alr - beta, di = ali, dd = dr * dr + di * di;
                 const cd scale = make_double2(dr / dd, -di / dd);          // 1 / (alpha - beta)
                 cd v = make_double2(1.0, 0.0);
-                if (tid >= 1 && tid < m) v = g_mul(xi, scale);
+                if (tid >= 1 && tid < m) v = zmul(xi, scale);
                 if (tid < m) { vs[tid] = v; col[tid] = v; }
                 if (tid == 0) { tau[k] = tk; e[k] = beta; }
             }
@@ -425,15 +397,15 @@ __global__ void __launch_bounds__(GE_NT) global_coherence_eigh_kernel(GcEighArgs
                     acc.x += aij.x * vj.x - aij.y * vj.y;
                     acc.y += aij.x * vj.y + aij.y * vj.x;
                 }
-                pi = g_mul(tk, acc);
+                pi = zmul(tk, acc);
             }
             const cd vi = tid < m ? vs[tid] : make_double2(0.0, 0.0);
             const double dre = ge_block_sum<GE_NT>(pi.x * vi.x + pi.y * vi.y, red, tid);       // p^H v
             const double dim = ge_block_sum<GE_NT>(pi.x * vi.y - pi.y * vi.x, red, tid);
-            const cd al2 = g_mul(make_double2(-0.5 * tk.x, -0.5 * tk.y), make_double2(dre, dim));
+            const cd al2 = zmul(make_double2(-0.5 * tk.x, -0.5 * tk.y), make_double2(dre, dim));
             cd wi = make_double2(0.0, 0.0);
             if (tid < m) {
-                const cd t = g_mul(al2, vi);
+                const cd t = zmul(al2, vi);
                 wi = make_double2(pi.x + t.x, pi.y + t.y);
                 ws[tid] = wi;
             }
@@ -503,8 +475,8 @@ __global__ void __launch_bounds__(GE_NT) global_coherence_eigh_kernel(GcEighArgs
             ev[tid] = 0.5 * (lo + hi);
         }
         __syncthreads();
-        double* val = a.values + (p * a.N + n) * K;
-        cd* vec = a.vectors + (p * a.N + n) * (int64_t)C * K;
+        double* val = a.values + (p * a.v.N + n) * K;
+        cd* vec = a.vectors + (p * a.v.N + n) * (int64_t)C * K;
         for (int k = tid; k < K; k += GE_NT) {
             const int r = a.ascending ? K - 1 - k : k;     // rank from the top
             const double v = ev[C - 1 - r];
@@ -642,7 +614,7 @@ __global__ void __launch_bounds__(GE_NT) global_coherence_eigh_kernel(GcEighArgs
                     }
 #pragma unroll
                     for (int off = 32; off > 0; off >>= 1) { sr += __shfl_xor(sr, off); si += __shfl_xor(si, off); }
-                    const cd f = g_mul(tk, make_double2(sr, si));
+                    const cd f = zmul(tk, make_double2(sr, si));
 #pragma unroll
                     for (int q = 0; q < XQ; ++q) {
                         xr[q] -= vq[q].x * f.x - vq[q].y * f.y;
@@ -672,7 +644,7 @@ __global__ void __launch_bounds__(GE_NT) global_coherence_eigh_kernel(GcEighArgs
 #pragma unroll
                 for (int q = 0; q < XQ; ++q) {
                     const int i = lane + 64 * q;
-                    if (i < C) vec[(int64_t)i * K + kout] = g_mul(make_double2(xr[q], xim[q]), ph);
+                    if (i < C) vec[(int64_t)i * K + kout] = zmul(make_double2(xr[q], xim[q]), ph);
                 }
             }
         }
@@ -686,22 +658,17 @@ extern "C" int sc_global_coherence_f64(const void* d_accum, int64_t n_groups, in
                                        double* d_values, void* d_vectors, void* stream) {
     ScTimed timed_("global_coherence", stream);
     SC_REQUIRE(d_accum && d_values && d_vectors, "NULL argument");
-    SC_REQUIRE(planes & SC_PLANE_CSM, "accumulator record must contain SC_PLANE_CSM");
-    SC_REQUIRE(n_freq_accum == N || n_freq_accum == N / 2 + 1, "accumulators must hold N or N/2+1 bins");
-    SC_REQUIRE(n_groups >= 1 && n_groups <= 65535 && N >= 1 && n_obs >= 1, "bad problem size");
+    GcArgs a;
+    const int rcv = sc_csm_view(planes, n_freq_accum, N, C, n_obs, &a.v);
+    if (rcv != SC_OK) return rcv;
+    SC_REQUIRE(n_groups >= 1 && n_groups <= 65535 && N >= 1, "bad problem size");
     if (C < 1 || C > GC_EIGH_CMAX) {
         sc_set_error("global coherence: n_signals <= %d (got %lld)", GC_EIGH_CMAX, (long long)C);
         return SC_EUNSUPPORTED;
     }
     SC_REQUIRE(max_rank >= 1 && max_rank <= C, "max_rank must be in 1..n_signals");
-    GcArgs a;
     a.accum = sc_rec(d_accum, planes); a.values = d_values; a.vectors = (cd*)d_vectors;
-    a.N = N; a.F = n_freq_accum; a.C = (int)C;
-    a.NB = sc_n_blocks(C); a.n_tiles = sc_n_tiles(a.NB);
-    a.p_csm = sc_plane_offset(planes, SC_PLANE_CSM);
-    a.two_sided = (n_freq_accum == N && N > 1) ? 1 : 0;
-    a.floats_per_bin = (int64_t)sc_plane_count(planes) * a.n_tiles * SC_TILE_ELEMS;
-    a.max_rank = max_rank; a.ascending = ascending; a.n_obs = (double)n_obs;
+    a.C = (int)C; a.max_rank = max_rank; a.ascending = ascending;
     const int M = (int)C + ((int)C & 1);
     const char* eig_env = sc_switch(SC_SW_GLOBAL_EIG);       // "jacobi": the round-2 kernels beyond 64 signals too (cross-check)
     if (C > GC_HUGE_CMAX && eig_env && strcmp(eig_env, "jacobi") == 0) {

@@ -6,9 +6,6 @@
 #pragma once
 #include "sc_common.h"
 
-typedef double2 jcd;
-__device__ inline jcd g_mul(jcd a, jcd b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-#define cd jcd
 __device__ inline int gc_tri(int i, int j, int C) { return i * C - i * (i - 1) / 2 + (j - i); }   // i <= j
 __device__ inline cd gc_get(const cd* A, int i, int j, int C) {
     if (i <= j) return A[gc_tri(i, j, C)];
@@ -96,16 +93,16 @@ __device__ inline void gc_jacobi(cd* A, int C, double* rc, cd* rs, int* rp, cons
                 cd b11 = (uhas && vhas) ? gc_get(A, uq, vq, C) : make_double2(0, 0);
                 // T = B J_v : columns vp, vq
                 const cd svc = make_double2(sv.x, -sv.y);
-                cd t00 = make_double2(cv * b00.x - g_mul(svc, b01).x, cv * b00.y - g_mul(svc, b01).y);
-                cd t01 = make_double2(g_mul(sv, b00).x + cv * b01.x, g_mul(sv, b00).y + cv * b01.y);
-                cd t10 = make_double2(cv * b10.x - g_mul(svc, b11).x, cv * b10.y - g_mul(svc, b11).y);
-                cd t11 = make_double2(g_mul(sv, b10).x + cv * b11.x, g_mul(sv, b10).y + cv * b11.y);
+                cd t00 = make_double2(cv * b00.x - zmul(svc, b01).x, cv * b00.y - zmul(svc, b01).y);
+                cd t01 = make_double2(zmul(sv, b00).x + cv * b01.x, zmul(sv, b00).y + cv * b01.y);
+                cd t10 = make_double2(cv * b10.x - zmul(svc, b11).x, cv * b10.y - zmul(svc, b11).y);
+                cd t11 = make_double2(zmul(sv, b10).x + cv * b11.x, zmul(sv, b10).y + cv * b11.y);
                 // B' = J_u^H T : rows up, uq  (row p' = c row p - s row q ; row q' = conj(s) row p + c row q)
                 const cd suc = make_double2(su.x, -su.y);
-                const cd n00 = make_double2(cu * t00.x - g_mul(su, t10).x, cu * t00.y - g_mul(su, t10).y);
-                const cd n01 = make_double2(cu * t01.x - g_mul(su, t11).x, cu * t01.y - g_mul(su, t11).y);
-                const cd n10 = make_double2(g_mul(suc, t00).x + cu * t10.x, g_mul(suc, t00).y + cu * t10.y);
-                const cd n11 = make_double2(g_mul(suc, t01).x + cu * t11.x, g_mul(suc, t01).y + cu * t11.y);
+                const cd n00 = make_double2(cu * t00.x - zmul(su, t10).x, cu * t00.y - zmul(su, t10).y);
+                const cd n01 = make_double2(cu * t01.x - zmul(su, t11).x, cu * t01.y - zmul(su, t11).y);
+                const cd n10 = make_double2(zmul(suc, t00).x + cu * t10.x, zmul(suc, t00).y + cu * t10.y);
+                const cd n11 = make_double2(zmul(suc, t01).x + cu * t11.x, zmul(suc, t01).y + cu * t11.y);
                 if (u == v) {
                     // diagonal block: Hermitian, off-diagonal annihilated by construction
                     gc_set(A, up, up, C, make_double2(n00.x, 0.0));
@@ -126,4 +123,3 @@ __device__ inline void gc_jacobi(cd* A, int C, double* rc, cd* rs, int* rp, cons
         __syncthreads();
     }
 }
-#undef cd

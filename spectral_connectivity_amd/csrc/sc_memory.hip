@@ -5,6 +5,15 @@
 // their own allocator and streams: every compute entry point takes raw device pointers from either.
 #include "sc_common.h"
 
+// d_out[0 .. n) = NaN on the stream: the "not computed" default of the stage-D outputs
+__global__ void fill_nan_kernel(double* out, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = nan("");
+}
+void sc_internal_fill_nan(double* d_out, int64_t n, hipStream_t st) {
+    hipLaunchKernelGGL(fill_nan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_out, n);
+}
+
 // The default pool hands freed memory back to the driver at the next synchronisation (release threshold 0): every
 // allocation of a steady-state loop would then be a real hipMalloc.  Keep what was freed (one setting per device).
 static void keep_pool_memory() {

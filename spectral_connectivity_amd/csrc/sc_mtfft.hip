@@ -69,27 +69,7 @@ __device__ __forceinline__ unsigned mt_pack_f16(float lo, float hi) {        // 
     const mt_h16x2 v = {(_Float16)lo, (_Float16)hi};
     return __builtin_bit_cast(unsigned, v);
 }
-// two scaled reals -> the dwords of their leading and trailing f16 pieces (x = h + m to 22 significant bits)
-__device__ __forceinline__ void mt_split2(float x0, float x1, unsigned& h, unsigned& m) {
-    // h = f16(x), m = f16(x - h), two values per register: one packed conversion and two mixed-precision fmas that read
-    // their f16 operand straight from the halves of h (left to the compiler: four conversions and a subtraction per value)
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h) : "v"(x0), "v"(x1));
-    asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(m) : "v"(x0), "v"(h));
-    asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(m) : "v"(x1), "v"(h));
-}
-
-// One step of a 4 x 4 transpose inside a quad of lanes (planes-format store loop): lanes with `hi` clear give b and take the
-// partner's a into b, lanes with `hi` set give a and take the partner's b into a; the partner is lane ^ 1 (CTRL = quad_perm
-// [1, 0, 3, 2]) or lane ^ 2 ([2, 3, 0, 1]).
-template <int CTRL>
-__device__ __forceinline__ void mt_quad_xchg(u32x4_t& a, u32x4_t& b, bool hi) {
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        const unsigned give = hi ? a[d] : b[d];
-        const unsigned take = (unsigned)__builtin_amdgcn_mov_dpp((int)give, CTRL, 0xf, 0xf, true);
-        if (hi) a[d] = take; else b[d] = take;
-    }
-}
+// (mt_split2, mt_quad_xchg of the planes-format store loop: sc_mtfft_bfly.h)
 
 // THREADS: 256 by default.  Long windows (N >= 1024) take 512-thread workgroups -- twice the transforms, so twice the
 // contiguous piece of a frequency row per store group (128 bytes at N = 1024: a full line) -- at the same number of
@@ -852,7 +832,7 @@ struct MxArgs {
     const float* scale;    // [C] powers of two
     int64_t row_bytes;
 };
-// two scaled reals (channels c, c + 1 of one component) -> their f16 pieces h and m = x - h, one dword each (sc_fused2.hip: f2_split2)
+// two scaled reals (channels c, c + 1 of one component) -> their f16 pieces h and m = x - h, one dword each (sc_fused2.hip: f2_split2; the compiler-scheduled form of mt_split2, sc_mtfft_bfly.h)
 __device__ __forceinline__ void mx_split2(float x0, float x1, unsigned& h, unsigned& m) {
     typedef _Float16 mx_h2 __attribute__((ext_vector_type(2)));
     const mx_h2 hv = {(_Float16)x0, (_Float16)x1};

@@ -1,4 +1,5 @@
-// sc_mtfft_bfly.h -- the float32 butterflies shared by the fused multitaper transform kernels (sc_mtfft.hip, sc_mtfft_long.hip).
+// sc_mtfft_bfly.h -- the float32 butterflies and the planes-format store helpers shared by the fused multitaper transform kernels
+// (sc_mtfft.hip, sc_mtfft_long.hip, sc_mtfft_mixed.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -57,4 +58,27 @@ __device__ __forceinline__ void dft8r(float2 (&x)[8]) {
     x[1] = make_float2(e1.x + o1.x, e1.y + o1.y); x[5] = make_float2(e1.x - o1.x, e1.y - o1.y);
     x[2] = make_float2(e2.x + o2.x, e2.y + o2.y); x[6] = make_float2(e2.x - o2.x, e2.y - o2.y);
     x[3] = make_float2(e3.x + o3.x, e3.y + o3.y); x[7] = make_float2(e3.x - o3.x, e3.y - o3.y);
+}
+
+// two scaled reals -> the dwords of their leading and trailing f16 pieces (x = h + m to 22 significant bits)
+__device__ __forceinline__ void mt_split2(float x0, float x1, unsigned& h, unsigned& m) {
+    // h = f16(x), m = f16(x - h), two values per register: one packed conversion and two mixed-precision fmas that read
+    // their f16 operand straight from the halves of h (left to the compiler: four conversions and a subtraction per value)
+    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h) : "v"(x0), "v"(x1));
+    asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(m) : "v"(x0), "v"(h));
+    asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(m) : "v"(x1), "v"(h));
+}
+
+// One step of a 4 x 4 transpose inside a quad of lanes (planes-format store loop): lanes with `hi` clear give b and take the
+// partner's a into b, lanes with `hi` set give a and take the partner's b into a; the partner is lane ^ 1 (CTRL = quad_perm
+// [1, 0, 3, 2]) or lane ^ 2 ([2, 3, 0, 1]).
+typedef unsigned mt_u32x4 __attribute__((ext_vector_type(4)));
+template <int CTRL>
+__device__ __forceinline__ void mt_quad_xchg(mt_u32x4& a, mt_u32x4& b, bool hi) {
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        const unsigned give = hi ? a[d] : b[d];
+        const unsigned take = (unsigned)__builtin_amdgcn_mov_dpp((int)give, CTRL, 0xf, 0xf, true);
+        if (hi) a[d] = take; else b[d] = take;
+    }
 }

@@ -15,53 +15,49 @@
 #include <cstring>
 #include "sc_common.h"
 
-typedef double2 zd;
-__device__ __forceinline__ zd zd_add(zd a, zd b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ zd zd_sub(zd a, zd b) { return make_double2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ zd zd_mul(zd a, zd b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 
 struct MdArgs {
     const double* x;
     const double* tapers;   // [K][L], already divided by fs
-    zd* X;                  // [F][W][R][K][C]
+    cd* X;                  // [F][W][R][K][C]
     int T, R, C, L, step, W, K, detrend;
 };
 
 // one radix-R butterfly of a Stockham pass: inputs src[b + t m] (twiddled by W^(t k tw_step), k = b mod Ls), DFT_R in registers
 template <int R>
-__device__ __forceinline__ void md_bfly_compute(const zd* __restrict__ src, const zd* __restrict__ tw, int b, int m, int Ls,
-                                                int tw_step, zd (&v)[R]) {
+__device__ __forceinline__ void md_bfly_compute(const cd* __restrict__ src, const cd* __restrict__ tw, int b, int m, int Ls,
+                                                int tw_step, cd (&v)[R]) {
     const int k = b % Ls;
 #pragma unroll
     for (int t = 0; t < R; ++t) {
         v[t] = src[b + t * m];
-        if (t > 0 && Ls > 1) v[t] = zd_mul(v[t], tw[t * k * tw_step]);
+        if (t > 0 && Ls > 1) v[t] = zmul(v[t], tw[t * k * tw_step]);
     }
     if constexpr (R == 2) {
-        const zd a = v[0], c = v[1];
-        v[0] = zd_add(a, c); v[1] = zd_sub(a, c);
+        const cd a = v[0], c = v[1];
+        v[0] = zadd(a, c); v[1] = zsub(a, c);
     } else if constexpr (R == 3) {
         constexpr double S3 = 0.86602540378443864676;
-        const zd s = zd_add(v[1], v[2]), d = zd_sub(v[1], v[2]);
-        const zd t = make_double2(v[0].x - 0.5 * s.x, v[0].y - 0.5 * s.y);
-        v[0] = zd_add(v[0], s);
+        const cd s = zadd(v[1], v[2]), d = zsub(v[1], v[2]);
+        const cd t = make_double2(v[0].x - 0.5 * s.x, v[0].y - 0.5 * s.y);
+        v[0] = zadd(v[0], s);
         v[1] = make_double2(t.x + S3 * d.y, t.y - S3 * d.x);      // t - i S3 d
         v[2] = make_double2(t.x - S3 * d.y, t.y + S3 * d.x);      // t + i S3 d
     } else if constexpr (R == 4) {
-        const zd s02 = zd_add(v[0], v[2]), d02 = zd_sub(v[0], v[2]), s13 = zd_add(v[1], v[3]), d13 = zd_sub(v[1], v[3]);
-        v[0] = zd_add(s02, s13);
-        v[2] = zd_sub(s02, s13);
+        const cd s02 = zadd(v[0], v[2]), d02 = zsub(v[0], v[2]), s13 = zadd(v[1], v[3]), d13 = zsub(v[1], v[3]);
+        v[0] = zadd(s02, s13);
+        v[2] = zsub(s02, s13);
         v[1] = make_double2(d02.x + d13.y, d02.y - d13.x);        // d02 - i d13
         v[3] = make_double2(d02.x - d13.y, d02.y + d13.x);        // d02 + i d13
     } else {
         constexpr double C1 = 0.30901699437494742410, C2 = -0.80901699437494742410;
         constexpr double S1 = 0.95105651629515357212, S2 = 0.58778525229247312917;
-        const zd a1 = zd_add(v[1], v[4]), a2 = zd_add(v[2], v[3]), b1 = zd_sub(v[1], v[4]), b2 = zd_sub(v[2], v[3]);
-        const zd p1 = make_double2(v[0].x + C1 * a1.x + C2 * a2.x, v[0].y + C1 * a1.y + C2 * a2.y);
-        const zd p2 = make_double2(v[0].x + C2 * a1.x + C1 * a2.x, v[0].y + C2 * a1.y + C1 * a2.y);
-        const zd q1 = make_double2(S1 * b1.x + S2 * b2.x, S1 * b1.y + S2 * b2.y);
-        const zd q2 = make_double2(S2 * b1.x - S1 * b2.x, S2 * b1.y - S1 * b2.y);
-        v[0] = zd_add(v[0], zd_add(a1, a2));
+        const cd a1 = zadd(v[1], v[4]), a2 = zadd(v[2], v[3]), b1 = zsub(v[1], v[4]), b2 = zsub(v[2], v[3]);
+        const cd p1 = make_double2(v[0].x + C1 * a1.x + C2 * a2.x, v[0].y + C1 * a1.y + C2 * a2.y);
+        const cd p2 = make_double2(v[0].x + C2 * a1.x + C1 * a2.x, v[0].y + C2 * a1.y + C1 * a2.y);
+        const cd q1 = make_double2(S1 * b1.x + S2 * b2.x, S1 * b1.y + S2 * b2.y);
+        const cd q2 = make_double2(S2 * b1.x - S1 * b2.x, S2 * b1.y - S1 * b2.y);
+        v[0] = zadd(v[0], zadd(a1, a2));
         v[1] = make_double2(p1.x + q1.y, p1.y - q1.x);            // p1 - i q1
         v[4] = make_double2(p1.x - q1.y, p1.y + q1.x);            // p1 + i q1
         v[2] = make_double2(p2.x + q2.y, p2.y - q2.x);            // p2 - i q2
@@ -70,7 +66,7 @@ __device__ __forceinline__ void md_bfly_compute(const zd* __restrict__ src, cons
 }
 // ... and its outputs: dst[(b - k) R + k + t Ls] (autosort: natural order after the last pass)
 template <int R>
-__device__ __forceinline__ void md_bfly_store(zd* __restrict__ dst, int b, int Ls, const zd (&v)[R]) {
+__device__ __forceinline__ void md_bfly_store(cd* __restrict__ dst, int b, int Ls, const cd (&v)[R]) {
     const int k = b % Ls, base = (b - k) * R + k;
 #pragma unroll
     for (int t = 0; t < R; ++t) dst[base + t * Ls] = v[t];
@@ -86,14 +82,14 @@ __device__ __forceinline__ void md_bfly_store(zd* __restrict__ dst, int b, int L
 // all passes of one transform, in place, by one wave: a lane pulls the butterflies b = lane, lane + 64, ... of the pass into
 // registers, the wave meets, and writes them back
 template <int N, int LS>
-__device__ __forceinline__ void md_passes_wave(zd* z, const zd* tw, int lane) {
+__device__ __forceinline__ void md_passes_wave(cd* z, const cd* tw, int lane) {
     if constexpr (LS < N) {
         constexpr int rem = N / LS;
         constexpr int R = rem % 5 == 0 ? 5 : (rem % 4 == 0 ? 4 : (rem % 3 == 0 ? 3 : 2));
         constexpr int m = N / R, tw_step = N / (LS * R), ROUNDS = (m + 63) / 64;
         // In place needs every input of the pass read before any output is written: all ROUNDS butterflies of a lane live
         // in registers at once (N = 1024, radix 4: 4 rounds x 4 x 4 registers = 64).
-        zd v[ROUNDS][R];
+        cd v[ROUNDS][R];
 #pragma unroll
         for (int j = 0; j < ROUNDS; ++j) {
             const int b = lane + 64 * j;
@@ -115,9 +111,9 @@ __global__ void __launch_bounds__(64 * NF) mtfft_f64_kernel(MdArgs p) {
     constexpr int NT = 64 * NF, CT = 2 * NF, XS = CT + 1, F = N / 2 + 1;
     constexpr int LCT = CT == 32 ? 5 : (CT == 16 ? 4 : (CT == 8 ? 3 : 2)), LNF = LCT - 1;
     extern __shared__ __align__(16) unsigned char smem[];
-    zd* z = reinterpret_cast<zd*>(smem);                          // [NF][N]; the detrend scratch aliases it
+    cd* z = reinterpret_cast<cd*>(smem);                          // [NF][N]; the detrend scratch aliases it
     double* red = reinterpret_cast<double*>(smem);                // [2][NT] + trend [2][CT]
-    zd* tw = z + (NF * N > (NT + CT) ? NF * N : (NT + CT));       // [N]
+    cd* tw = z + (NF * N > (NT + CT) ? NF * N : (NT + CT));       // [N]
     double* tile = reinterpret_cast<double*>(tw + N);             // [L][XS] (odd stride: the column walks of the trend sums)
     __shared__ int nzf[CT], nbf[CT];                              // channel not identically zero after the detrend / holds a non-finite sample
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -196,11 +192,11 @@ __global__ void __launch_bounds__(64 * NF) mtfft_f64_kernel(MdArgs p) {
     const int spr = 2 * (tid & (NF - 1));
     const bool na = nbf[spr] != 0, nb = nbf[spr + 1] != 0, za = !na && nzf[spr] == 0, zb = !nb && nzf[spr + 1] == 0;
     const int64_t sF = (int64_t)p.W * p.R * p.K * C;
-    zd* zw = z + wave * N;                                        // this wave's pair
+    cd* zw = z + wave * N;                                        // this wave's pair
     for (int k = 0; k < p.K; ++k) {
         const double* hk = p.tapers + (int64_t)k * L;
         for (int n = lane; n < N; n += 64) {
-            zd v = make_double2(0.0, 0.0);
+            cd v = make_double2(0.0, 0.0);
             if (n < L) {
                 const double h = hk[n];
                 v = make_double2(tile[n * XS + 2 * wave] * h, tile[n * XS + 2 * wave + 1] * h);
@@ -210,18 +206,18 @@ __global__ void __launch_bounds__(64 * NF) mtfft_f64_kernel(MdArgs p) {
         MD_WAVE_SYNC();
         md_passes_wave<N, 1>(zw, tw, lane);
         __syncthreads();                                          // every pair transformed
-        zd* Xk = p.X + (((int64_t)w * p.R + r) * p.K + k) * C + c0;
+        cd* Xk = p.X + (((int64_t)w * p.R + r) * p.K + k) * C + c0;
         for (int idx = tid; idx < F * NF; idx += NT) {
             const int f = idx >> LNF, pr = idx & (NF - 1), c = c0 + 2 * pr;
             if (c >= C) continue;
-            const zd u1 = z[pr * N + f], u2 = z[pr * N + (f == 0 ? 0 : N - f)];
-            zd A = make_double2(0.5 * (u1.x + u2.x), 0.5 * (u1.y - u2.y));
-            zd B = make_double2(0.5 * (u1.y + u2.y), 0.5 * (u2.x - u1.x));
+            const cd u1 = z[pr * N + f], u2 = z[pr * N + (f == 0 ? 0 : N - f)];
+            cd A = make_double2(0.5 * (u1.x + u2.x), 0.5 * (u1.y - u2.y));
+            cd B = make_double2(0.5 * (u1.y + u2.y), 0.5 * (u2.x - u1.x));
             if (za) A = make_double2(0.0, 0.0);
             if (zb) B = make_double2(0.0, 0.0);
             if (na) A = make_double2(__longlong_as_double(0x7ff8000000000000LL), __longlong_as_double(0x7ff8000000000000LL));
             if (nb) B = make_double2(__longlong_as_double(0x7ff8000000000000LL), __longlong_as_double(0x7ff8000000000000LL));
-            zd* d = Xk + (int64_t)f * sF + 2 * pr;
+            cd* d = Xk + (int64_t)f * sF + 2 * pr;
             d[0] = A;                       // (16-byte halves of a 32-byte pair: the write-back L2 merges them -- no streaming hint)
             if (c + 1 < C) d[1] = B;
         }
@@ -237,41 +233,7 @@ __global__ void __launch_bounds__(64 * NF) mtfft_f64_kernel(MdArgs p) {
 // reads), +radix 2 / 4 for 512 / 1024; every exchange stays inside one wavefront (N / 16 <= 64 threads per transform), so it
 // needs no workgroup barrier; the thread's 16 x 2 detrended samples stay in registers for all tapers.  256 threads, 16 / 8 /
 // 4 transforms (32 / 16 / 8 channels) per workgroup at N <= 256 / 512 / 1024.
-__device__ __forceinline__ zd zd_mulc(zd a, double c, double s) { return make_double2(a.x * c - a.y * s, a.x * s + a.y * c); }
-__device__ __forceinline__ void zd_dft4(zd& a0, zd& a1, zd& a2, zd& a3) {
-    const zd b0 = zd_add(a0, a2), b1 = zd_sub(a0, a2), b2 = zd_add(a1, a3), b3 = make_double2(a1.y - a3.y, a3.x - a1.x);
-    a0 = zd_add(b0, b2); a1 = zd_add(b1, b3); a2 = zd_sub(b0, b2); a3 = zd_sub(b1, b3);
-}
-// in: x[n], n = 4 n1 + n2 ; out: o[k], k = k1 + 4 k2   (forward DFT, exp(-2 pi i n k / 16))
-__device__ __forceinline__ void zd_dft16(zd (&x)[16], zd (&o)[16]) {
-    constexpr double C1 = 0.92387953251128673848, S1 = 0.38268343236508978178, H = 0.70710678118654752440;
-#pragma unroll
-    for (int n2 = 0; n2 < 4; ++n2) zd_dft4(x[n2], x[4 + n2], x[8 + n2], x[12 + n2]);
-    x[4 + 1] = zd_mulc(x[4 + 1], C1, -S1);  x[8 + 1] = zd_mulc(x[8 + 1], H, -H);    x[12 + 1] = zd_mulc(x[12 + 1], S1, -C1);
-    x[4 + 2] = zd_mulc(x[4 + 2], H, -H);    x[8 + 2] = make_double2(x[8 + 2].y, -x[8 + 2].x);
-    x[12 + 2] = zd_mulc(x[12 + 2], -H, -H);
-    x[4 + 3] = zd_mulc(x[4 + 3], S1, -C1);  x[8 + 3] = zd_mulc(x[8 + 3], -H, -H);   x[12 + 3] = zd_mulc(x[12 + 3], -C1, S1);
-#pragma unroll
-    for (int k1 = 0; k1 < 4; ++k1) {
-        zd a0 = x[4 * k1], a1 = x[4 * k1 + 1], a2 = x[4 * k1 + 2], a3 = x[4 * k1 + 3];
-        zd_dft4(a0, a1, a2, a3);
-        o[k1] = a0; o[k1 + 4] = a1; o[k1 + 8] = a2; o[k1 + 12] = a3;
-    }
-}
-__device__ __forceinline__ void zd_dft8(zd (&x)[8]) {     // natural order in and out
-    constexpr double H = 0.70710678118654752440;
-    zd e0 = x[0], e1 = x[2], e2 = x[4], e3 = x[6], o0 = x[1], o1 = x[3], o2 = x[5], o3 = x[7];
-    zd_dft4(e0, e1, e2, e3);
-    zd_dft4(o0, o1, o2, o3);
-    o1 = zd_mulc(o1, H, -H);
-    o2 = make_double2(o2.y, -o2.x);
-    o3 = zd_mulc(o3, -H, -H);
-    x[0] = zd_add(e0, o0); x[4] = zd_sub(e0, o0);
-    x[1] = zd_add(e1, o1); x[5] = zd_sub(e1, o1);
-    x[2] = zd_add(e2, o2); x[6] = zd_sub(e2, o2);
-    x[3] = zd_add(e3, o3); x[7] = zd_sub(e3, o3);
-}
-
+// (butterflies: zdft4/8/16 of sc_complex.h)
 template <int LOG2N>
 __global__ void __launch_bounds__(256, 2) mtfft16_f64_kernel(MdArgs p, int kh) {
     constexpr int N = 1 << LOG2N, TPF = N / 16, NF = 256 / TPF, CT = 2 * NF, XS = CT + 2, ZS = N + N / 16 + 1, F = N / 2 + 1;
@@ -280,9 +242,9 @@ __global__ void __launch_bounds__(256, 2) mtfft16_f64_kernel(MdArgs p, int kh) {
     constexpr size_t XT_BYTES = (size_t)N * XS * 8, Z_BYTES = (size_t)NF * ZS * 16;
     constexpr size_t UNION_BYTES = XT_BYTES > Z_BYTES ? XT_BYTES : Z_BYTES;
     double* xt = reinterpret_cast<double*>(smem);                                 // [N][XS] window tile ...
-    zd* z = reinterpret_cast<zd*>(smem);                                          // ... then [NF][ZS] exchange buffers
+    cd* z = reinterpret_cast<cd*>(smem);                                          // ... then [NF][ZS] exchange buffers
     double* red = reinterpret_cast<double*>(smem + UNION_BYTES);                  // [2][256] + trend [2][CT]; dead after the detrend:
-    zd* tw = reinterpret_cast<zd*>(smem + UNION_BYTES);                           // [N] twiddles
+    cd* tw = reinterpret_cast<cd*>(smem + UNION_BYTES);                           // [N] twiddles
     double* hk = reinterpret_cast<double*>(tw + N);                               // [kh][L] tapers (kh = K, or 2 buffers)
     __shared__ int nzf[CT], nbf[CT];
     const int tid = threadIdx.x;
@@ -292,7 +254,7 @@ __global__ void __launch_bounds__(256, 2) mtfft16_f64_kernel(MdArgs p, int kh) {
     const int64_t RC = (int64_t)p.R * C;
     const double* xw = p.x + ((int64_t)w * p.step * p.R + r) * C + c0;
     const int pf = tid / TPF, i = tid - pf * TPF;          // transform (channel pair) and butterfly index
-    zd* zf = z + pf * ZS;
+    cd* zf = z + pf * ZS;
     const int64_t sF = (int64_t)p.W * p.R * p.K * C;
     const bool resident = kh == p.K;
     // window tile: 16-byte loads where the row is aligned
@@ -300,9 +262,9 @@ __global__ void __launch_bounds__(256, 2) mtfft16_f64_kernel(MdArgs p, int kh) {
         constexpr int V = CT / 2;
         for (int idx = tid; idx < L * V; idx += 256) {
             const int l = idx / V, cc = 2 * (idx - l * V);
-            zd v = make_double2(0.0, 0.0);
-            if (c0 + cc + 1 < C) v = *reinterpret_cast<const zd*>(xw + (int64_t)l * RC + cc);
-            *reinterpret_cast<zd*>(xt + l * XS + cc) = v;
+            cd v = make_double2(0.0, 0.0);
+            if (c0 + cc + 1 < C) v = *reinterpret_cast<const cd*>(xw + (int64_t)l * RC + cc);
+            *reinterpret_cast<cd*>(xt + l * XS + cc) = v;
         }
     } else {
         for (int idx = tid; idx < L * CT; idx += 256) {
@@ -343,7 +305,7 @@ __global__ void __launch_bounds__(256, 2) mtfft16_f64_kernel(MdArgs p, int kh) {
         }
     }
     __syncthreads();                                          // tile and trend coefficients visible
-    zd xs[16];                                                // this thread's pass-1 inputs, the same for every taper
+    cd xs[16];                                                // this thread's pass-1 inputs, the same for every taper
     {
         const double invL = 1.0 / (double)L;
         const double a0 = detr ? red[512 + 2 * pf] : 0.0, a1 = detr ? red[512 + 2 * pf + 1] : 0.0;
@@ -352,9 +314,9 @@ __global__ void __launch_bounds__(256, 2) mtfft16_f64_kernel(MdArgs p, int kh) {
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
             const int n = i + t * TPF;
-            zd v = make_double2(0.0, 0.0);
+            cd v = make_double2(0.0, 0.0);
             if (n < L) {
-                v = *reinterpret_cast<const zd*>(xt + n * XS + 2 * pf);
+                v = *reinterpret_cast<const cd*>(xt + n * XS + 2 * pf);
                 if (detr) {           // the expression of the wave-per-pair kernel
                     const double tt = (double)(n + 1) * invL;
                     v.x -= a0 * tt + b0;
@@ -410,7 +372,7 @@ __global__ void __launch_bounds__(256, 2) mtfft16_f64_kernel(MdArgs p, int kh) {
             }
         }
         __syncthreads();     // taper k (and, first time, the twiddles) visible; the split of taper k - 1 done
-        zd a[16], o[16];
+        cd a[16], o[16];
         // pass 1: radix 16, inputs straight from registers
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
@@ -418,7 +380,7 @@ __global__ void __launch_bounds__(256, 2) mtfft16_f64_kernel(MdArgs p, int kh) {
             const double h = (n < L) ? hkk[n] : 0.0;
             a[t] = make_double2(xs[t].x * h, xs[t].y * h);
         }
-        zd_dft16(a, o);
+        zdft16(a, o);
 #pragma unroll
         for (int u = 0; u < 16; ++u) zf[PHYS(16 * i + u)] = o[u];
         MD_WAVE_SYNC();
@@ -428,13 +390,13 @@ __global__ void __launch_bounds__(256, 2) mtfft16_f64_kernel(MdArgs p, int kh) {
 #pragma unroll
             for (int b = 0; b < 16 / R2; ++b) {
                 const int u = i + R2 * b;
-                zd q[R2];
+                cd q[R2];
 #pragma unroll
                 for (int j = 0; j < R2; ++j) {
-                    const zd v = zf[PHYS(16 * j + u)];
-                    q[j] = (j == 0) ? v : zd_mul(v, tw[j * u]);
+                    const cd v = zf[PHYS(16 * j + u)];
+                    q[j] = (j == 0) ? v : zmul(v, tw[j * u]);
                 }
-                if constexpr (R2 == 4) zd_dft4(q[0], q[1], q[2], q[3]); else zd_dft8(q);
+                if constexpr (R2 == 4) zdft4(q[0], q[1], q[2], q[3]); else zdft8(q);
 #pragma unroll
                 for (int v = 0; v < R2; ++v) a[b * R2 + v] = q[v];
             }
@@ -450,10 +412,10 @@ __global__ void __launch_bounds__(256, 2) mtfft16_f64_kernel(MdArgs p, int kh) {
             const int kk = i & 15;
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
-                const zd v = zf[PHYS(i + t * TPF)];
-                a[t] = (t == 0) ? v : zd_mul(v, tw[t * kk * (N / 256)]);
+                const cd v = zf[PHYS(i + t * TPF)];
+                a[t] = (t == 0) ? v : zmul(v, tw[t * kk * (N / 256)]);
             }
-            zd_dft16(a, o);
+            zdft16(a, o);
             if constexpr (LOG2N != 8) MD_WAVE_SYNC();         // N = 256 writes back exactly the slots it read
             const int j = ((i - kk) << 4) + kk;
 #pragma unroll
@@ -464,9 +426,9 @@ __global__ void __launch_bounds__(256, 2) mtfft16_f64_kernel(MdArgs p, int kh) {
 #pragma unroll
             for (int b = 0; b < 8; ++b) {
                 const int ib = i + b * TPF;
-                const zd u0 = zf[PHYS(ib)], u1 = zd_mul(zf[PHYS(ib + 256)], tw[ib]);
-                a[2 * b] = zd_add(u0, u1);
-                a[2 * b + 1] = zd_sub(u0, u1);
+                const cd u0 = zf[PHYS(ib)], u1 = zmul(zf[PHYS(ib + 256)], tw[ib]);
+                a[2 * b] = zadd(u0, u1);
+                a[2 * b + 1] = zsub(u0, u1);
             }
 #pragma unroll
             for (int b = 0; b < 8; ++b) {
@@ -482,10 +444,10 @@ __global__ void __launch_bounds__(256, 2) mtfft16_f64_kernel(MdArgs p, int kh) {
                 const int ib = i + b * TPF;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
-                    const zd v = zf[PHYS(ib + t * 256)];
-                    a[4 * b + t] = (t == 0) ? v : zd_mul(v, tw[t * ib]);
+                    const cd v = zf[PHYS(ib + t * 256)];
+                    a[4 * b + t] = (t == 0) ? v : zmul(v, tw[t * ib]);
                 }
-                zd_dft4(a[4 * b], a[4 * b + 1], a[4 * b + 2], a[4 * b + 3]);
+                zdft4(a[4 * b], a[4 * b + 1], a[4 * b + 2], a[4 * b + 3]);
             }
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
@@ -504,24 +466,24 @@ __global__ void __launch_bounds__(256, 2) mtfft16_f64_kernel(MdArgs p, int kh) {
             }
         }
         // split the packed pair, store X[f][w][r][k][c .. c + 1]: eight rounds of 256 outputs + the Nyquist row
-        zd* Xk = p.X + (((int64_t)w * p.R + r) * p.K + k) * C + c0;
+        cd* Xk = p.X + (((int64_t)w * p.R + r) * p.K + k) * C + c0;
         const int pr = tid & (NF - 1), fb = tid / NF, c = c0 + 2 * pr;
         if (c < C) {
-            const zd* zp = z + pr * ZS;
-            auto put = [&](int f, zd u1, zd u2) {
-                zd A = make_double2(0.5 * (u1.x + u2.x), 0.5 * (u1.y - u2.y));
-                zd B = make_double2(0.5 * (u1.y + u2.y), 0.5 * (u2.x - u1.x));
+            const cd* zp = z + pr * ZS;
+            auto put = [&](int f, cd u1, cd u2) {
+                cd A = make_double2(0.5 * (u1.x + u2.x), 0.5 * (u1.y - u2.y));
+                cd B = make_double2(0.5 * (u1.y + u2.y), 0.5 * (u2.x - u1.x));
                 if (za) A = make_double2(0.0, 0.0);
                 if (zb) B = make_double2(0.0, 0.0);
                 if (na) A = make_double2(qnan, qnan);
                 if (nb) B = make_double2(qnan, qnan);
-                zd* dst = Xk + (int64_t)f * sF + 2 * pr;
+                cd* dst = Xk + (int64_t)f * sF + 2 * pr;
                 dst[0] = A;                 // (16-byte halves of a 32-byte pair: the write-back L2 merges them -- no streaming hint;
                 if (c + 1 < C) dst[1] = B;  //  with it the kernel takes 6.1 instead of 4.1 ms at cfg3)
             };
 #pragma unroll
             for (int h = 0; h < 8; h += 4) {
-                zd z1[4], z2[4];
+                cd z1[4], z2[4];
 #pragma unroll
                 for (int it = 0; it < 4; ++it) {
                     const int f = fb + (h + it) * TPF;
@@ -531,7 +493,7 @@ __global__ void __launch_bounds__(256, 2) mtfft16_f64_kernel(MdArgs p, int kh) {
 #pragma unroll
                 for (int it = 0; it < 4; ++it) put(fb + (h + it) * TPF, z1[it], z2[it]);
             }
-            if (tid < NF) { const zd zn = zp[PHYS(N / 2)]; put(N / 2, zn, zn); }
+            if (tid < NF) { const cd zn = zp[PHYS(N / 2)]; put(N / 2, zn, zn); }
         }
         // the barrier at the top of the next taper orders these reads before pass 1 rewrites z
     }
@@ -595,7 +557,7 @@ extern "C" int sc_multitaper_fft_f64(const double* d_x, int64_t T, int64_t R, in
                      "sc_fft_execute_f64", (long long)N, (long long)L);
         return SC_EUNSUPPORTED;
     }
-    MdArgs m{d_x, d_tapers, (zd*)d_X, (int)T, (int)R, (int)C, (int)L, (int)step, (int)W, (int)K, detrend_type};
+    MdArgs m{d_x, d_tapers, (cd*)d_X, (int)T, (int)R, (int)C, (int)L, (int)step, (int)W, (int)K, detrend_type};
     hipStream_t s = (hipStream_t)stream;
     // powers of two: the radix-16 kernel (SC_MTFFT_F64=wave, diagnostic: the wave-per-pair kernel for every length)
     const char* sel = sc_switch(SC_SW_MTFFT_F64);

@@ -54,24 +54,7 @@ struct LongArgs {
 typedef _Float16 ml_h16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned ml_u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned ml_u32x2 __attribute__((ext_vector_type(2)));
-// two scaled reals -> the dwords of their leading and trailing f16 pieces (x = h + m to 22 significant bits): one packed conversion
-// and two mixed-precision fmas that read their f16 operand straight from the halves of h (as in sc_mtfft.hip)
-__device__ __forceinline__ void ml_split2(float x0, float x1, unsigned& h, unsigned& m) {
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h) : "v"(x0), "v"(x1));
-    asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(m) : "v"(x0), "v"(h));
-    asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(m) : "v"(x1), "v"(h));
-}
-// One step of a 4 x 4 transpose inside a quad of lanes: lanes with `hi` clear give b and take the partner's a into b, lanes with
-// `hi` set give a and take the partner's b into a; the partner is lane ^ 1 (CTRL = quad_perm [1, 0, 3, 2]) or lane ^ 2 ([2, 3, 0, 1]).
-template <int CTRL>
-__device__ __forceinline__ void ml_quad_xchg(ml_u32x4& a, ml_u32x4& b, bool hi) {
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        const unsigned give = hi ? a[d] : b[d];
-        const unsigned take = (unsigned)__builtin_amdgcn_mov_dpp((int)give, CTRL, 0xf, 0xf, true);
-        if (hi) a[d] = take; else b[d] = take;
-    }
-}
+// (mt_split2, mt_quad_xchg: sc_mtfft_bfly.h)
 
 template <int LOG2N, int HT, bool PL, bool GRP = false>
 __global__ void __launch_bounds__(2 * HT, HT == 512 ? 1 : 4) mtfft_long_kernel(LongArgs p) {
@@ -511,18 +494,18 @@ __global__ void __launch_bounds__(2 * HT, HT == 512 ? 1 : 4) mtfft_long_kernel(L
                 if (qnb) B = make_float2(__int_as_float(0x7fc00000), __int_as_float(0x7fc00000));
             }
             unsigned h, m;
-            ml_split2(A.x, B.x, h, m);
+            mt_split2(A.x, B.x, h, m);
             rh[q] = h; rm[q] = m;
-            ml_split2(A.y, B.y, h, m);
+            mt_split2(A.y, B.y, h, m);
             ih[q] = h; im[q] = m;
         }
         const int64_t fs = rows_f * p.row_bytes;
         if constexpr (TR) {
             // items (rh, rm, ih, im) = planes 0 .. 3 of this lane's frequency  ->  plane pj of the quad's frequencies 0 .. 3
-            ml_quad_xchg<0xB1>(rh, rm, (pj & 1) != 0);
-            ml_quad_xchg<0xB1>(ih, im, (pj & 1) != 0);
-            ml_quad_xchg<0x4E>(rh, ih, (pj & 2) != 0);
-            ml_quad_xchg<0x4E>(rm, im, (pj & 2) != 0);
+            mt_quad_xchg<0xB1>(rh, rm, (pj & 1) != 0);
+            mt_quad_xchg<0xB1>(ih, im, (pj & 1) != 0);
+            mt_quad_xchg<0x4E>(rh, ih, (pj & 2) != 0);
+            mt_quad_xchg<0x4E>(rm, im, (pj & 2) != 0);
             const int f0 = f - pj;
             unsigned char* dst = dst0 + (int64_t)f0 * fs;
             *reinterpret_cast<VT*>(dst) = rh;

@@ -168,12 +168,7 @@ __device__ __forceinline__ void dft(float2 (&v)[R]) {
 
 typedef unsigned mx_u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned mx_u32x2 __attribute__((ext_vector_type(2)));
-// two scaled reals -> the dwords of their leading and trailing f16 pieces (as in sc_mtfft_long.hip)
-__device__ __forceinline__ void mx_split2(float x0, float x1, unsigned& h, unsigned& m) {
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h) : "v"(x0), "v"(x1));
-    asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(m) : "v"(x0), "v"(h));
-    asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(m) : "v"(x1), "v"(h));
-}
+// (mt_split2: sc_mtfft_bfly.h)
 
 // Geometry of one instantiation, shared by the kernel and its launcher.
 template <int N_, int RM_, int RF_, int HT_, bool ALIGNED_, int BP_, int ZPAD_, int RP_ = 10, bool GRP_ = false>
@@ -606,9 +601,9 @@ __global__ void __launch_bounds__(2 * GEO::HT, 2 * GEO::HT <= 512 ? 4 : 1) mtfft
                 if (qnb) B = make_float2(__int_as_float(0x7fc00000), __int_as_float(0x7fc00000));
             }
             unsigned h, m;
-            mx_split2(A.x, B.x, h, m);
+            mt_split2(A.x, B.x, h, m);
             rh[q] = h; rm[q] = m;
-            mx_split2(A.y, B.y, h, m);
+            mt_split2(A.y, B.y, h, m);
             ih[q] = h; im[q] = m;
         }
         *reinterpret_cast<VT*>(dst) = rh;

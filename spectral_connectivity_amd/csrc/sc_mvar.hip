@@ -14,7 +14,7 @@
 //                           with partial pivoting, the second factor as column operations from the logged multipliers
 //                           (65 ... 128 signals: m_inverse_inplace + two m_gemm_mfma products)
 //     causal transform pair a = ifft_n(A), 1/N, a[0] *= 1/2, strict lower triangle of a[0] = 0, a[n >= (N+1)/2] = 0,
-//                           A+ = fft_n(a): one kernel (sc_wilson_fft.hip) for N = 256 ... 4096, else rocFFT Z2Z + m_causal
+//                           A+ = fft_n(a): one kernel (sc_wilson_fft.hip) for N = 256 ... 4096, else rocFFT Z2Z + wilson_causal
 //     m_update_mfma         G <- G A+, err = max |G - G_old| on the fp64 matrix cores (m_gemm_mfma beyond 64 signals)
 //   measures                H0 = Re mean_n G; H = G (H0 + lam I)^-1 on the non-negative bins;
 //                           A_mvar = (H + lam' I)^-1; Sigma = H0 H0^T; DTF / DC / PDC / gPDC / dDTF.
@@ -24,17 +24,7 @@
 // (m_inverse_global) and the products as 128 x 128 output blocks of m_gemm_mfma.
 #include <stdlib.h>
 #include <string.h>
-#include <rocfft/rocfft.h>
-#include "sc_common.h"
-
-typedef double2 cd;
-__device__ inline cd m_mul(cd a, cd b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ inline cd m_sub(cd a, cd b) { return make_double2(a.x - b.x, a.y - b.y); }
-__device__ inline cd m_conj(cd a) { return make_double2(a.x, -a.y); }
-__device__ inline cd m_div(cd a, cd b) {
-    const double d = b.x * b.x + b.y * b.y;
-    return make_double2((a.x * b.x + a.y * b.y) / d, (a.y * b.x - a.x * b.y) / d);
-}
+#include "sc_wilson_loop.h"
 
 #define MV_CMAX 512          // <= 64: register-resident [G | S] elimination; 65 ... 128: explicit in-register inverse + matrix-
 #define MV_CSMALL 64         // core products; 129 ... 512: panel-blocked inverse in global memory + blocked products
@@ -71,7 +61,7 @@ __device__ void mv_lu_forward(cd* M, cd* R, int C, int NR, int* piv) {
             __syncthreads();
         }
         const cd d = M[k * C + k];
-        for (int i = k + 1 + tid; i < C; i += nt) M[i * C + k] = m_div(M[i * C + k], d);
+        for (int i = k + 1 + tid; i < C; i += nt) M[i * C + k] = zdiv(M[i * C + k], d);
         __syncthreads();
         // trailing update of M and R: thread (ty, tx) walks rows ty, ty + nty, ... and columns tx, tx + 32, ...
         // (no integer division in the O(C^3) loop)
@@ -82,10 +72,10 @@ __device__ void mv_lu_forward(cd* M, cd* R, int C, int NR, int* piv) {
             for (int jj = (nt < 32 ? tid : tx); jj < cm + NR; jj += ntx) {
                 if (jj < cm) {
                     const int j = k + 1 + jj;
-                    M[i * C + j] = m_sub(M[i * C + j], m_mul(l, M[k * C + j]));
+                    M[i * C + j] = zsub(M[i * C + j], zmul(l, M[k * C + j]));
                 } else {
                     const int j = jj - cm;
-                    R[i * NR + j] = m_sub(R[i * NR + j], m_mul(l, R[k * NR + j]));
+                    R[i * NR + j] = zsub(R[i * NR + j], zmul(l, R[k * NR + j]));
                 }
             }
         }
@@ -98,47 +88,25 @@ __device__ void mv_back_subst(const cd* M, cd* R, int C, int NR) {
     const int tid = threadIdx.x, nt = blockDim.x;
     for (int k = C - 1; k >= 0; --k) {
         const cd d = M[k * C + k];
-        for (int j = tid; j < NR; j += nt) R[k * NR + j] = m_div(R[k * NR + j], d);
+        for (int j = tid; j < NR; j += nt) R[k * NR + j] = zdiv(R[k * NR + j], d);
         __syncthreads();
         const int tx = tid & 31, ty = tid >> 5, nty = nt >> 5 ? nt >> 5 : 1, ntx = nt < 32 ? nt : 32;
         for (int i = ty; i < k; i += nty) {
             const cd l = M[i * C + k];
-            for (int j = (nt < 32 ? tid : tx); j < NR; j += ntx) R[i * NR + j] = m_sub(R[i * NR + j], m_mul(l, R[k * NR + j]));
+            for (int j = (nt < 32 ? tid : tx); j < NR; j += ntx) R[i * NR + j] = zsub(R[i * NR + j], zmul(l, R[k * NR + j]));
         }
         __syncthreads();
     }
 }
 
 // ---- spectra in, factor out ---------------------------------------------------------------------
-struct MvDims {
-    int64_t P, N, F;     // windows, two-sided FFT length, accumulated bins per window
-    int C, NB, n_tiles, p_csm, two_sided;
-    int64_t floats_per_bin;
-    double n_obs;
-};
-
-// S[p][e][n] from the accumulator records (upper-triangular 16x16 tiles, un-normalised sums)
-__global__ void m_build(ScRec accum, MvDims d, cd* S, int64_t sn, int64_t se) {
+// S[p][e][n] from the accumulator records (sc_csm_two_sided: window p, two-sided bin n)
+__global__ void m_build(ScRec accum, ScCsmView v, int C, cd* S, int64_t sn, int64_t se) {
     const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t p = blockIdx.z;
-    if (n >= d.N) return;
-    for (int e = blockIdx.y; e < d.C * d.C; e += gridDim.y) {
-    const int i = e / d.C, j = e % d.C;
-    int64_t bin = n;
-    bool conj = false;
-    if (!d.two_sided && n > d.N / 2) { bin = d.N - n; conj = true; }   // real input: S(-f) = conj S(f)
-    const ScRec rec = accum + (p * d.F + bin) * d.floats_per_bin;
-    int ti = i >> 4, tj = j >> 4, ii = i & 15, jj = j & 15;
-    const bool m = (ti > tj) || (ti == tj && ii > jj);
-    if (m) { int t = ti; ti = tj; tj = t; t = ii; ii = jj; jj = t; }
-    const int64_t off = (int64_t)sc_tile_index(ti, tj, d.NB) * SC_TILE_ELEMS + ii * 16 + jj;
-    const double re = (double)rec[(int64_t)d.p_csm * d.n_tiles * SC_TILE_ELEMS + off] / d.n_obs;
-    double im = (double)rec[(int64_t)(d.p_csm + 1) * d.n_tiles * SC_TILE_ELEMS + off] / d.n_obs;
-    if (m) im = -im;
-    if (conj) im = -im;
-    if (i == j) im = 0.0;
-    S[p * d.C * d.C * d.N + n * sn + e * se] = make_double2(re, im);      // series: sn = 1, se = N; natural: sn = C^2, se = 1
-    }
+    if (n >= v.N) return;
+    for (int e = blockIdx.y; e < C * C; e += gridDim.y)       // series: sn = 1, se = N; natural: sn = C^2, se = 1
+        S[p * C * C * v.N + n * sn + e * se] = sc_csm_two_sided(accum, v, p, n, e / C, e % C);
 }
 
 // natural [p][n][e] <-> series [p][e][n]
@@ -256,23 +224,6 @@ __global__ void m_fill(const double* __restrict__ g0, cd* __restrict__ G, int64_
         for (int e = blockIdx.y; e < E; e += gridDim.y) G[(p * E + e) * N + n] = make_double2(g0[p * E + e], 0.0);
 }
 
-__global__ void m_causal(cd* A, int64_t N, int C) {
-    const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t p = blockIdx.z;
-    if (n >= N) return;
-    for (int e = blockIdx.y; e < C * C; e += gridDim.y) {
-        const int i = e / C, j = e % C;
-        double sc = (n < (N + 1) / 2) ? 1.0 / (double)N : 0.0;
-        if (n == 0) { sc *= 0.5; if (i > j) sc = 0.0; }
-        cd* a = A + (p * C * C + e) * N + n;
-        *a = make_double2(a->x * sc, a->y * sc);
-    }
-}
-
-__device__ inline void mv_atomic_max_nonneg(double* addr, double v) {
-    atomicMax(reinterpret_cast<unsigned long long*>(addr), (unsigned long long)__double_as_longlong(v));
-}
-
 // ---- predict / update of the Wilson iteration, second generation ------------------------------------------------
 // The first version (LU with partial pivoting on an LDS-resident matrix pair, three LDS accesses per complex FMA) was 3.2 ms
 // per launch for 1792 problems of 64 x 64: LDS-bandwidth bound at 3 % of the fp64 rate.  m_predict_gj keeps the WHOLE
@@ -341,8 +292,8 @@ __device__ __forceinline__ void mv_gj_eliminate(cd (&g)[Q][Q], cd (&s)[Q][Q], cd
                     if (ty + 16 * a == pr) {
 #pragma unroll
                         for (int b = 0; b < Q; ++b) {
-                            g[a][b] = m_mul(g[a][b], inv);
-                            s[a][b] = m_mul(s[a][b], inv);
+                            g[a][b] = zmul(g[a][b], inv);
+                            s[a][b] = zmul(s[a][b], inv);
                             rowbuf[tx + 16 * b] = g[a][b];
                             rowbuf[CP + tx + 16 * b] = s[a][b];
                         }
@@ -410,7 +361,7 @@ __global__ void __launch_bounds__(256, 2) m_predict_gj(const cd* __restrict__ S,
     // ---- pass 2: the same elimination as column operations on Y' (held in s) ----
     for (int k = 0; k < C; ++k) {
         const int pr = prow[k];
-        const cd cinv = m_conj(pinv[k]);
+        const cd cinv = zconj(pinv[k]);
         cd* cb = colbuf + (k & 1) * CP;
         if (tx == (pr & 15)) {
 #pragma unroll
@@ -418,7 +369,7 @@ __global__ void __launch_bounds__(256, 2) m_predict_gj(const cd* __restrict__ S,
                 if (tx + 16 * b == pr) {
 #pragma unroll
                     for (int a = 0; a < Q; ++a) {
-                        s[a][b] = m_mul(s[a][b], cinv);
+                        s[a][b] = zmul(s[a][b], cinv);
                         cb[ty + 16 * a] = s[a][b];
                     }
                 }
@@ -555,7 +506,7 @@ __global__ void __launch_bounds__(256) m_update_mfma(cd* __restrict__ G, const c
     __syncthreads();
     if (tid == 0) {
         const double e4 = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-        if (e4 > 0.0) mv_atomic_max_nonneg(err + p, e4);
+        if (e4 > 0.0) atomic_max_nonneg(err + p, e4);
     }
 }
 
@@ -645,7 +596,7 @@ __global__ void __launch_bounds__(512) m_inverse_inplace(MvMat M, const double* 
                     if (ty + TY * a == pr) {
 #pragma unroll
                         for (int b = 0; b < Q; ++b) {
-                            g[a][b] = (b == kb && tx == kx) ? inv : m_mul(g[a][b], inv);
+                            g[a][b] = (b == kb && tx == kx) ? inv : zmul(g[a][b], inv);
                             rowbuf[tx + 16 * b] = g[a][b];
                         }
                         used |= 1u << a;
@@ -780,11 +731,11 @@ __global__ void __launch_bounds__(64 * Q) m_inverse_mfma(MvMat M, const double* 
                     const cd inv = make_double2(piv.x * d, -piv.y * d);
                     if (pr_row == pr) {
 #pragma unroll
-                        for (int c = 0; c < 4; ++c) pe[c] = (pg == jg && c == jj) ? inv : m_mul(w[c], inv);
+                        for (int c = 0; c < 4; ++c) pe[c] = (pg == jg && c == jj) ? inv : zmul(w[c], inv);
                         used = true;
                         if (pg == 0) { prow[16 * kb + j] = pr; pos[pr] = 16 * kb + j; ppos[pr] = j; }
                     } else {
-                        const cd l = m_mul(m, inv);
+                        const cd l = zmul(m, inv);
 #pragma unroll
                         for (int c = 0; c < 4; ++c) {
                             if (pg == jg && c == jj) { pe[c] = make_double2(-l.x, -l.y); continue; }
@@ -934,7 +885,7 @@ __global__ void __launch_bounds__(1024) m_inverse_global(MvMat M, const double* 
                         const cd inv = make_double2(piv.x / pden, -piv.y / pden);
 #pragma unroll
                         for (int c = 0; c < 4; ++c) {
-                            pe[c] = (pq == jq && c == jj) ? inv : m_mul(pe[c], inv);
+                            pe[c] = (pq == jq && c == jj) ? inv : zmul(pe[c], inv);
                             rowbuf[4 * pq + c] = pe[c];
                         }
                         row_used = true;
@@ -1087,7 +1038,7 @@ __global__ void __launch_bounds__(512) m_gemm_mfma(MvMat X, MvMat Y, MvMat O, co
         for (int u = 0; u < NU; ++u) {
             const int idx = tid + 512 * u;
             Xs[(idx >> 4) * LSX + (idx & 15)] = rx[u];
-            if constexpr (BH) Ys[(idx & 15) * LSY + (idx >> 4)] = m_conj(ry[u]);
+            if constexpr (BH) Ys[(idx & 15) * LSY + (idx >> 4)] = zconj(ry[u]);
             else { const int kr = idx / CP; Ys[kr * LSY + (idx - kr * CP)] = ry[u]; }
         }
     };
@@ -1143,7 +1094,7 @@ __global__ void __launch_bounds__(512) m_gemm_mfma(MvMat X, MvMat Y, MvMat O, co
                         emax = fmax(emax, hypot(v.x - old.x, v.y - old.y));
                     }
                     ob[(int64_t)(i * C + j) * O.se] = v;
-                    if (HERM && (!diag || tj > wrow)) ob[(int64_t)(j * C + i) * O.se] = m_conj(v);
+                    if (HERM && (!diag || tj > wrow)) ob[(int64_t)(j * C + i) * O.se] = zconj(v);
                 }
             }
         }
@@ -1157,7 +1108,7 @@ __global__ void __launch_bounds__(512) m_gemm_mfma(MvMat X, MvMat Y, MvMat O, co
             double e8 = red[0];
 #pragma unroll
             for (int q = 1; q < 8; ++q) e8 = fmax(e8, red[q]);
-            if (e8 > 0.0) mv_atomic_max_nonneg(err + p, e8);
+            if (e8 > 0.0) atomic_max_nonneg(err + p, e8);
         }
     }
 }
@@ -1194,17 +1145,6 @@ __global__ void __launch_bounds__(256) m_sumsq(const cd* __restrict__ H, double*
         __syncthreads();
     }
     if (threadIdx.x == 0) sq[b] = red[0];
-}
-
-__global__ void m_flags(int32_t* status, int32_t* n_iter, double* err, double tol, int64_t P, int32_t* n_running) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P) return;
-    if (status[p] == 0) {
-        n_iter[p] += 1;
-        if (err[p] < tol) status[p] = 1;
-        else atomicAdd(n_running, 1);
-    }
-    err[p] = 0.0;
 }
 
 // ---- measures -----------------------------------------------------------------------------------
@@ -1367,18 +1307,6 @@ __global__ void m_measure(const cd* H, const cd* Amv, const double* sigma, const
 }
 
 // ---- host side ------------------------------------------------------------------------------------
-#define MV_CHECK_FFT(expr)                                                                       \
-    do {                                                                                         \
-        rocfft_status s_ = (expr);                                                               \
-        if (s_ != rocfft_status_success) {                                                       \
-            sc_set_error("%s failed: rocfft_status %d (%s:%d)", #expr, (int)s_, __FILE__, __LINE__); \
-            rc = SC_EFFT; goto done;                                                             \
-        }                                                                                        \
-    } while (0)
-
-#define MV_HIST 1024          // iterations whose "still running" counts the workspace logs (max_iterations <= this)
-#define MV_POLL 4             // iterations queued between two looks at the counts
-
 static size_t mv_gj_lds(int Q) {
     const size_t CP = 16 * (size_t)Q;
     return (CP * CP + 2 * CP + 2 * CP + CP) * sizeof(cd) + 2 * CP * sizeof(unsigned) + 2 * CP * sizeof(int) + 64;
@@ -1513,7 +1441,7 @@ extern "C" int sc_mvar_workspace_bytes(int64_t n_groups, int64_t C, int64_t N, s
     const size_t E = (size_t)C * C, P = (size_t)n_groups, F = (size_t)N / 2 + 1;
     // factor: S, G, A series (beyond 64 signals also G^-1 and G^-1 S); measures: H, A_mvar natural + small per-window arrays
     const size_t n_big = C > mv_small_max() ? 5 : 3;
-    const size_t factor = n_big * P * E * (size_t)N * sizeof(cd) + P * 16 + P * E * 8 + 128 + (size_t)MV_HIST * 4;
+    const size_t factor = n_big * P * E * (size_t)N * sizeof(cd) + P * 16 + P * E * 8 + 128 + (size_t)WILSON_HIST * 4;
     // (beyond 128 signals: + the scratch of the blocked inverse, which also parks |H|^2 / |A|^2 for m_measure)
     // (sq: one partial sum per (window, bin) and, before that, per (window, 256-element chunk of the matrix))
     const size_t n_sq = (F > 16 ? F : 16) > (E + 255) / 256 ? (F > 16 ? F : 16) : (E + 255) / 256;
@@ -1556,136 +1484,82 @@ extern "C" int sc_mvar_factor_f64(const void* d_accum, const void* d_S, int64_t 
     }
     double* err = (double*)w; w += (size_t)P * 8;
     double* g0 = (double*)w; w += (size_t)P * E * 8;
-    int32_t* n_fallback = (int32_t*)w; w += 64;
-    int32_t* n_running = (int32_t*)w;
+    int32_t* n_fallback = (int32_t*)w;          // 64 bytes, then the [WILSON_HIST] slots of the still-running counts
     const dim3 gridE((unsigned)((N + 255) / 256), (unsigned)(E < MV_GRID_Y ? E : MV_GRID_Y), (unsigned)P);
     const bool huge = C > MV_CMID;
     if (d_accum) {
-        SC_REQUIRE(planes & SC_PLANE_CSM, "accumulator record must contain SC_PLANE_CSM");
-        SC_REQUIRE(n_freq_accum == N || n_freq_accum == N / 2 + 1, "accumulators must hold N or N/2+1 bins");
-        MvDims d;
-        d.P = P; d.N = N; d.F = n_freq_accum; d.C = (int)C;
-        d.NB = sc_n_blocks(C); d.n_tiles = sc_n_tiles(d.NB);
-        d.p_csm = sc_plane_offset(planes, SC_PLANE_CSM);
-        d.two_sided = (n_freq_accum == N && N > 1) ? 1 : 0;
-        d.floats_per_bin = (int64_t)sc_plane_count(planes) * d.n_tiles * SC_TILE_ELEMS;
-        d.n_obs = (double)n_obs;
-        hipLaunchKernelGGL(m_build, gridE, dim3(256), 0, st, sc_rec(d_accum, planes), d, S, big ? (int64_t)E : (int64_t)1,
+        ScCsmView v;
+        const int rcv = sc_csm_view(planes, n_freq_accum, N, C, n_obs, &v);
+        if (rcv != SC_OK) return rcv;
+        hipLaunchKernelGGL(m_build, gridE, dim3(256), 0, st, sc_rec(d_accum, planes), v, (int)C, S, big ? (int64_t)E : (int64_t)1,
                            big ? (int64_t)1 : N);
     } else if (big) {
         SC_CHECK_HIP(hipMemcpyAsync(S, d_S, (size_t)P * E * N * sizeof(cd), hipMemcpyDeviceToDevice, st));
     } else {
         hipLaunchKernelGGL(m_to_series, gridE, dim3(256), 0, st, (const cd*)d_S, S, N, E);
     }
-    int rc = SC_OK;
-    rocfft_plan fwd = nullptr, inv = nullptr;
-    bool fwd_cached = false, inv_cached = false;
-    rocfft_execution_info info = nullptr;
-    void* fft_work = nullptr;
-    size_t ws_f = 0, ws_i = 0;
-    static int rocfft_ready = 0;
-    if (!rocfft_ready) { rocfft_setup(); rocfft_ready = 1; }
+    int rc;
+    WilsonFft fft;
     const dim3 gridB((unsigned)N, (unsigned)P);
-    int iters = 0, running = (int)P, queued = 0;
-    int32_t hist[MV_POLL];
     const bool fused = sc_internal_causal_fft_supported(N);
     // Beyond 64 signals A crosses the transform in the layout of the products around it where the transform has the loads for it
     const bool natA = big && fused && sc_internal_causal_fft_natural_supported(N);
     const MvMat Adesc = natA ? mv_natural(A, N, E) : mv_series(A, N, E);
     const int Q = (int)((C + 15) / 16);
-    if (max_iter > MV_HIST) {
-        sc_set_error("max_iterations = %d exceeds the %d iterations the workspace can log", max_iter, MV_HIST);
-        return SC_EINVAL;
-    }
-    if (!fused) {
-        if ((rc = sc_internal_z2z_plan(&fwd, 1, (size_t)N, (size_t)E * P, &fwd_cached)) != SC_OK) goto done;
-        if ((rc = sc_internal_z2z_plan(&inv, 0, (size_t)N, (size_t)E * P, &inv_cached)) != SC_OK) goto done;
-        MV_CHECK_FFT(rocfft_plan_get_work_buffer_size(fwd, &ws_f));
-        MV_CHECK_FFT(rocfft_plan_get_work_buffer_size(inv, &ws_i));
-        MV_CHECK_FFT(rocfft_execution_info_create(&info));
-        if (ws_f < ws_i) ws_f = ws_i;
-        if (ws_f) {
-            if (hipMallocAsync(&fft_work, ws_f, st) != hipSuccess) { sc_set_error("rocFFT work buffer alloc failed"); rc = SC_ENOMEM; goto done; }
-            MV_CHECK_FFT(rocfft_execution_info_set_work_buffer(info, fft_work, ws_f));
-        }
-        MV_CHECK_FFT(rocfft_execution_info_set_stream(info, st));
-    }
-    (void)hipMemsetAsync(err, 0, (size_t)P * 8, st);
-    (void)hipMemsetAsync(d_n_iter, 0, (size_t)P * 4, st);
-    (void)hipMemsetAsync(n_fallback, 0, 64 + (size_t)MV_HIST * 4, st);
-    // G0 = chol(Re ifft_n(S)[lag 0])^H broadcast over the bins (minimum_phase_decomposition.py:48-77)
-    if (big) hipLaunchKernelGGL(m_lag0_nat, dim3((unsigned)((E + 255) / 256), (unsigned)P), dim3(256), 0, st, S, g0, N, E);
-    else hipLaunchKernelGGL(m_lag0, dim3((unsigned)(((int64_t)P * E + 3) / 4)), dim3(256), 0, st, S, g0, N, (int64_t)P * E);
-    if (!huge) SC_CHECK_HIP(hipFuncSetAttribute((const void*)m_chol, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)E * 8)));
-    hipLaunchKernelGGL(m_chol, dim3((unsigned)P), dim3(256), huge ? (size_t)0 : (size_t)E * 8, st, g0, d_status, n_fallback, (int)C,
-                       huge ? 1 : 0);
-    hipLaunchKernelGGL(m_restart_all, dim3(64), dim3(256), 0, st, g0, n_fallback, (int64_t)P, (int)C);
-    hipLaunchKernelGGL(m_restart_count, dim3(1), dim3(1), 0, st, n_fallback, (int32_t)P);
-    if (big) hipLaunchKernelGGL(m_fill_nat, dim3((unsigned)((E + 255) / 256), (unsigned)N, (unsigned)P), dim3(256), 0, st, g0, G, N, E);
-    else hipLaunchKernelGGL(m_fill, gridE, dim3(256), 0, st, g0, G, N, E);
-    // The stream is synchronised once per MV_POLL iterations: every iteration logs how many windows are still running
-    // into its own slot; converged windows are skipped by every kernel, so the iterations queued past the last
-    // convergence are empty launches.
-    while (queued < max_iter && running > 0) {
-        const int first = queued;
-        for (int b = 0; b < MV_POLL && queued < max_iter; ++b, ++queued) {
-            void* bufs[1] = {A};
+    if (max_iter <= WILSON_HIST && !fused && (rc = fft.init((size_t)N, (size_t)E * P, st)) != SC_OK) return rc;
+    const WilsonCounters c = {err, d_n_iter, d_status, n_fallback, 64};
+    const WilsonLoopResult r = wilson_loop(c, P, tol, max_iter, st,
+        [&]() -> int {
+            // G0 = chol(Re ifft_n(S)[lag 0])^H broadcast over the bins (minimum_phase_decomposition.py:48-77)
+            if (big) hipLaunchKernelGGL(m_lag0_nat, dim3((unsigned)((E + 255) / 256), (unsigned)P), dim3(256), 0, st, S, g0, N, E);
+            else hipLaunchKernelGGL(m_lag0, dim3((unsigned)(((int64_t)P * E + 3) / 4)), dim3(256), 0, st, S, g0, N, (int64_t)P * E);
+            if (!huge) SC_CHECK_HIP(hipFuncSetAttribute((const void*)m_chol, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)E * 8)));
+            hipLaunchKernelGGL(m_chol, dim3((unsigned)P), dim3(256), huge ? (size_t)0 : (size_t)E * 8, st, g0, d_status, n_fallback, (int)C,
+                               huge ? 1 : 0);
+            hipLaunchKernelGGL(m_restart_all, dim3(64), dim3(256), 0, st, g0, n_fallback, (int64_t)P, (int)C);
+            hipLaunchKernelGGL(m_restart_count, dim3(1), dim3(1), 0, st, n_fallback, (int32_t)P);
+            if (big) hipLaunchKernelGGL(m_fill_nat, dim3((unsigned)((E + 255) / 256), (unsigned)N, (unsigned)P), dim3(256), 0, st, g0, G, N, E);
+            else hipLaunchKernelGGL(m_fill, gridE, dim3(256), 0, st, g0, G, N, E);
+            return (int)SC_OK;
+        },
+        [&]() -> int {
+            int rcs;
             if (big) {          // A = G^-1 S G^-H + I: explicit inverse, two matrix-core products
                 // (G, S, G^-1 and G^-1 S in the natural layout [p][n][e]: coalesced; only A crosses the transform as series)
                 // (beyond 128 signals T doubles as the scratch of the inverse: it is written only by the product after it)
-                if ((rc = mv_launch_inverse_big(C, gridB, st, mv_natural(G, N, E), nullptr, mv_natural(Ginv, N, E), d_status, T)) != SC_OK) goto done;
-                if ((rc = mv_launch_gemm(C, MV_GEMM_PLAIN, gridB, st, mv_natural(Ginv, N, E), mv_natural(S, N, E),
-                                         mv_natural(T, N, E), d_status, nullptr)) != SC_OK) goto done;
-                if ((rc = mv_launch_gemm(C, MV_GEMM_BH_I, gridB, st, mv_natural(T, N, E), mv_natural(Ginv, N, E),
-                                         Adesc, d_status, nullptr)) != SC_OK) goto done;
-            } else if ((rc = mv_launch_predict(Q, gridB, st, S, G, d_status, A, N, (int)C)) != SC_OK) goto done;
-            if (fused) {        // ifft -> causal mask -> fft in one kernel (sc_wilson_fft.hip)
-                if ((rc = natA ? sc_internal_causal_fft_pair_natural(A, d_status, P, (int)C, N, st)
-                               : sc_internal_causal_fft_pair(A, d_status, P, (int)C, N, st)) != SC_OK) goto done;
-            } else {
-                MV_CHECK_FFT(rocfft_execute(inv, bufs, nullptr, info));
-                hipLaunchKernelGGL(m_causal, gridE, dim3(256), 0, st, A, N, (int)C);
-                MV_CHECK_FFT(rocfft_execute(fwd, bufs, nullptr, info));
-            }
+                if ((rcs = mv_launch_inverse_big(C, gridB, st, mv_natural(G, N, E), nullptr, mv_natural(Ginv, N, E), d_status, T)) != SC_OK) return rcs;
+                if ((rcs = mv_launch_gemm(C, MV_GEMM_PLAIN, gridB, st, mv_natural(Ginv, N, E), mv_natural(S, N, E),
+                                          mv_natural(T, N, E), d_status, nullptr)) != SC_OK) return rcs;
+                if ((rcs = mv_launch_gemm(C, MV_GEMM_BH_I, gridB, st, mv_natural(T, N, E), mv_natural(Ginv, N, E),
+                                          Adesc, d_status, nullptr)) != SC_OK) return rcs;
+            } else if ((rcs = mv_launch_predict(Q, gridB, st, S, G, d_status, A, N, (int)C)) != SC_OK) return rcs;
+            // ifft -> causal mask -> fft: one kernel (sc_wilson_fft.hip) where the length has one
+            rcs = !fused ? fft.causal<false>(A, N, (int)C, P, gridE)
+                         : natA ? sc_internal_causal_fft_pair_natural(A, d_status, P, (int)C, N, st)
+                                : sc_internal_causal_fft_pair(A, d_status, P, (int)C, N, st);
+            if (rcs != SC_OK) return rcs;
             if (huge) {         // the blocked product cannot run in place: G A+ into T (frozen windows copied), then swap
-                if ((rc = mv_launch_gemm(C, MV_GEMM_ERR, gridB, st, mv_natural(G, N, E), Adesc, mv_natural(T, N, E),
-                                         d_status, err)) != SC_OK) goto done;
+                if ((rcs = mv_launch_gemm(C, MV_GEMM_ERR, gridB, st, mv_natural(G, N, E), Adesc, mv_natural(T, N, E),
+                                          d_status, err)) != SC_OK) return rcs;
                 cd* t = G; G = T; T = t;
-            } else if (big) {
-                if ((rc = mv_launch_gemm(C, MV_GEMM_ERR, gridB, st, mv_natural(G, N, E), Adesc, mv_natural(G, N, E),
-                                         d_status, err)) != SC_OK) goto done;
-            } else if ((rc = mv_launch_update(Q, gridB, st, G, A, d_status, err, N, (int)C)) != SC_OK) goto done;
-            hipLaunchKernelGGL(m_flags, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, d_status, d_n_iter, err, tol, P,
-                               n_running + queued);
-        }
-        if (hipMemcpyAsync(hist, n_running + first, (size_t)(queued - first) * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) {
-            sc_set_error("Wilson iterations %d..%d: %s", first, queued, hipGetErrorString(hipGetLastError()));
-            rc = SC_EHIP; goto done;
-        }
-        for (int b = 0; b < queued - first; ++b) {
-            running = hist[b];
-            iters = first + b + 1;
-            if (running == 0) break;
-        }
-    }
+                return (int)SC_OK;
+            }
+            if (big) return mv_launch_gemm(C, MV_GEMM_ERR, gridB, st, mv_natural(G, N, E), Adesc, mv_natural(G, N, E), d_status, err);
+            return mv_launch_update(Q, gridB, st, G, A, d_status, err, N, (int)C);
+        });
+    if (r.rc != SC_OK) return r.rc;
     if (big) (void)hipMemcpyAsync(d_G, G, (size_t)P * E * N * sizeof(cd), hipMemcpyDeviceToDevice, st);
     else hipLaunchKernelGGL(m_to_natural, gridE, dim3(256), 0, st, G, (cd*)d_G, N, E);
     if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
         sc_set_error("Wilson factor copy-out failed: %s", hipGetErrorString(hipGetLastError()));
-        rc = SC_EHIP; goto done;
+        return SC_EHIP;
     }
     if (h_summary) {
         int fb = 0;
         (void)hipMemcpy(&fb, n_fallback, 4, hipMemcpyDeviceToHost);      // the stream was synchronised just above
-        h_summary[0] = iters; h_summary[1] = running; h_summary[2] = fb;
+        h_summary[0] = r.iters; h_summary[1] = r.running; h_summary[2] = fb;
     }
-done:
-    if (info) rocfft_execution_info_destroy(info);
-    if (fwd && !fwd_cached) rocfft_plan_destroy(fwd);       // (cached plans live as long as the process: sc_internal_z2z_plan)
-    if (inv && !inv_cached) rocfft_plan_destroy(inv);
-    if (fft_work) (void)hipFreeAsync(fft_work, st);
-    return rc;
+    return SC_OK;
 }
 
 // d_G [P][N][C][C] complex128 -> the requested quantity.

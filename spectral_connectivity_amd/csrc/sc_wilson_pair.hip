@@ -28,15 +28,9 @@
 #include <string.h>
 #include "sc_wilson_fft.h"
 
-__device__ __forceinline__ cd pz_mul(cd a, cd b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ cd pz_conj(cd a) { return make_double2(a.x, -a.y); }
-__device__ __forceinline__ cd pz_add(cd a, cd b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ cd pz_sub(cd a, cd b) { return make_double2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ cd pz_div(cd a, cd b) {
-    const double d = b.x * b.x + b.y * b.y;
-    return make_double2((a.x * b.x + a.y * b.y) / d, (a.y * b.x - a.x * b.y) / d);
-}
-
+// (the record fields are a copy of the entry point's ScCsmView, and pair_read_S below is this file's own reader, on purpose: the
+//  kernels run at the register limit of one wave per SIMD, and sc_csm_entry in their place -- its diagonal test, the view's layout --
+//  moves their scalar registers and the scratch of the 2400-sample form)
 struct PairArgs {
     ScRec accum;
     const int32_t* pairs;
@@ -78,18 +72,18 @@ __device__ __forceinline__ void pair_read_S(const PairArgs& a, int64_t g, int ci
 // the Hermitian structure of A used -- a00, a11 are real (only their real parts are formed), a10 = conj(a01) is not computed at
 // all: A[0] = (a00, 0), A[1] = a01, A[2] = a11 as (a11, 0).
 __device__ __forceinline__ void pair_predict(const cd (&g)[4], const double (&sv)[4], cd (&A)[3]) {
-    const cd s01 = make_double2(sv[2], sv[3]), s10 = pz_conj(s01);
-    const cd det = pz_sub(pz_mul(g[0], g[3]), pz_mul(g[1], g[2]));
+    const cd s01 = make_double2(sv[2], sv[3]), s10 = zconj(s01);
+    const cd det = zsub(zmul(g[0], g[3]), zmul(g[1], g[2]));
     const double rd = 1.0 / (det.x * det.x + det.y * det.y);
     const cd idet = make_double2(det.x * rd, -det.y * rd);
-    const cd i00 = pz_mul(g[3], idet), i01 = pz_mul(make_double2(-g[1].x, -g[1].y), idet);
-    const cd i10 = pz_mul(make_double2(-g[2].x, -g[2].y), idet), i11 = pz_mul(g[0], idet);
+    const cd i00 = zmul(g[3], idet), i01 = zmul(make_double2(-g[1].x, -g[1].y), idet);
+    const cd i10 = zmul(make_double2(-g[2].x, -g[2].y), idet), i11 = zmul(g[0], idet);
     // X = G^-1 S (s00, s11 real)
-    const cd x00 = pz_add(make_double2(i00.x * sv[0], i00.y * sv[0]), pz_mul(i01, s10)), x01 = pz_add(pz_mul(i00, s01), make_double2(i01.x * sv[1], i01.y * sv[1]));
-    const cd x10 = pz_add(make_double2(i10.x * sv[0], i10.y * sv[0]), pz_mul(i11, s10)), x11 = pz_add(pz_mul(i10, s01), make_double2(i11.x * sv[1], i11.y * sv[1]));
+    const cd x00 = zadd(make_double2(i00.x * sv[0], i00.y * sv[0]), zmul(i01, s10)), x01 = zadd(zmul(i00, s01), make_double2(i01.x * sv[1], i01.y * sv[1]));
+    const cd x10 = zadd(make_double2(i10.x * sv[0], i10.y * sv[0]), zmul(i11, s10)), x11 = zadd(zmul(i10, s01), make_double2(i11.x * sv[1], i11.y * sv[1]));
     // A = G^-1 X^H + I
     A[0] = make_double2(i00.x * x00.x + i00.y * x00.y + i01.x * x01.x + i01.y * x01.y + 1.0, 0.0);
-    A[1] = pz_add(pz_mul(i00, pz_conj(x10)), pz_mul(i01, pz_conj(x11)));
+    A[1] = zadd(zmul(i00, zconj(x10)), zmul(i01, zconj(x11)));
     A[2] = make_double2(i10.x * x10.x + i10.y * x10.y + i11.x * x11.x + i11.y * x11.y + 1.0, 0.0);
 }
 
@@ -116,11 +110,8 @@ __global__ void __launch_bounds__(256) pair_lag0_kernel(PairArgs a, int64_t N) {
     }
     if (threadIdx.x == 0) {
         const double r00 = red[0][0] / (double)N, r11 = red[1][0] / (double)N, r01 = red[2][0] / (double)N;
-        double l00 = sqrt(r00), l10 = r01 / l00;
-        const double t = r11 - l10 * l10;
-        double l11 = sqrt(t);
-        const bool bad = !(r00 > 0.0) || !(t > 0.0);
-        if (bad) { l00 = 1.0; l10 = 0.0; l11 = 1.0; atomicOr(a.batch_bad + p % a.n_batch, 1); }
+        double l00, l10, l11;
+        sc_lag0_cholesky2(r00, r11, r01, l00, l10, l11, a.batch_bad + p % a.n_batch);
         a.chol[p * 4] = l00; a.chol[p * 4 + 1] = l10; a.chol[p * 4 + 2] = l11;
     }
 }
@@ -261,11 +252,11 @@ __global__ void __launch_bounds__(256 * HALVES, HALVES) wilson_pair_kernel(PairA
             Ap[2] = make_double2(0.5 * (p2.y + m2.y), 0.5 * (m2.x - p2.x));
             if (!done) {
                 cd n[4];
-                n[0] = pz_add(pz_mul(g[0], Ap[0]), pz_mul(g[1], Ap[2])); n[1] = pz_add(pz_mul(g[0], Ap[1]), pz_mul(g[1], Ap[3]));
-                n[2] = pz_add(pz_mul(g[2], Ap[0]), pz_mul(g[3], Ap[2])); n[3] = pz_add(pz_mul(g[2], Ap[1]), pz_mul(g[3], Ap[3]));
+                n[0] = zadd(zmul(g[0], Ap[0]), zmul(g[1], Ap[2])); n[1] = zadd(zmul(g[0], Ap[1]), zmul(g[1], Ap[3]));
+                n[2] = zadd(zmul(g[2], Ap[0]), zmul(g[3], Ap[2])); n[3] = zadd(zmul(g[2], Ap[1]), zmul(g[3], Ap[3]));
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const cd d = pz_sub(n[k], g[k]);
+                    const cd d = zsub(n[k], g[k]);
                     e2 = fmax(e2, d.x * d.x + d.y * d.y);          // (the square root is taken once, of the maximum)
                     g[k] = n[k];
                 }
@@ -578,11 +569,11 @@ __global__ void __launch_bounds__(TB) wilson_pair_mixed_kernel(PairArgs a) {
             Ap[2] = make_double2(0.5 * (p2.y + m2.y), 0.5 * (m2.x - p2.x));
             if (!done) {
                 cd n[4];
-                n[0] = pz_add(pz_mul(g[0], Ap[0]), pz_mul(g[1], Ap[2])); n[1] = pz_add(pz_mul(g[0], Ap[1]), pz_mul(g[1], Ap[3]));
-                n[2] = pz_add(pz_mul(g[2], Ap[0]), pz_mul(g[3], Ap[2])); n[3] = pz_add(pz_mul(g[2], Ap[1]), pz_mul(g[3], Ap[3]));
+                n[0] = zadd(zmul(g[0], Ap[0]), zmul(g[1], Ap[2])); n[1] = zadd(zmul(g[0], Ap[1]), zmul(g[1], Ap[3]));
+                n[2] = zadd(zmul(g[2], Ap[0]), zmul(g[3], Ap[2])); n[3] = zadd(zmul(g[2], Ap[1]), zmul(g[3], Ap[3]));
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const cd d = pz_sub(n[k], g[k]);
+                    const cd d = zsub(n[k], g[k]);
                     e2 = fmax(e2, d.x * d.x + d.y * d.y);
                     g[k] = n[k];
                 }
@@ -667,67 +658,6 @@ static bool pair_mixed_has(int64_t N) {
     return false;
 }
 
-// lam = 1e-12 * mean over (windows, entries) of H0^2 per pair, Hinv = (H0 + lam I)^-1, rot from Sigma = H0 H0^T
-// (connectivity.py:1739-1742, :1847-1848; the arithmetic of sc_wilson.hip's k_pair_consts)
-__global__ void pair_consts_kernel(const double* h0, double* hinv, double* rot, int64_t n_groups, int64_t n_pairs) {
-    const int64_t pr = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (pr >= n_pairs) return;
-    double m = 0.0;
-    int64_t n_ok = 0;
-    for (int64_t g = 0; g < n_groups; ++g) {
-        const double* hh = h0 + (g * n_pairs + pr) * 4;
-        const double q = hh[0] * hh[0] + hh[1] * hh[1] + hh[2] * hh[2] + hh[3] * hh[3];
-        if (isfinite(q)) { m += q; ++n_ok; }
-    }
-    const double lam = n_ok ? 1e-12 * m / (double)(4 * n_ok) : 0.0;
-    for (int64_t g = 0; g < n_groups; ++g) {
-        const int64_t p = g * n_pairs + pr;
-        const double a = h0[p * 4], b = h0[p * 4 + 1], c = h0[p * 4 + 2], d = h0[p * 4 + 3];
-        const double ra = a + lam, rd = d + lam, det = ra * rd - b * c;
-        hinv[p * 4] = rd / det; hinv[p * 4 + 1] = -b / det; hinv[p * 4 + 2] = -c / det; hinv[p * 4 + 3] = ra / det;
-        const double s00 = a * a + b * b, s01 = a * c + b * d, s11 = c * c + d * d;
-        rot[p * 4] = s00 - s00 * s00 / s00; rot[p * 4 + 1] = s11 - s01 * s01 / s00;
-        rot[p * 4 + 2] = s00 - s01 * s01 / s11; rot[p * 4 + 3] = s11 - s11 * s11 / s11;
-    }
-}
-
-__global__ void pair_fill_nan_kernel(double* out, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < total) out[i] = nan("");
-}
-
-// GP = log P - log(P - rot |H|^2), H = G Hinv (connectivity.py:1679-1779, :1825-1848) on the non-negative bins
-__global__ void pair_granger_kernel(PairArgs a, const double* hinv, const double* rot, int64_t F, double* out) {
-    const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t p = (int64_t)blockIdx.z * 65535 + blockIdx.y;
-    if (f >= F || p >= a.P) return;
-    const int64_t g = p / a.n_pairs, pr = p % a.n_pairs;
-    const int ci = a.pairs[2 * pr], cj = a.pairs[2 * pr + 1];
-    const int idx[2] = {ci, cj};
-    double* o = out + ((g * F + f) * a.C) * a.C;
-    const cd* Gp = a.Ghalf + p * 4 * F;
-    const cd gg[4] = {Gp[f], Gp[F + f], Gp[2 * F + f], Gp[3 * F + f]};
-    const double* hi = hinv + p * 4;
-    cd Hm[4];
-    Hm[0] = make_double2(gg[0].x * hi[0] + gg[1].x * hi[2], gg[0].y * hi[0] + gg[1].y * hi[2]);
-    Hm[1] = make_double2(gg[0].x * hi[1] + gg[1].x * hi[3], gg[0].y * hi[1] + gg[1].y * hi[3]);
-    Hm[2] = make_double2(gg[2].x * hi[0] + gg[3].x * hi[2], gg[2].y * hi[0] + gg[3].y * hi[2]);
-    Hm[3] = make_double2(gg[2].x * hi[1] + gg[3].x * hi[3], gg[2].y * hi[1] + gg[3].y * hi[3]);
-    double s[4];
-    pair_read_S(a, g, ci, cj, F, (int)f, s);
-    const double tp[2] = {s[0], s[1]};               // total power of the two channels
-    for (int x = 0; x < 2; ++x)
-        for (int y = 0; y < 2; ++y) {
-            if (x == y) continue;                    // diagonal is NaN (connectivity.py:2337-2339)
-            const cd hh = Hm[x * 2 + y];
-            double intrinsic = tp[x] - rot[p * 4 + x * 2 + y] * (hh.x * hh.x + hh.y * hh.y);
-            if (intrinsic == 0.0) intrinsic = 2.220446049250313e-16;
-            double gp = log(tp[x]) - log(intrinsic);
-            if (!(gp > 0.0)) gp = nan("");
-            o[(int64_t)idx[x] * a.C + idx[y]] = gp;
-        }
-}
-
 template <int LOG2N>
 static int pair_launch(const PairArgs& a, hipStream_t st) {
     constexpr int WP_HALVES = LOG2N <= 8 ? 2 : 1;
@@ -753,20 +683,19 @@ bool sc_internal_granger_resident_applies(int64_t n_freq_accum, int64_t N) {
 }
 
 // The resident form of sc_granger_pairwise_f64 (same arguments; called from there when it applies).
-int sc_internal_granger_resident(const void* d_accum, int64_t n_groups, int64_t N, int64_t C, uint32_t planes, int64_t n_obs,
+int sc_internal_granger_resident(const void* d_accum, int64_t n_groups, const ScCsmView& v, int64_t C, uint32_t planes,
                                  const int32_t* d_pairs, int64_t n_pairs, double tol, int max_iter, void* d_work, size_t work_bytes,
                                  int keep_output, double* d_out, int32_t* d_n_iter, int32_t* d_status, int32_t* h_summary,
                                  hipStream_t st) {
-    const int64_t P = n_groups * n_pairs, F = N / 2 + 1;
+    const int64_t N = v.N, P = n_groups * n_pairs, F = N / 2 + 1;
     SC_REQUIRE(work_bytes >= pair_workspace_bytes(P, n_pairs, N), "workspace too small");
     PairArgs a;
     a.accum = sc_rec(d_accum, planes);
     a.pairs = d_pairs;
     a.P = P; a.n_pairs = n_pairs; a.n_batch = n_pairs;
-    a.C = (int)C; a.NB = sc_n_blocks(C); a.n_tiles = sc_n_tiles(a.NB);
-    a.p_csm = sc_plane_offset(planes, SC_PLANE_CSM);
-    a.floats_per_bin = (int64_t)sc_plane_count(planes) * a.n_tiles * SC_TILE_ELEMS;
-    a.n_obs = (double)n_obs;
+    a.C = (int)C; a.NB = v.NB; a.n_tiles = v.n_tiles; a.p_csm = v.p_csm;
+    a.floats_per_bin = v.floats_per_bin;
+    a.n_obs = v.n_obs;
     char* w = (char*)d_work;
     a.Ghalf = (cd*)w; w += (size_t)P * F * 4 * 16;
     a.chol = (double*)w; w += (size_t)P * 32;
@@ -779,8 +708,7 @@ int sc_internal_granger_resident(const void* d_accum, int64_t n_groups, int64_t 
     a.tol = tol; a.max_iter = max_iter;
     SC_CHECK_HIP(hipMemsetAsync(a.batch_bad, 0, (size_t)n_pairs * 4 + 256, st));          // the flags and the summary behind them
     if (!keep_output)
-        hipLaunchKernelGGL(pair_fill_nan_kernel, dim3((unsigned)((n_groups * F * C * C + 255) / 256)), dim3(256), 0, st, d_out,
-                           n_groups * F * C * C);
+        sc_internal_fill_nan(d_out, n_groups * F * C * C, st);
     hipLaunchKernelGGL(pair_lag0_kernel, dim3((unsigned)P), dim3(256), 0, st, a, N);
     hipLaunchKernelGGL(pair_restart_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, a);
     int rc;
@@ -799,9 +727,7 @@ int sc_internal_granger_resident(const void* d_accum, int64_t n_groups, int64_t 
     default: rc = pair_launch<12>(a, st); break;
     }
     if (rc != SC_OK) return rc;
-    hipLaunchKernelGGL(pair_consts_kernel, dim3((unsigned)((n_pairs + 63) / 64)), dim3(64), 0, st, a.h0, hinv, rot, n_groups, n_pairs);
-    const dim3 gridF((unsigned)((F + 255) / 256), (unsigned)(P < 65535 ? P : 65535), (unsigned)((P + 65534) / 65535));
-    hipLaunchKernelGGL(pair_granger_kernel, gridF, dim3(256), 0, st, a, hinv, rot, F, d_out);
+    sc_internal_granger_epilogue(a.Ghalf, F, a.h0, hinv, rot, a.accum, v, d_pairs, n_groups, n_pairs, C, d_out, st);
     int32_t sum[3] = {0, 0, 0};
     if (hipMemcpyAsync(sum, a.summary, sizeof sum, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
         hipGetLastError() != hipSuccess) {

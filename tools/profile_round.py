@@ -88,8 +88,8 @@ if stage_b in traffic:
                     "measure_epilogue": traffic.get("measure_tile_multi_kernel")}}
     # BASELINE configs[3]: the kernels of the resident pairwise Granger (sc_wilson_pair.hip), summed over the entry point
     f4, w4 = pmc("fetch4.txt", "FETCH_SIZE"), pmc("write4.txt", "WRITE_SIZE")
-    g_rows = [("wilson_pair_kernel", "wilson_pair_kernel"), ("pair_lag0_kernel", "pair_lag0"), ("pair_granger_kernel", "pair_granger"),
-              ("pair_fill_nan_kernel", "pair_fill_nan"), ("pair_consts_kernel", "pair_consts")]
+    g_rows = [("wilson_pair_kernel", "wilson_pair_kernel"), ("pair_lag0_kernel", "pair_lag0"), ("k_granger", "k_granger"),
+              ("fill_nan_kernel", "fill_nan_kernel"), ("k_pair_consts", "k_pair_consts")]
     g_txt, g_total = [], 0.0
     for name, key in g_rows:
         fk, wk = find(f4, key), find(w4, key)
