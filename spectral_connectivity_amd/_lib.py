@@ -574,6 +574,12 @@ PLANES_FORMAT_MAX_CHANNELS = 1024      # F2_MAX_SIGNALS of csrc/sc_fused2.hip
 PLANES_MIN_TYPICAL = 2.5       # SC_PLANES_MIN_TYPICAL of include/sc_hip.h: smallest typical coefficient (scaled units) the format is used for
 
 
+def padded_channels(n_signals, limit):
+    """Channels per row of the float32 engine's spectra: an odd count gets ONE all-zero channel (16-byte aligned rows, even counts for
+    the one-pass stage-B kernels) while that stays within the caller's ``limit`` (PLANES_FORMAT_MAX_CHANNELS, or 256: complex64 only)."""
+    return n_signals + 1 if (n_signals % 2 and n_signals + 1 <= limit) else n_signals
+
+
 def planes_format_applies(n_window, n_fft, n_alloc, planes_hint, spectra_bytes=None):
     """Does stage A write the planes format for a caller that will ask for the accumulator families ``planes_hint``?
     ``spectra_bytes``: size of the complex64 spectra of the request, when the caller knows it.

@@ -176,15 +176,10 @@ class Connectivity:
         """Would the planes-format stage B (sc_fused2.hip) take ``planes`` with this object's expectation type and shape?  Asked
         BEFORE a pending transform picks the device format of the spectra: its observations must form one run of rows (every
         expectation type but "time_tapers" with several trials)."""
-        from ctypes import byref
-        from ._lib import SpectraDesc
+        from . import _stage_abc
         W, R, K, N, C = (int(v) for v in self._shape5)
-        C_alloc = C + 1 if (C % 2 and C + 1 <= _lib.PLANES_FORMAT_MAX_CHANNELS) else C
-        axes = EXPECTATION_AXES[self.expectation_type]
-        d = SpectraDesc(n_freq=N // 2 + 1, n_windows=W, n_trials=R, n_tapers=K, n_signals=C_alloc, stride_freq=W * R * K * C_alloc,
-                        stride_window=R * K * C_alloc, stride_trial=K * C_alloc, stride_taper=C_alloc, reduce_window=int(0 in axes),
-                        reduce_trial=int(1 in axes), reduce_taper=int(2 in axes), reserved=0)
-        return bool(_lib.load().sc_fused2_supported(byref(d), planes))
+        return _stage_abc.planes_request_ok(W, R, K, N, _lib.padded_channels(C, _lib.PLANES_FORMAT_MAX_CHANNELS), self.expectation_type,
+                                            planes)
 
     def _settle(self):
         """Settle what the transform left pending (Multitaper.settle_device_checks: the deferred NaN / infinity warning, the planes

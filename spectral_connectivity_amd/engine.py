@@ -2,21 +2,20 @@
 
 Nothing here computes on the CPU: every function launches HIP kernels / rocFFT through the
 C ABI (include/sc_hip.h) on the current torch stream and returns device tensors.
+
+The call sequences live in _stage_abc.py (stages A to C) and _stage_d.py, once for this host and the torch-free one.  Here is the
+PyTorch host's side of them: the memory adapter ``TorchMemory`` (tensors, the current stream, the plan / twiddle / workspace caches),
+``DeviceSpectra``, and public functions that are one call into a driver plus this host's tensor arithmetic -- the pad-channel copy of
+a device series, ``row_multiple`` / ``have`` around stage B, the tiling of more than 256 signals, partial records, ``GraphedMeasures``.
 """
-import ctypes
-import os
-from ctypes import byref, c_int64, c_void_p
+import collections
+import contextlib
+from ctypes import byref, c_void_p
 
 import numpy as np
 import torch
 
-from . import _lib, _stage_d
-from ._lib import SpectraDesc
-
-# connectivity.py:67-75 of the reference: which of (window, trial, taper) are averaged
-EXPECTATION_AXES = _lib.EXPECTATION_AXES
-
-import collections
+from . import _lib, _stage_abc, _stage_d
 
 _plan_cache = collections.OrderedDict()     # (N, batch, device, f64) -> sc_fft_plan handle, least recently used first
 PLAN_CACHE_SIZE = 4                          # every plan owns a rocFFT work buffer and up to 64 MB of transform scratch
@@ -78,8 +77,8 @@ def clear_plan_cache():
     _plan_cache.clear()
 
 
-class DeviceSpectra:
-    """One-sided (or caller-described) Fourier coefficients resident in HBM.
+class DeviceSpectra(_stage_abc.Spectra):
+    """One-sided (or caller-described) Fourier coefficients resident in HBM (geometry and ``desc``: _stage_abc.Spectra).
 
     ``X`` is a complex64 tensor (float32 engine) or a complex128 tensor (float64 engine, ``f64``: no pad channel,
     every consumer takes the fp64 kernels of sc_f64.hip); ``dims`` = (F, W, R, K, C) logical sizes and ``strides`` =
@@ -94,22 +93,8 @@ class DeviceSpectra:
     CSM / |Im s| accumulation then runs on it directly, and ``X`` is decoded from it on first use by anything else.
     """
 
-    is_device_spectra = True        # (what Connectivity tests for: the torch-free host has a class of its own with the same mark)
-
     def __init__(self, X, dims, strides, n_fft, real_input, C_alloc=None, P=None, scale=None):
-        self._X = X
-        self.P, self.scale = P, scale
-        self.F, self.W, self.R, self.K, self.C = (int(d) for d in dims)
-        self.C_alloc = self.C if C_alloc is None else int(C_alloc)
-        assert self.C_alloc in (self.C, self.C + 1) and -(-self.C_alloc // 16) == -(-self.C // 16)
-        self.strides = tuple(int(s) for s in strides)
-        self.n_fft = int(n_fft)
-        self.real_input = bool(real_input)   # negative bins are conj mirrors of positive ones
-        self.f64 = X is not None and X.dtype == torch.complex128
-        # planes format written by stage A: ``quality`` is a device scalar, min over the channels of (typical sample magnitude x
-        # channel scale); times ``taper_l2_min`` it is the typical coefficient in scaled units, which the caller that owns the series
-        # compares with _lib.PLANES_MIN_TYPICAL (Multitaper.device_spectra does; planes_typical_coefficient() reads it back)
-        self.quality = self.taper_l2_min = None
+        super().__init__(X, dims, strides, n_fft, real_input, C_alloc, P, scale, f64=X is not None and X.dtype == torch.complex128)
         self.device = X.device if X is not None else P.device
 
     def planes_typical_coefficient(self):
@@ -120,12 +105,7 @@ class DeviceSpectra:
     def X(self):
         """The complex64 / complex128 coefficients; decoded from the planes format (lossless up to its 22 bits) on first use."""
         if self._X is None:
-            lib = _lib.load()
-            X = torch.empty((self.F, self.W, self.R, self.K, self.C_alloc), dtype=torch.complex64, device=self.P.device)
-            d = self.desc("trials_tapers", padded=True)
-            _lib.check(lib.sc_spectra_from_planes_f32(_ptr(self.P), byref(d), _ptr(self.scale), _ptr(X), _stream()),
-                       "sc_spectra_from_planes_f32")
-            self._X = X
+            self._X = _stage_abc.decode_planes(TorchMemory(self.device), self)
         return self._X
 
     def coefficients(self):
@@ -145,16 +125,6 @@ class DeviceSpectra:
         return DeviceSpectra(flat, (f1 - f0, self.W, self.R, self.K, self.C), self.strides, self.n_fft,
                              self.real_input, C_alloc=self.C_alloc, P=P, scale=self.scale)
 
-    def desc(self, expectation_type, n_freq=None, padded=False):
-        """Descriptor of the spectra; ``padded``: with the zero pad channel counted as a signal."""
-        axes = EXPECTATION_AXES[expectation_type]
-        sF, sW, sR, sK = self.strides
-        return SpectraDesc(n_freq=self.F if n_freq is None else n_freq, n_windows=self.W,
-                           n_trials=self.R, n_tapers=self.K, n_signals=self.C_alloc if padded else self.C, stride_freq=sF,
-                           stride_window=sW, stride_trial=sR, stride_taper=sK,
-                           reduce_window=int(0 in axes), reduce_trial=int(1 in axes),
-                           reduce_taper=int(2 in axes), reserved=0)
-
 
 def _taper_norms(tapers_over_fs):
     """(max_k sum_n |h_k[n]|, min_k ||h_k||_2): the bound behind the channel scales of the planes format and the size of a typical
@@ -173,151 +143,8 @@ def twiddles(n_fft, device):
     key = (int(n_fft), str(device))
     tw = _twiddle_cache.get(key)
     if tw is None:
-        lib = _lib.load()
-        tw = torch.empty((n_fft,), dtype=torch.complex64, device=device)
-        _lib.check(lib.sc_fft_twiddles_f32(n_fft, _ptr(tw), _stream()), "sc_fft_twiddles_f32")
-        _twiddle_cache[key] = tw
+        tw = _twiddle_cache[key] = _stage_abc.make_twiddles(TorchMemory(device), n_fft)
     return tw
-
-
-PLANES_FORMAT_FAMILIES = _lib.PLANES_FORMAT_FAMILIES
-planes_format_applies = _lib.planes_format_applies
-
-
-def multitaper_spectra(x, tapers_over_fs, n_window, n_step, n_fft, n_windows, detrend_type, mark=None,
-                       use_fused=None, n_signals=None, planes_hint=None):
-    """Stage A on device: (T,R,C) float32 tensor -> DeviceSpectra [F][W][R][K][C].
-
-    ``tapers_over_fs``: (K, L) float32 device tensor = reference tapers^T / fs
-    (folds the sqrt(fs) of transforms.py:1440 and the /fs of transforms.py:1405).
-    ``n_signals``: number of real channels when ``x`` already carries the all-zero pad channel of an odd channel count
-    (appended on the host before the upload, transforms.Multitaper.device_spectra); a device tensor with an odd channel
-    count that arrives unpadded is copied into a padded buffer here (one strided device copy).
-    ``planes_hint``: the accumulator families the caller will ask for.  Any family sc_fused2.hip serves, 44 ... 1024 signals, a
-    window length stage A has the output for (the powers of two 64 ... 4096, the lengths 200 ... 2000 of sc_mtfft_mixed.hip:
-    sc_multitaper_fft_planes_supported) and at least 256 MB of spectra (_lib.planes_format_applies): the spectra are
-    written in the planes format (two f16 pieces per real number) -- a scan of the series for the channel scales, then the same
-    fused transform.  The scan also reports how large a typical coefficient will be in the format's scaled units
-    (``DeviceSpectra.planes_typical_coefficient()``): one scale per channel serves every window, so the format is meant for
-    series without samples hundreds of times the typical amplitude; Multitaper.device_spectra checks against
-    _lib.PLANES_MIN_TYPICAL and re-runs the transform into complex64 otherwise.
-    """
-    lib = _lib.load()
-    T, R, C_real = x.shape
-    if n_signals is not None:
-        assert n_signals in (C_real, C_real - 1)
-        C_real = int(n_signals)
-    elif C_real % 2 and C_real + 1 <= _lib.PLANES_FORMAT_MAX_CHANNELS:
-        padded = torch.zeros((T, R, C_real + 1), dtype=x.dtype, device=x.device)
-        padded[..., :C_real].copy_(x)                # odd channel count: one zero channel (see DeviceSpectra)
-        x = padded
-    T, R, C = x.shape
-    K, L = tapers_over_fs.shape
-    assert L == n_window
-    F = n_fft // 2 + 1
-    strides = (n_windows * R * K * C, R * K * C, K * C, C)
-    if use_fused is None:
-        use_fused = bool(lib.sc_multitaper_fft_supported(L, n_fft))
-    if use_fused and planes_format_applies(L, n_fft, C, planes_hint, spectra_bytes=F * n_windows * R * K * C * 8):
-        row_bytes = int(lib.sc_planes_row_bytes(C))
-        P = torch.empty((F * n_windows * R * K * row_bytes,), dtype=torch.uint8, device=x.device)
-        scale = torch.empty((2 * C,), dtype=torch.float32, device=x.device)
-        work_bytes = int(lib.sc_planes_scales_work_bytes(T * R, C))
-        work = torch.empty((work_bytes,), dtype=torch.uint8, device=x.device)
-        quality = torch.empty((1,), dtype=torch.float32, device=x.device)      # DeviceSpectra.quality, see there
-        abs_sum, l2_min = _taper_norms(tapers_over_fs)
-        _lib.check(lib.sc_planes_scales_quality_f32(_ptr(x), T, R, C, _lib.DETREND[detrend_type], abs_sum, _ptr(scale), _ptr(work),
-                                                    work_bytes, _ptr(quality), _stream()), "sc_planes_scales_quality_f32")
-        _lib.check(lib.sc_multitaper_fft_planes_f32(_ptr(x), T, R, C, L, n_step, n_windows, n_fft, _ptr(tapers_over_fs), K,
-                                                    _lib.DETREND[detrend_type], _ptr(twiddles(n_fft, x.device)), _ptr(scale),
-                                                    _ptr(P), _stream()), "sc_multitaper_fft_planes_f32")
-        if mark:
-            mark("mtfft_fused")
-        sp = DeviceSpectra(None, (F, n_windows, R, K, C_real), strides, n_fft, real_input=True, C_alloc=C, P=P, scale=scale)
-        sp.quality, sp.taper_l2_min = quality, l2_min
-        return sp
-    if use_fused:
-        # one kernel: window + detrend + taper + FFT + transposed store (sc_mtfft.hip)
-        X = torch.empty((F, n_windows, R, K, C), dtype=torch.complex64, device=x.device)
-        _lib.check(lib.sc_multitaper_fft_f32(_ptr(x), T, R, C, L, n_step, n_windows, n_fft,
-                                             _ptr(tapers_over_fs), K, _lib.DETREND[detrend_type],
-                                             _ptr(twiddles(n_fft, x.device)), _ptr(X), _stream()),
-                   "sc_multitaper_fft_f32")
-        if mark:
-            mark("mtfft_fused")
-        return DeviceSpectra(X, (F, n_windows, R, K, C_real), strides, n_fft, real_input=True, C_alloc=C)
-    batch = n_windows * R * K * C
-    y = torch.empty((batch, n_fft), dtype=torch.float32, device=x.device)
-    _lib.check(lib.sc_taper_windows_f32(_ptr(x), T, R, C, L, n_step, n_windows, n_fft,
-                                        _ptr(tapers_over_fs), K, _lib.DETREND[detrend_type],
-                                        _ptr(y), _stream()), "sc_taper_windows_f32")
-    if mark:
-        mark("taper_windows")
-    X = torch.empty((F, n_windows, R, K, C), dtype=torch.complex64, device=x.device)
-    _lib.check(lib.sc_fft_execute(fft_plan(n_fft, batch), _ptr(y), _ptr(X), _stream()), "sc_fft_execute")
-    if mark:
-        mark("rocfft_r2c")
-    del y
-    return DeviceSpectra(X, (F, n_windows, R, K, C_real), strides, n_fft, real_input=True, C_alloc=C)
-
-
-def multitaper_spectra_f64(x, tapers_over_fs, n_window, n_step, n_fft, n_windows, detrend_type, mark=None, use_fused=None):
-    """Stage A of the float64 engine: (T,R,C) float64 tensor -> complex128 DeviceSpectra [F][W][R][K][C].  One fused kernel
-    (sc_multitaper_fft_f64) for the lengths it compiles; sc_taper_windows_f64 + double-precision rocFFT + transpose for
-    any other window / FFT length."""
-    lib = _lib.load()
-    T, R, C = x.shape
-    K, L = tapers_over_fs.shape
-    assert L == n_window and x.dtype == torch.float64 and tapers_over_fs.dtype == torch.float64
-    F = n_fft // 2 + 1
-    strides = (n_windows * R * K * C, R * K * C, K * C, C)
-    batch = n_windows * R * K * C
-    if use_fused is None:
-        use_fused = bool(lib.sc_multitaper_fft_f64_supported(L, n_fft)) and R <= 65535 and n_windows <= 65535
-    if use_fused:
-        X = torch.empty((F, n_windows, R, K, C), dtype=torch.complex128, device=x.device)
-        _lib.check(lib.sc_multitaper_fft_f64(_ptr(x), T, R, C, L, n_step, n_windows, n_fft, _ptr(tapers_over_fs), K,
-                                             _lib.DETREND[detrend_type], _ptr(X), _stream()), "sc_multitaper_fft_f64")
-        if mark:
-            mark("mtfft_fused_f64")
-        return DeviceSpectra(X, (F, n_windows, R, K, C), strides, n_fft, real_input=True)
-    y = torch.empty((batch, n_fft), dtype=torch.float64, device=x.device)
-    _lib.check(lib.sc_taper_windows_f64(_ptr(x), T, R, C, L, n_step, n_windows, n_fft, _ptr(tapers_over_fs), K,
-                                        _lib.DETREND[detrend_type], _ptr(y), _stream()), "sc_taper_windows_f64")
-    if mark:
-        mark("taper_windows_f64")
-    X = torch.empty((F, n_windows, R, K, C), dtype=torch.complex128, device=x.device)
-    _lib.check(lib.sc_fft_execute_f64(fft_plan(n_fft, batch, f64=True), _ptr(y), _ptr(X), _stream()),
-               "sc_fft_execute_f64")
-    if mark:
-        mark("rocfft_d2z")
-    del y
-    return DeviceSpectra(X, (F, n_windows, R, K, C), strides, n_fft, real_input=True)
-
-
-def upload_coefficients(coef, device="cuda", f64=False):
-    """Reference-layout (W,R,K,N,C) complex coefficients -> DeviceSpectra (all N bins, as given)."""
-    coef = np.asarray(coef)
-    W, R, K, N, C_real = coef.shape
-    if f64:
-        X = torch.from_numpy(np.ascontiguousarray(coef, dtype=np.complex128)).to(device)
-        return DeviceSpectra(X, (N, W, R, K, C_real), (C_real, R * K * N * C_real, K * N * C_real, N * C_real), N,
-                             real_input=False)
-    coef = np.ascontiguousarray(coef, dtype=np.complex64)
-    if C_real % 2 and C_real + 1 <= 256:
-        coef = np.concatenate([coef, np.zeros(coef.shape[:-1] + (1,), dtype=np.complex64)], axis=-1)
-    C = coef.shape[-1]
-    X = torch.from_numpy(coef).to(device)
-    return DeviceSpectra(X, (N, W, R, K, C_real), (C, R * K * N * C, K * N * C, N * C), N, real_input=False, C_alloc=C)
-
-
-def accum_layout(spectra, expectation_type, planes, n_freq=None):
-    lib = _lib.load()
-    d = spectra.desc(expectation_type, n_freq)
-    n_bins, fpb, n_groups, n_obs = c_int64(), c_int64(), c_int64(), c_int64()
-    _lib.check(lib.sc_accum_layout(byref(d), planes, byref(n_bins), byref(fpb), byref(n_groups),
-                                   byref(n_obs)), "sc_accum_layout")
-    return n_bins.value, fpb.value, n_groups.value, n_obs.value
 
 
 _ws_cache = {}
@@ -336,6 +163,113 @@ def _workspace(n_bytes, device, owner=None):
         buf = torch.empty(n_bytes, dtype=torch.uint8, device=device)
         cache[key] = buf
     return buf
+
+
+_TORCH_DTYPES = {np.uint8: torch.uint8, np.int32: torch.int32, np.float32: torch.float32, np.float64: torch.float64,
+                 np.complex64: torch.complex64, np.complex128: torch.complex128}
+_TORCH_DTYPES.update({np.dtype(k): v for k, v in list(_TORCH_DTYPES.items())})
+
+
+class TorchMemory:
+    """The memory adapter of the shared drivers (_stage_abc.py, _stage_d.py) on this host: tensors of ``device``, calls on the
+    current stream."""
+
+    def __init__(self, device):
+        self.device = device
+
+    def empty(self, shape, dtype):
+        return torch.empty(shape, dtype=_TORCH_DTYPES[dtype], device=self.device)
+
+    def zeros(self, shape, dtype):
+        return torch.zeros(shape, dtype=_TORCH_DTYPES[dtype], device=self.device)
+
+    def upload(self, array):
+        return torch.from_numpy(np.ascontiguousarray(array)).to(self.device)
+
+    def ptr(self, t, first_row=0):
+        return c_void_p(t.data_ptr() + (first_row * t.stride(0) * t.element_size() if first_row else 0))
+
+    stream = staticmethod(_stream)
+    download = staticmethod(to_host)
+    spectra = DeviceSpectra
+
+    def is_f64(self, record):
+        return record.dtype == torch.float64
+
+    def fill_nan(self, t):
+        t.fill_(float("nan"))
+
+    def read_int(self, t):
+        return int(t.item())
+
+    def hstack(self, chunks, n_rows):
+        return chunks[0] if len(chunks) == 1 else torch.cat([c.view(n_rows, -1) for c in chunks], dim=1).reshape(-1)
+
+    def head(self, t, n):
+        return t[:n]
+
+    def twiddles(self, n_fft):
+        return twiddles(n_fft, self.device)
+
+    def workspace(self, n_bytes, owner=None):
+        return _workspace(n_bytes, self.device, owner)
+
+    @contextlib.contextmanager
+    def fft_plan(self, n_fft, batch, f64=False):
+        yield fft_plan(n_fft, batch, f64)       # (cached: nothing to wait for or destroy)
+
+
+def multitaper_spectra(x, tapers_over_fs, n_window, n_step, n_fft, n_windows, detrend_type, mark=None,
+                       use_fused=None, n_signals=None, planes_hint=None):
+    """Stage A on device: (T,R,C) float32 tensor -> DeviceSpectra [F][W][R][K][C] (_stage_abc.spectra_f32).
+
+    ``tapers_over_fs``: (K, L) float32 device tensor = reference tapers^T / fs
+    (folds the sqrt(fs) of transforms.py:1440 and the /fs of transforms.py:1405).
+    ``n_signals``: number of real channels when ``x`` already carries the all-zero pad channel of an odd channel count
+    (appended on the host before the upload, transforms.Multitaper.device_spectra); a device tensor with an odd channel
+    count that arrives unpadded is copied into a padded buffer here (one strided device copy).
+    ``planes_hint``: the accumulator families the caller will ask for.  Any family sc_fused2.hip serves, 44 ... 1024 signals, a
+    window length stage A has the output for (the powers of two 64 ... 4096, the lengths 200 ... 2000 of sc_mtfft_mixed.hip:
+    sc_multitaper_fft_planes_supported) and at least 256 MB of spectra (_lib.planes_format_applies): the spectra are
+    written in the planes format (two f16 pieces per real number) -- a scan of the series for the channel scales, then the same
+    fused transform.  The scan also reports how large a typical coefficient will be in the format's scaled units
+    (``DeviceSpectra.planes_typical_coefficient()``): one scale per channel serves every window, so the format is meant for
+    series without samples hundreds of times the typical amplitude; Multitaper.device_spectra checks against
+    _lib.PLANES_MIN_TYPICAL and re-runs the transform into complex64 otherwise.
+    """
+    T, R, C_real = x.shape
+    if n_signals is not None:
+        assert n_signals in (C_real, C_real - 1)
+        C_real = int(n_signals)
+    elif _lib.padded_channels(C_real, _lib.PLANES_FORMAT_MAX_CHANNELS) != C_real:
+        padded = torch.zeros((T, R, C_real + 1), dtype=x.dtype, device=x.device)
+        padded[..., :C_real].copy_(x)                # odd channel count: one zero channel (see DeviceSpectra)
+        x = padded
+    T, R, C = x.shape
+    K, L = tapers_over_fs.shape
+    assert L == n_window
+    return _stage_abc.spectra_f32(TorchMemory(x.device), x, tapers_over_fs, T, R, C, C_real, L, n_step, n_windows, n_fft,
+                                  _lib.DETREND[detrend_type], planes_hint, mark, use_fused,
+                                  taper_norms=lambda: _taper_norms(tapers_over_fs))
+
+
+def multitaper_spectra_f64(x, tapers_over_fs, n_window, n_step, n_fft, n_windows, detrend_type, mark=None, use_fused=None):
+    """Stage A of the float64 engine: (T,R,C) float64 tensor -> complex128 DeviceSpectra [F][W][R][K][C].  One fused kernel
+    (sc_multitaper_fft_f64) for the lengths it compiles; sc_taper_windows_f64 + double-precision rocFFT + transpose for
+    any other window / FFT length (_stage_abc.spectra_f64)."""
+    T, R, C = x.shape
+    K, L = tapers_over_fs.shape
+    assert L == n_window and x.dtype == torch.float64 and tapers_over_fs.dtype == torch.float64
+    return _stage_abc.spectra_f64(TorchMemory(x.device), x, tapers_over_fs, T, R, C, L, n_step, n_windows, n_fft,
+                                  _lib.DETREND[detrend_type], mark, use_fused)
+
+
+def upload_coefficients(coef, device="cuda", f64=False):
+    """Reference-layout (W,R,K,N,C) complex coefficients -> DeviceSpectra (all N bins, as given)."""
+    return _stage_abc.upload_coefficients(TorchMemory(device), coef, f64)
+
+
+accum_layout = _stage_abc.accum_layout
 
 
 def _record_tensor(n_bins, fpb, dtype, device, row_multiple):
@@ -363,15 +297,12 @@ def plane_slots(planes):
     return out
 
 
-MAX_KERNEL_SIGNALS = 256          # SC_MAX_SIGNALS of csrc/sc_common.h: what one launch of the stage-B kernels stages per observation row
-
-
 def _channel_subset(spectra, cols):
     """The spectra of the channels ``cols`` (a LongTensor of channel indices) as a dense DeviceSpectra of its own: one gathering
     copy; an odd count gets the zero pad channel of the float32 engine."""
     X = spectra.X
     n = int(cols.numel())
-    n_alloc = n if (spectra.f64 or n % 2 == 0) else n + 1
+    n_alloc = n if spectra.f64 else _lib.padded_channels(n, _stage_abc.MAX_KERNEL_SIGNALS)      # (n <= 256: two channel blocks)
     sub = torch.zeros(tuple(X.shape[:-1]) + (n_alloc,), dtype=X.dtype, device=X.device) if n_alloc != n else \
         torch.empty(tuple(X.shape[:-1]) + (n_alloc,), dtype=X.dtype, device=X.device)
     torch.index_select(X, X.dim() - 1, cols, out=sub[..., :n]) if n_alloc == n else sub[..., :n].copy_(X.index_select(X.dim() - 1, cols))
@@ -410,7 +341,8 @@ def _accumulate_blocked(spectra, expectation_type, planes, n_freq, mark, row_mul
 def accumulate(spectra, expectation_type, planes, n_freq=None, mark=None, use_fused=None, row_multiple=1, have=None,
                fold=True, ws_owner=None):
     """Stage B: un-normalised accumulator record tensor [n_bins, floats_per_bin] (float32; float64 records from
-    complex128 spectra).  ``row_multiple``: see _record_tensor (trial-sharded callers pass the world size).
+    complex128 spectra) -- one call of _stage_abc.accumulate; what is tensor arithmetic of this host happens around it.
+    ``row_multiple``: see _record_tensor (trial-sharded callers pass the world size).
     ``fold=False`` (planes-format path only; ignored elsewhere): when stage B split every bin over several workgroups, their
     partial records are NOT summed -- the result is then ONE 3-D tensor [n_parts, n_bins, floats_per_bin] of its own (the sum
     over axis 0, in part order, is the record): measure() / measure_multi() add the parts while their kernel reads them (one pass
@@ -419,128 +351,34 @@ def accumulate(spectra, expectation_type, planes, n_freq=None, mark=None, use_fu
     expectation are copied over (a strided device copy) and only the missing ones are computed -- its CSM and
     per-observation planes are separate kernels, so a wPLI after a coherence costs the |Im s| plane alone.
     ``ws_owner``: see _workspace (a dict that owns the split-bin scratch of this call instead of the per-device cache)."""
-    lib = _lib.load()
-    if spectra.C > MAX_KERNEL_SIGNALS:
+    if spectra.C > _stage_abc.MAX_KERNEL_SIGNALS:
         # planes-format spectra go straight to sc_fused2.hip, which plans its launches over any number of 32-channel blocks (round 6);
         # every other request beyond 256 signals is tiled over channel-block pairs
         direct = (not spectra.f64 and spectra.P is not None and use_fused is not False
-                  and bool(lib.sc_fused2_supported(byref(spectra.desc(expectation_type, n_freq, padded=True)), planes)))
+                  and _stage_abc.fused2_takes(spectra.desc(expectation_type, n_freq, padded=True), planes))
         if not direct:
             return _accumulate_blocked(spectra, expectation_type, planes, n_freq, mark, row_multiple)
-    d = spectra.desc(expectation_type, n_freq)
-    n_bins, fpb, _, n_obs = accum_layout(spectra, expectation_type, planes, n_freq)
-    if spectra.f64:
-        # float64 engine: fp64 matrix cores for the CSM planes, fp64 VALU for the others, double records
-        accum = _record_tensor(n_bins, fpb, torch.float64, spectra.device, row_multiple)
-        which = planes
-        if have is not None and have[1].dtype == torch.float64 and have[1].shape[0] == n_bins and (have[0] & planes):
+    out = which = None
+    copy_have = spectra.f64 and have is not None
+    if row_multiple != 1 or copy_have:
+        # the record is this host's to shape: padded rows for a reduce-scatter, or partly filled from a record at hand
+        n_bins, fpb, _, _ = accum_layout(spectra, expectation_type, planes, n_freq)
+        out = _record_tensor(n_bins, fpb, torch.float64 if spectra.f64 else torch.float32, spectra.device, row_multiple)
+        if copy_have and have[1].dtype == torch.float64 and have[1].shape[0] == n_bins and (have[0] & planes):
+            which = planes
             old_planes, old = have
             new_slots, old_slots = plane_slots(planes), plane_slots(old_planes)
             n_new, n_old = sum(w for _, w in new_slots.values()), sum(w for _, w in old_slots.values())
-            new_v, old_v = accum.view(n_bins, n_new, fpb // n_new), old.view(n_bins, n_old, old.shape[1] // n_old)
+            new_v, old_v = out.view(n_bins, n_new, fpb // n_new), old.view(n_bins, n_old, old.shape[1] // n_old)
             for bit, (i_new, width) in new_slots.items():
                 if bit in old_slots:
                     new_v[:, i_new:i_new + width].copy_(old_v[:, old_slots[bit][0]:old_slots[bit][0] + width])
                     which &= ~bit
-        if which:
-            _lib.check(lib.sc_accumulate_f64(_ptr(spectra.X), byref(d), planes, which, _ptr(accum), _stream()),
-                       "sc_accumulate_f64")
-        if mark:
-            mark("accumulate_f64")
-        return accum, n_obs
-    accum = None
-    if spectra.P is not None and use_fused is not False:
-        dp = spectra.desc(expectation_type, n_freq, padded=True)
-        if lib.sc_fused2_supported(byref(dp), planes):
-            # planes format: CSM (+ |Im s|) straight from the f16 pieces stage A wrote (sc_fused2.hip)
-            ws_bytes = int(lib.sc_fused_workspace_bytes(byref(dp), planes))
-            part_bytes = n_bins * fpb * 4
-            if not fold and ws_bytes >= part_bytes and row_multiple == 1:
-                # partial records kept: parts 1 .. behind part 0 in one allocation of the caller's own
-                max_parts = 1 + ws_bytes // part_bytes
-                parts = torch.empty((max_parts, n_bins, fpb), dtype=torch.float32, device=spectra.device)
-                n_parts = ctypes.c_int(1)
-                _lib.check(lib.sc_fused2_csm_absim_parts_f32(_ptr(spectra.P), byref(dp), _ptr(spectra.scale), planes, _ptr(parts[0]),
-                                                             _ptr(parts[1]), (max_parts - 1) * part_bytes, byref(n_parts), _stream()),
-                           "sc_fused2_csm_absim_parts_f32")
-                if mark:
-                    mark("fused2_csm_absim")
-                return (parts[:n_parts.value] if n_parts.value > 1 else parts[0]), n_obs
-            ws = _workspace(ws_bytes, spectra.device, ws_owner)
-            accum = _record_tensor(n_bins, fpb, torch.float32, spectra.device, row_multiple)
-            _lib.check(lib.sc_fused2_csm_absim_f32(_ptr(spectra.P), byref(dp), _ptr(spectra.scale), planes, _ptr(accum),
-                                                   _ptr(ws) if ws is not None else None, ws_bytes, _stream()),
-                       "sc_fused2_csm_absim_f32")
-            if mark:
-                mark("fused2_csm_absim")
-            return accum, n_obs
-    accum = _record_tensor(n_bins, fpb, torch.float32, spectra.device, row_multiple)
-    per_plane_only = use_fused is False        # explicit request (tests): every plane through its separate kernel
-    if use_fused is None:
-        use_fused = bool(lib.sc_fused_supported(spectra.C_alloc))
-    # planes the one-pass kernels fill for this shape (sc_fused.hip): CSM, |Im s|, s/|s|; for few channels also
-    # (Im s)^2 and sign(Im s).  Whatever is left goes to the per-plane VALU kernel.  The one-pass kernels see the zero
-    # pad channel of an odd channel count as a signal: same record (DeviceSpectra).
-    d_real, d = d, spectra.desc(expectation_type, n_freq, padded=True)
-    one_pass = int(lib.sc_fused_planes_covered(byref(d), planes)) if use_fused else 0
-    if one_pass:
-        ws_bytes = int(lib.sc_fused_workspace_bytes(byref(d), planes))
-        ws = _workspace(ws_bytes, spectra.device, ws_owner)
-        ws_ptr = _ptr(ws) if ws is not None else None
-        if one_pass & _lib.PLANE_CSM:
-            # CSM (+ the per-observation |Im s| products, + (Im s)^2): bf16 matrix pipe, or the f32 VALU kernel
-            _lib.check(lib.sc_fused_csm_absim_ws_f32(_ptr(spectra.X), byref(d), planes, _ptr(accum), ws_ptr, ws_bytes,
-                                                     _stream()), "sc_fused_csm_absim_ws_f32")
-            if mark:
-                mark("fused_csm_absim")
-        if one_pass & _lib.PLANE_SIGN_IM:
-            _lib.check(lib.sc_fused_sign_ws_f32(_ptr(spectra.X), byref(d), planes, _ptr(accum), ws_ptr, ws_bytes,
-                                                _stream()), "sc_fused_sign_ws_f32")
-            if mark:
-                mark("fused_sign")
-        if one_pass & _lib.PLANE_UNIT:
-            # sum s/|s| = the CSM of the unit phasors x/|x|: the same kernels on normalised rows
-            sb = int(lib.sc_fused_unit_scratch_bytes(byref(d)))
-            scratch = torch.empty((sb,), dtype=torch.uint8, device=spectra.device) if sb else None
-            _lib.check(lib.sc_fused_unit_ws_f32(_ptr(spectra.X), byref(d), planes, _ptr(accum), ws_ptr, ws_bytes,
-                                                _ptr(scratch) if scratch is not None else None, sb, _stream()),
-                       "sc_fused_unit_ws_f32")
-            if mark:
-                mark("fused_unit")
-        nl = planes & ~one_pass
-        if nl:
-            _lib.check(lib.sc_nonlinear_accumulate_f32(_ptr(spectra.X), byref(d_real), planes, nl, _ptr(accum),
-                                                       _stream()), "sc_nonlinear_accumulate_f32")
-            if mark:
-                mark("nonlinear_valu")
-        return accum, n_obs
-    d = d_real
-    if planes & _lib.PLANE_CSM:
-        _lib.check(lib.sc_csm_accumulate_f32(_ptr(spectra.X), byref(d), planes, _ptr(accum), _stream()),
-                   "sc_csm_accumulate_f32")
-        if mark:
-            mark("csm_mfma")
-    nl = planes & ~_lib.PLANE_CSM
-    if nl & _lib.PLANE_UNIT and not per_plane_only:
-        # sum s/|s| as the CSM of a normalised copy of the spectra (f32 MFMA) instead of a per-pair rsqrt on the VALU
-        sb = int(lib.sc_unit_scratch_bytes(byref(d)))
-        scratch = torch.empty((sb,), dtype=torch.uint8, device=spectra.device)
-        _lib.check(lib.sc_unit_accumulate_f32(_ptr(spectra.X), byref(d), planes, _ptr(accum), _ptr(scratch), sb,
-                                              _stream()), "sc_unit_accumulate_f32")
-        nl &= ~_lib.PLANE_UNIT
-        if mark:
-            mark("unit_mfma")
-    if nl:
-        _lib.check(lib.sc_nonlinear_accumulate_f32(_ptr(spectra.X), byref(d), planes, nl, _ptr(accum),
-                                                   _stream()), "sc_nonlinear_accumulate_f32")
-        if mark:
-            mark("nonlinear_valu")
+    accum, n_obs = _stage_abc.accumulate(TorchMemory(spectra.device), spectra, expectation_type, planes, n_freq, which, out, fold,
+                                         ws_owner, use_fused, mark)
+    if accum.dim() == 3 and accum.shape[0] == 1:
+        accum = accum[0]                                   # (the kernel did not split the bins: an ordinary record)
     return accum, n_obs
-
-
-def rec_planes(accum, planes):
-    """`planes` as the consumers of a record tensor want it: with SC_RECORD_F64 when the records are doubles."""
-    return _lib.record_planes(planes, accum.dtype == torch.float64)
 
 
 def fold_parts(accum):
@@ -558,42 +396,24 @@ def fold_parts(accum):
     return cached
 
 
+def _record_and_parts(accum, summed_by_kernel=True):
+    """(2-D record, partial records or None): contiguous partial records [n_parts > 1, n_bins, floats_per_bin] go to the epilogue as
+    they are when its kernel sums them in part order while it reads (``summed_by_kernel``); they are folded here otherwise."""
+    if accum.dim() != 3:
+        return accum, None
+    if summed_by_kernel and accum.shape[0] > 1 and accum.is_contiguous():
+        return accum[0], accum
+    return fold_parts(accum), None                       # part (= rank) order
+
+
 def measure(accum, n_signals, planes, n_obs, which, out=None, wide=None):
-    """Stage C: one measure from an accumulator tensor (after any cross-GPU sum).  ``wide``: write float64 /
-    complex128 (what the reference returns) straight from the epilogue; default: wide for double records."""
-    lib = _lib.load()
-    parts = None
-    if accum.dim() == 3:
-        # partial records (accumulate(fold=False), or the blocks of a direct exchange): the epilogue kernels sum them in part order
-        # while they read (sc_measure_parts: every measure, power and the complex-valued ones included)
-        if accum.shape[0] > 1 and accum.is_contiguous():
-            parts, accum = accum, accum[0]
-        else:
-            accum = fold_parts(accum)
-    n_bins = accum.shape[0]
-    C = n_signals
+    """Stage C: one measure from an accumulator tensor (after any cross-GPU sum; partial records: sc_measure_parts, every measure,
+    power and the complex-valued ones included).  ``wide``: write float64 / complex128 (what the reference returns) straight from
+    the epilogue; default: wide for double records."""
+    accum, parts = _record_and_parts(accum)
     if wide is None:
         wide = accum.dtype == torch.float64
-    real_t, cplx_t = (torch.float64, torch.complex128) if wide else (torch.float32, torch.complex64)
-    if which == _lib.M_POWER:
-        shape, dtype = (n_bins, C), real_t
-    elif which in _lib.COMPLEX_MEASURES:
-        shape, dtype = (n_bins, C, C), cplx_t
-    else:
-        shape, dtype = (n_bins, C, C), real_t
-    if out is None:
-        out = torch.empty(shape, dtype=dtype, device=accum.device)
-    if parts is not None:
-        _lib.check(lib.sc_measure_parts(_ptr(parts[0]), _ptr(parts[1]), parts.shape[0], parts.stride(0), n_bins, C,
-                                        rec_planes(accum, planes), n_obs, which, _ptr(out), int(bool(wide)), _stream()), "sc_measure_parts")
-        return out
-    fn = lib.sc_measure_f64 if wide else lib.sc_measure_f32
-    _lib.check(fn(_ptr(accum), n_bins, C, rec_planes(accum, planes), n_obs, which, _ptr(out), _stream()),
-               "sc_measure")
-    return out
-
-
-MEASURE_MULTI_MAX = 4
+    return _stage_abc.measure(TorchMemory(accum.device), accum, n_signals, planes, n_obs, which, wide, parts, out)
 
 
 def measure_multi(accum, n_signals, planes, n_obs, which, wide=None, stacked=False):
@@ -605,36 +425,15 @@ def measure_multi(accum, n_signals, planes, n_obs, which, wide=None, stacked=Fal
     that the epilogue sums in part order while it reads them (sc_measure_multi_parts) -- or, where the one-launch form
     does not apply, that are summed first."""
     which = list(which)
-    parts = None
-    simple = [w for w in which if w != _lib.M_POWER and w not in _lib.COMPLEX_MEASURES]
-    if accum.dim() == 3:
-        if accum.shape[0] > 1 and len(simple) == len(which) and 1 <= len(which) <= MEASURE_MULTI_MAX and accum.is_contiguous():
-            parts = accum
-            accum = parts[0]
-        else:
-            accum = fold_parts(accum)                                # part (= rank) order
-    if parts is None and (len(simple) != len(which) or not 2 <= len(which) <= MEASURE_MULTI_MAX):
-        return [measure(accum, n_signals, planes, n_obs, w, wide=wide) for w in which]
-    lib = _lib.load()
-    n_bins, C = accum.shape[0], n_signals
+    accum, parts = _record_and_parts(accum, _stage_abc.one_launch(which, True))
     if wide is None:
         wide = accum.dtype == torch.float64
-    if stacked:
-        block = torch.empty((len(which), n_bins, C, C), dtype=torch.float64 if wide else torch.float32, device=accum.device)
+    outs = None
+    if stacked and _stage_abc.one_launch(which, parts is not None):
+        block = torch.empty((len(which), accum.shape[0], n_signals, n_signals), dtype=torch.float64 if wide else torch.float32,
+                            device=accum.device)
         outs = list(block.unbind(0))
-    else:
-        outs = [torch.empty((n_bins, C, C), dtype=torch.float64 if wide else torch.float32, device=accum.device) for _ in which]
-    ids = (ctypes.c_int * len(which))(*which)
-    ptrs = (ctypes.c_void_p * len(which))(*[o.data_ptr() for o in outs])
-    if parts is not None:
-        _lib.check(lib.sc_measure_multi_parts(_ptr(parts[0]), _ptr(parts[1]), parts.shape[0], parts.stride(0), n_bins, C,
-                                              rec_planes(accum, planes), n_obs, len(which), ids, ptrs, int(bool(wide)), _stream()),
-                   "sc_measure_multi_parts")
-        return outs
-    fn = lib.sc_measure_multi_f64 if wide else lib.sc_measure_multi_f32
-    _lib.check(fn(_ptr(accum), n_bins, C, rec_planes(accum, planes), n_obs, len(which), ids, ptrs, _stream()),
-               "sc_measure_multi")
-    return outs
+    return _stage_abc.measure_multi(TorchMemory(accum.device), accum, n_signals, planes, n_obs, which, wide, parts, outs)
 
 
 # ---- stage D: the call sequences live in _stage_d.py (shared with the torch-free host); here are the memory adapter of this host
@@ -642,42 +441,6 @@ def measure_multi(accum, n_signals, planes, n_obs, which, wide=None, stacked=Fal
 MAX_WILSON_ITERATIONS = _stage_d.MAX_WILSON_ITERATIONS
 check_max_iterations = _stage_d.check_max_iterations
 GRANGER_WORK_BYTES = _lib.GRANGER_WORK_BYTES      # (the bound the drivers read is _lib.GRANGER_WORK_BYTES)
-_TORCH_DTYPES = {np.dtype(np.uint8): torch.uint8, np.dtype(np.int32): torch.int32, np.dtype(np.float64): torch.float64,
-                 np.dtype(np.complex128): torch.complex128}
-
-
-class TorchMemory:
-    """The memory adapter of the stage-D drivers (_stage_d.py) on this host: tensors of ``device``, calls on the current stream."""
-
-    def __init__(self, device):
-        self.device = device
-
-    def empty(self, shape, dtype):
-        return torch.empty(shape, dtype=_TORCH_DTYPES[np.dtype(dtype)], device=self.device)
-
-    def zeros(self, shape, dtype):
-        return torch.zeros(shape, dtype=_TORCH_DTYPES[np.dtype(dtype)], device=self.device)
-
-    def upload(self, array):
-        return torch.from_numpy(np.ascontiguousarray(array)).to(self.device)
-
-    def ptr(self, t, first_row=0):
-        return c_void_p(t.data_ptr() + (first_row * t.stride(0) * t.element_size() if first_row else 0))
-
-    stream = staticmethod(_stream)
-    download = staticmethod(to_host)
-
-    def is_f64(self, record):
-        return record.dtype == torch.float64
-
-    def fill_nan(self, t):
-        t.fill_(float("nan"))
-
-    def read_int(self, t):
-        return int(t.item())
-
-    def hstack(self, chunks, n_rows):
-        return chunks[0] if len(chunks) == 1 else torch.cat([c.view(n_rows, -1) for c in chunks], dim=1).reshape(-1)
 
 
 def granger_pairwise(accum, n_groups, n_freq_accum, n_fft, n_signals, planes, n_obs, pairs,

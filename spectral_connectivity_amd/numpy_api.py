@@ -9,18 +9,16 @@
 ``SC_HIP_HOST=numpy|torch`` selects (default: torch when it can be imported, NumPy otherwise); with ``numpy`` the package's
 ``Connectivity`` is the class below and ``Multitaper.fft()`` / ``Multitaper.device_spectra()`` run here -- ``torch`` is never
 imported.  Same constructor, properties, methods, shapes, dtypes, warnings and errors as the PyTorch-host class (it IS that class:
-only the methods of stages A-C that touch the device are replaced; stage D runs the base class's methods over the shared drivers of
-``_stage_d.py`` through ``NumpyHost.memory``), both engines (``dtype=complex64`` -> float32 engine, planes format
+only the methods of stages A-C that touch the device are replaced, and they call the same drivers, ``_stage_abc.py``, through
+``NumpyHost.memory``; stage D runs the base class's methods over the shared drivers of ``_stage_d.py`` the same way), both engines (``dtype=complex64`` -> float32 engine, planes format
 included; ``complex128``, the default -> float64 engine), every expectation-type measure, pairwise / subset Granger, the full
 Wilson factor and the directed MVAR measures, canonical and global coherence, MIC / MIM, the jackknife, the band statistics, more than 256
 signals (channel blocks of 128, tiled on the host).  Not here: complex-valued time series, multi-GPU (``parallel.ShardedConnectivity`` needs
 ``torch.distributed``), hipGraph replay (``engine.GraphedMeasures``).
 """
-from ctypes import byref
-
 import numpy as np
 
-from . import _lib, _stage_d
+from . import _lib, _stage_abc, _stage_d
 from .connectivity import Connectivity as _TorchHostConnectivity
 from .connectivity import _PendingSpectra
 from .numpy_host import DeviceArray as _Record      # accumulator records on the device: [n_bins][floats_per_bin] float32 / float64
@@ -48,14 +46,14 @@ def multitaper_spectra(m, precision, planes_hint=None):
         # more than 256 signals: planes-format spectra of the whole array where the format applies (round 6: sc_fused2.hip plans its
         # launches over any number of 32-channel blocks) -- otherwise no device spectra of the whole array, the record is tiled
         C = ts.shape[2]
-        C_alloc = C + (C & 1)
+        C_alloc = _lib.padded_channels(C, _lib.PLANES_FORMAT_MAX_CHANNELS)
         F, W, R, K = m.n_fft_samples // 2 + 1, int(m.n_time_windows), ts.shape[1], int(m.n_tapers)
         if (precision != "float64" and C_alloc <= _lib.PLANES_FORMAT_MAX_CHANNELS
                 and _lib.planes_format_applies(m.n_time_samples_per_window, m.n_fft_samples, C_alloc, planes_hint,
                                                spectra_bytes=F * W * R * K * C_alloc * 8)):
             sp = h.spectra(m, planes_hint=planes_hint)
-            if sp.get("P") is not None:
-                sp["wide_source"] = (m, precision)       # (a family outside the format later: back to the tiling, see _accumulators)
+            if sp.P is not None:
+                sp.wide_source = (m, precision)       # (a family outside the format later: back to the tiling, see _accumulators)
                 return sp
             sp.free()                                    # (the format's quality check sent the transform to complex64)
         return _WideSeries(m, precision)
@@ -72,7 +70,7 @@ class _WideSeries:
         ts = np.asarray(multitaper.time_series)
         self.W, self.R, self.K = int(multitaper.n_time_windows), int(ts.shape[1]), int(multitaper.n_tapers)
         self.n_fft, self.C = int(multitaper.n_fft_samples), int(ts.shape[2])
-        self.N, self.F = self.n_fft, self.n_fft // 2 + 1
+        self.F = self.n_fft // 2 + 1
         self.real_input, self.f64, self.P = True, precision == "float64", None
 
 
@@ -87,8 +85,8 @@ def fft(m):
     for cc in cols:
         sub = m if len(cols) == 1 else _channel_subset_multitaper(m, cc)
         sp = host().spectra_f64(sub) if precision == "float64" else host().spectra(sub)
-        dt = np.complex128 if sp["f64"] else np.complex64
-        one = host().download(sp["X"], (sp["F"], sp["W"], sp["R"], sp["K"], sp["C_alloc"]), dt)[..., :sp["C"]]
+        dt = np.complex128 if sp.f64 else np.complex64
+        one = host().download(sp.X, (sp.F, sp.W, sp.R, sp.K, sp.C_alloc), dt)[..., :sp.C]
         parts.append(np.array(one, dtype=np.complex128))
         sp.free()
     one = np.moveaxis(parts[0] if len(parts) == 1 else np.concatenate(parts, axis=-1), 0, 3)       # (W, R, K, F, C)
@@ -150,9 +148,7 @@ class Connectivity(_TorchHostConnectivity):
     def _accumulate(self, sp, expectation_type, planes, n_freq):
         if isinstance(sp, _WideSeries):
             return self._accumulate_wide(sp, expectation_type, planes, n_freq)
-        buf, n_bins, n_obs = host().accumulate(sp, expectation_type, planes, n_freq=n_freq)
-        dt = np.dtype(np.float64 if sp["f64"] else np.float32)
-        return _Record(buf, (n_bins, buf.n_bytes // (n_bins * dt.itemsize) if n_bins else 0), dt), n_obs
+        return host()._accumulate_record(sp, expectation_type, planes, n_freq)
 
     def _accumulate_wide(self, wide, expectation_type, planes, n_freq):
         """engine._accumulate_blocked on this host: every pair of channel blocks (_lib.tile_plan) is a request of its own (<= 256
@@ -165,12 +161,13 @@ class Connectivity(_TorchHostConnectivity):
         for _, _, cols, src, dst in _lib.tile_plan(wide.C):
             sub_m = _channel_subset_multitaper(m, cols)
             sp = host().spectra_f64(sub_m) if wide.f64 else host().spectra(sub_m)
-            buf, n_bins, n_obs = host().accumulate(sp, expectation_type, planes, n_freq=n_freq)
+            part, n_obs = host()._accumulate_record(sp, expectation_type, planes, n_freq)
             sp.free()
             nb_s = -(-len(cols) // 16)
             nt_s = nb_s * (nb_s + 1) // 2
-            rec = np.array(host().download(buf, (n_bins, buf.n_bytes // (n_bins * nt_s * 256 * dt.itemsize), nt_s, 256), dt))
-            buf.free()
+            n_bins = part.shape[0]
+            rec = np.array(host().download(part.buf, (n_bins, part.shape[1] // (nt_s * 256), nt_s, 256), dt))
+            del part
             if full is None:
                 full, n_obs_out = np.zeros((n_bins, rec.shape[1], NB * (NB + 1) // 2, 256), dtype=dt), n_obs
             full[:, :, dst] = rec[:, :, src]
@@ -190,8 +187,8 @@ class Connectivity(_TorchHostConnectivity):
             # float64 engine on this host: a later phase-lag request cannot copy the families a record already holds (the PyTorch
             # host does, with a strided device copy) and would accumulate everything again -- the |Im s| plane rides along instead
             planes = _lib.PLANE_CSM | _lib.PLANE_ABS_IM
-        if getattr(sp, "P", None) is not None and not host().lib.sc_fused2_supported(
-                byref(host()._desc(sp, self.expectation_type, True, self._n_freq)), planes):
+        if getattr(sp, "P", None) is not None and not _stage_abc.fused2_takes(sp.desc(self.expectation_type, self._n_freq, padded=True),
+                                                                             planes):
             # spectra held as f16 pieces, and a family their kernels do not take (PLV after coherence, ...): decoded once
             self._spectra = sp = self._decode_planes(sp)
         rec, n_obs = self._accumulate(sp, self.expectation_type, planes, self._n_freq)
@@ -203,16 +200,13 @@ class Connectivity(_TorchHostConnectivity):
     def _decode_planes(self, sp):
         """complex64 spectra from the planes format (sc_spectra_from_planes_f32: lossless up to its 22 bits).  More than 256 signals:
         the complex64 kernels do not take them in one piece -- back to the series and the channel-block tiling."""
-        h = host()
-        if sp["C"] > 256:
-            m, precision = sp["wide_source"]
+        if sp.C > 256:
+            m, precision = sp.wide_source
             sp.free()
             return _WideSeries(m, precision)
-        X = h.alloc(sp["F"] * sp["W"] * sp["R"] * sp["K"] * sp["C_alloc"] * 8)
-        d = h._desc(sp, "trials_tapers", True)
-        _lib.check(h.lib.sc_spectra_from_planes_f32(sp["P"].ptr, byref(d), sp["scale"].ptr, X.ptr, h.stream), "sc_spectra_from_planes_f32")
-        out = type(sp)(sp)
-        out.update(X=X, P=None, scale=None)
+        mem = host().memory
+        out = mem.spectra(_stage_abc.decode_planes(mem, sp), (sp.F, sp.W, sp.R, sp.K, sp.C), sp.strides, sp.n_fft, sp.real_input,
+                          C_alloc=sp.C_alloc)
         sp.free()
         return out
 
@@ -241,21 +235,9 @@ class Connectivity(_TorchHostConnectivity):
     def _measure(self, which):
         have, (rec, n_obs) = self._accumulators(_lib.MEASURE_PLANES[which])
         C = self._shape5[4]
-        wide = self._wide_output(which)
-        h = host()
-        n_bins = rec.shape[0]
-        if which == _lib.M_POWER:
-            shape, dt = (n_bins, C), (np.float64 if wide else np.float32)
-        elif which in _lib.COMPLEX_MEASURES:
-            shape, dt = (n_bins, C, C), (np.complex128 if wide else np.complex64)
-        else:
-            shape, dt = (n_bins, C, C), (np.float64 if wide else np.float32)
-        out = h.alloc(int(np.prod(shape)) * np.dtype(dt).itemsize)
-        fn = h.lib.sc_measure_f64 if wide else h.lib.sc_measure_f32
-        _lib.check(fn(rec.buf.ptr, n_bins, C, _lib.record_planes(have, rec.f64), self._n_observations_total(n_obs), which, out.ptr,
-                      h.stream), "sc_measure")
-        res = h.download(out, shape, dt)        # (the page-locked array itself: its owner recycles the block with the last view)
-        out.free()
+        out = _stage_abc.measure(host().memory, rec, C, have, self._n_observations_total(n_obs), which, self._wide_output(which))
+        res = host().download(out.buf, out.shape, out.dtype)        # (the page-locked array itself: its owner recycles the block with the last view)
+        del out
         tail = (C,) if which == _lib.M_POWER else (C, C)
         return res.reshape(self._kept_shape() + (self._n_freq,) + tail)
 

@@ -12,21 +12,25 @@ page-locked memory, copies and the stream come from the library's own ``sc_devic
                             n_time_samples_per_window=256, n_time_samples_per_step=128,
                             measures=("coherence_magnitude", "weighted_phase_lag_index"))
 
+The call sequences are the PyTorch host's: the shared drivers of ``_stage_abc.py`` (stages A to C) and ``_stage_d.py`` run here
+through ``NumpyMemory``; what this module adds is the memory (``DeviceBuffer`` / ``DeviceArray`` / ``PinnedArray``), the spectra
+object ``NpSpectra`` and this host's policy -- the planes format's quality check is read at once, an FFT plan lives for one transform.
+
 Scope of the functional interface below: the float32 engine's hot path -- stage A (fused transform, or tapered windows + rocFFT
 for the lengths the fused kernel does not take), stage B (every accumulator plane), the expectation-type measures of the reference
-(connectivity.py:612-1159), ``expectation_type`` as in the reference -- and stage D on float32 records through the shared drivers
-of ``_stage_d.py``: ``pairwise_spectral_granger_prediction``, ``canonical_coherence``, ``mvar_measures`` (the full Wilson factor)
-and ``global_coherence``.  Results are float64 / complex128 NumPy arrays shaped like the reference's.  The float64 engine, the
+(connectivity.py:612-1159), ``expectation_type`` as in the reference -- and stage D on float32 records:
+``pairwise_spectral_granger_prediction``, ``canonical_coherence``, ``mvar_measures`` (the full Wilson factor) and
+``global_coherence``.  Results are float64 / complex128 NumPy arrays shaped like the reference's.  The float64 engine, the
 other stage-D measures and more than 256 signals are on this host too, through the public classes (``numpy_api``, SC_HIP_HOST=numpy);
 multi-GPU needs the PyTorch host.  One process uses one host: see _lib.load().
 """
+import contextlib
 import ctypes
-from ctypes import byref, c_int64, c_void_p
+from ctypes import byref, c_void_p
 
 import numpy as np
 
-from . import _lib, _stage_d
-from ._lib import SpectraDesc
+from . import _lib, _stage_abc, _stage_d
 
 EXPECTATION_AXES = _lib.EXPECTATION_AXES
 MEASURES = {
@@ -92,7 +96,8 @@ class DeviceArray:
 
 
 class NumpyMemory:
-    """The memory adapter of the stage-D drivers (_stage_d.py) on this host: DeviceArray over NumpyHost.alloc / upload / download."""
+    """The memory adapter of the shared drivers (_stage_abc.py, _stage_d.py) on this host: DeviceArray over NumpyHost.alloc / upload /
+    download."""
 
     def __init__(self, host):
         self.host = host
@@ -135,6 +140,34 @@ class NumpyMemory:
         if len(chunks) == 1:
             return chunks[0]
         return self.upload(np.concatenate([self.download(c).reshape(n_rows, -1) for c in chunks], axis=1).reshape(-1))
+
+    def head(self, a, n):
+        return DeviceArray(a.buf, (n,) + a.shape[1:], a.dtype)
+
+    def spectra(self, X, dims, strides, n_fft, real_input, C_alloc=None, P=None, scale=None):
+        X, f64 = (None, False) if X is None else (X.buf, X.dtype == np.complex128)
+        return NpSpectra(X, dims, strides, n_fft, real_input, C_alloc, P and P.buf, scale and scale.buf, f64=f64)
+
+    def twiddles(self, n_fft):
+        tw = self.host._twiddles.get(n_fft)
+        if tw is None:
+            tw = self.host._twiddles[n_fft] = _stage_abc.make_twiddles(self, n_fft)
+        return tw
+
+    def workspace(self, n_bytes, owner=None):              # (a buffer of the call's own: back to the pool when the driver drops it)
+        return self.empty((n_bytes,), np.uint8) if n_bytes > 0 else None
+
+    @contextlib.contextmanager
+    def fft_plan(self, n_fft, batch, f64=False):
+        """A rocFFT plan for one execution: created, waited for, destroyed (its scratch must outlive the transform)."""
+        lib, plan = self.host.lib, c_void_p()
+        create = lib.sc_fft_plan_create_f64 if f64 else lib.sc_fft_plan_create
+        _lib.check(create(byref(plan), n_fft, batch), "sc_fft_plan_create")
+        try:
+            yield plan
+            self.host.synchronize()
+        finally:
+            lib.sc_fft_plan_destroy(plan)
 
     def download(self, a):
         """A NumPy array of its own (not the page-locked block, which goes back to the pool)."""
@@ -197,30 +230,21 @@ class _PinnedOwner:
             pass
 
 
-class NpSpectra(dict):
-    """Device spectra of this host: a dict (X / P / scale: DeviceBuffer or None; F, W, R, K, C, C_alloc, N; f64; real_input;
-    strides = (frequency, window, trial, taper) in elements or None for the dense [F][W][R][K][C_alloc] layout) with attribute
-    access and the mark Connectivity looks for."""
-    is_device_spectra = True
+class NpSpectra(_stage_abc.Spectra):
+    """Device spectra of this host (geometry and ``desc``: _stage_abc.Spectra): X / P / scale are DeviceBuffers or None, the
+    ``quality`` scalar of the planes format a DeviceArray."""
 
-    def __getattr__(self, name):
-        try:
-            return self[name]
-        except KeyError:
-            raise AttributeError(name) from None
+    def get(self, name, default=None):                      # (sp.get("P"), sp["P"]: the mapping access of the dict this class was)
+        return getattr(self, name, default)
 
-    @property
-    def n_fft(self):
-        return self["N"]
-
-    def desc(self, expectation_type, n_freq=None, padded=False):
-        return NumpyHost._desc(self, expectation_type, padded, n_freq)
+    def __getitem__(self, name):
+        return getattr(self, name)
 
     def free(self):
-        for key in ("X", "P", "scale"):
-            if self.get(key) is not None:
-                self[key].free()
-                self[key] = None
+        for buf in (self._X, self.P, self.scale):
+            if buf is not None:
+                buf.free()
+        self._X = self.P = self.scale = None
 
 
 class NumpyHost:
@@ -300,239 +324,108 @@ class NumpyHost:
         _lib.check(fn(buf.ptr, n, flag.ptr, self.stream), "sc_nonfinite")
         return bool(self.download(flag, (1,), np.int32)[0])
 
-    # ---- stage A ------------------------------------------------------------------------------------------------
+    # ---- stages A to C: the shared drivers of _stage_abc.py through self.memory; what stays here is this host's policy ----------
+    def _series_checks(self, m, what):
+        if np.iscomplexobj(m.time_series):
+            raise TypeError(what)
+        _stage_abc.check_detrend(m.detrend_type)
+
+    def _warn_nonfinite(self, m, x, f64=False):
+        """The constructor's deferred NaN / infinity scan on the uploaded (float32 engine: converted and padded) series."""
+        if getattr(m, "_finite_checked", True) is False and self.has_nonfinite(x.buf, int(np.prod(x.shape)), f64=f64):
+            import warnings
+            warnings.warn(_stage_abc.NONFINITE_WARNING, UserWarning, stacklevel=4)
+
     def spectra(self, multitaper, planes_hint=None):
-        """Stage A for a ``transforms.Multitaper`` (host geometry, tapers): dict with the device spectra
-        X[F][W][R][K][C_alloc] complex64 and their sizes -- or, when the accumulator families ``planes_hint`` the caller will
+        """Stage A for a ``transforms.Multitaper`` (host geometry, tapers): NpSpectra with the device spectra
+        X[F][W][R][K][C_alloc] complex64 -- or, when the accumulator families ``planes_hint`` the caller will
         ask for take it (``_lib.planes_format_applies``), the same coefficients in the planes format of sc_fused2.hip:
         P (rows of sc_planes_row_bytes) + the per-channel scales, X = None."""
-        import warnings
-        m, lib = multitaper, self.lib
-        if np.iscomplexobj(m.time_series):
-            raise TypeError("complex-valued time series: use the PyTorch host (spectral_connectivity_amd.Multitaper), which "
-                            "transforms the real and imaginary parts and assembles the two-sided spectrum")
-        if m.detrend_type not in _lib.DETREND:
-            raise ValueError(f"Invalid trend type '{m.detrend_type}' is not supported.\n"
-                             "Valid options are 'linear'/'l', 'constant'/'c' or None.")
+        m, mem = multitaper, self.memory
+        self._series_checks(m, "complex-valued time series: use the PyTorch host (spectral_connectivity_amd.Multitaper), which "
+                               "transforms the real and imaginary parts and assembles the two-sided spectrum")
         ts = np.asarray(m.time_series)
         T, R, C = ts.shape
-        C_alloc = C + 1 if (C % 2 and C + 1 <= _lib.PLANES_FORMAT_MAX_CHANNELS) else C       # (beyond 256 signals: planes-format requests only)
-        L, step, N, W = m.n_time_samples_per_window, m.n_time_samples_per_step, m.n_fft_samples, m.n_time_windows
-        tapers = np.asarray(m.tapers, dtype=np.float64)                                   # (L, K), * sqrt(fs)
-        K = tapers.shape[1]
-        h = self.upload(np.ascontiguousarray(tapers.T / m.sampling_frequency, dtype=np.float32))
-        if ts.dtype == np.float64 and ts.size:
-            # float64 series: converted on the device, the per-(trial, signal) constant taken out in float64 first
-            xd = self.upload(ts)
-            x = self.alloc(T * R * C_alloc * 4)
-            _lib.check(lib.sc_timeseries_to_f32(xd.ptr, T, R, C, int(m.detrend_type is not None), x.ptr, C_alloc,
-                                                self.stream), "sc_timeseries_to_f32")
-            xd.free()
-        else:
-            xh = np.ascontiguousarray(ts, dtype=np.float32)
-            if C_alloc != C:
-                xh = np.concatenate([xh, np.zeros(xh.shape[:2] + (1,), dtype=np.float32)], axis=2)
-            x = self.upload(xh)
-        if getattr(m, "_finite_checked", True) is False and self.has_nonfinite(x, T * R * C_alloc):
-            warnings.warn("Input time_series contains NaN or infinite values.\n"
-                          "This will produce invalid spectral estimates.", UserWarning, stacklevel=3)
-        F = N // 2 + 1
-        detrend = _lib.DETREND[m.detrend_type]
-        fused = bool(lib.sc_multitaper_fft_supported(L, N))
-        if fused and N not in self._twiddles:
-            tw = self.alloc(N * 8)
-            _lib.check(lib.sc_fft_twiddles_f32(N, tw.ptr, self.stream), "sc_fft_twiddles_f32")
-            self._twiddles[N] = tw
-        if fused and _lib.planes_format_applies(L, N, C_alloc, planes_hint, spectra_bytes=F * W * R * K * C_alloc * 8):
-            # planes format: one scan of the series for the channel scales, then the fused transform writes the f16 pieces
-            P = self.alloc(F * W * R * K * int(lib.sc_planes_row_bytes(C_alloc)))
-            work_bytes = int(lib.sc_planes_scales_work_bytes(T * R, C_alloc))
-            scale, work, rng = self.alloc(2 * C_alloc * 4), self.alloc(work_bytes), self.alloc(4)
-            h32 = np.asarray(tapers.T / m.sampling_frequency, dtype=np.float32)
-            h_abs_sum, h_l2_min = float(np.abs(h32).sum(axis=1).max()), float(np.sqrt((h32.astype(np.float64) ** 2).sum(axis=1)).min())
-            _lib.check(lib.sc_planes_scales_quality_f32(x.ptr, T, R, C_alloc, detrend, h_abs_sum, scale.ptr, work.ptr, work_bytes, rng.ptr,
-                                                        self.stream), "sc_planes_scales_quality_f32")
-            _lib.check(lib.sc_multitaper_fft_planes_f32(x.ptr, T, R, C_alloc, L, step, W, N, h.ptr, K, detrend,
-                                                        self._twiddles[N].ptr, scale.ptr, P.ptr, self.stream),
-                       "sc_multitaper_fft_planes_f32")
-            # the quality check of the format (Multitaper.device_spectra of the PyTorch host does the same): one scale per channel
-            # serves every window, so a channel with samples far outside its usual range keeps complex64
-            ratio = float(self.download(rng, (1,), np.float32)[0]) * h_l2_min
-            work.free(); rng.free()
-            if ratio >= _lib.PLANES_MIN_TYPICAL:
-                for b in (x, h):
-                    b.free()
-                return NpSpectra(X=None, P=P, scale=scale, F=F, W=W, R=R, K=K, C=C, C_alloc=C_alloc, N=N, f64=False, real_input=True,
-                                 strides=None)
-            P.free(); scale.free()
-        X = self.alloc(F * W * R * K * C_alloc * 8)
-        if fused:
-            _lib.check(lib.sc_multitaper_fft_f32(x.ptr, T, R, C_alloc, L, step, W, N, h.ptr, K, detrend,
-                                                 self._twiddles[N].ptr, X.ptr, self.stream), "sc_multitaper_fft_f32")
-        else:
-            batch = W * R * K * C_alloc
-            y = self.alloc(batch * N * 4)
-            _lib.check(lib.sc_taper_windows_f32(x.ptr, T, R, C_alloc, L, step, W, N, h.ptr, K, detrend, y.ptr,
-                                                self.stream), "sc_taper_windows_f32")
-            plan = c_void_p()
-            _lib.check(lib.sc_fft_plan_create(byref(plan), N, batch), "sc_fft_plan_create")
-            try:
-                _lib.check(lib.sc_fft_execute(plan, y.ptr, X.ptr, self.stream), "sc_fft_execute")
-                self.synchronize()
-            finally:
-                lib.sc_fft_plan_destroy(plan)
-            y.free()
-        x.free()
-        h.free()
-        return NpSpectra(X=X, P=None, scale=None, F=F, W=W, R=R, K=K, C=C, C_alloc=C_alloc, N=N, f64=False, real_input=True, strides=None)
+        C_alloc = _lib.padded_channels(C, _lib.PLANES_FORMAT_MAX_CHANNELS)       # (beyond 256 signals: planes-format requests only)
+        h32 = np.ascontiguousarray(np.asarray(m.tapers, dtype=np.float64).T / m.sampling_frequency, dtype=np.float32)   # (K, L)
+        h = mem.upload(h32)
+        x = _stage_abc.upload_series_f32(mem, ts, C_alloc, m.detrend_type)
+        self._warn_nonfinite(m, x)
+
+        def taper_norms():
+            return float(np.abs(h32).sum(axis=1).max()), float(np.sqrt((h32.astype(np.float64) ** 2).sum(axis=1)).min())
+
+        args = (mem, x, h, T, R, C_alloc, C, m.n_time_samples_per_window, m.n_time_samples_per_step, m.n_time_windows, m.n_fft_samples,
+                _lib.DETREND[m.detrend_type])
+        sp = _stage_abc.spectra_f32(*args, planes_hint, taper_norms=taper_norms)
+        if sp.P is not None:
+            # the quality check of the format, read at once (Multitaper.device_spectra of the PyTorch host defers it): one scale per
+            # channel serves every window, so a channel with samples far outside its usual range keeps complex64
+            if not float(mem.download(sp.quality)[0]) * sp.taper_l2_min >= _lib.PLANES_MIN_TYPICAL:
+                sp.free()
+                sp = _stage_abc.spectra_f32(*args, None)
+        return sp
 
     def spectra_f64(self, multitaper):
         """Stage A of the float64 engine (the reference's default dtype): float64 windows, tapers and transform, complex128
-        spectra X[F][W][R][K][C] -- one fused kernel (sc_multitaper_fft_f64) for the lengths it has, sc_taper_windows_f64 +
-        double-precision rocFFT otherwise (engine.multitaper_spectra_f64 of the PyTorch host)."""
-        import warnings
-        m, lib = multitaper, self.lib
-        if np.iscomplexobj(m.time_series):
-            raise TypeError("complex-valued time series: use the PyTorch host (SC_HIP_HOST=torch)")
-        if m.detrend_type not in _lib.DETREND:
-            raise ValueError(f"Invalid trend type '{m.detrend_type}' is not supported.\n"
-                             "Valid options are 'linear'/'l', 'constant'/'c' or None.")
+        spectra X[F][W][R][K][C] (_stage_abc.spectra_f64)."""
+        m, mem = multitaper, self.memory
+        self._series_checks(m, "complex-valued time series: use the PyTorch host (SC_HIP_HOST=torch)")
         ts = np.ascontiguousarray(np.asarray(m.time_series), dtype=np.float64)
         T, R, C = ts.shape
-        L, step, N, W = m.n_time_samples_per_window, m.n_time_samples_per_step, m.n_fft_samples, m.n_time_windows
-        tapers = np.asarray(m.tapers, dtype=np.float64)
-        K = tapers.shape[1]
-        x = self.upload(ts)
-        h = self.upload(np.ascontiguousarray(tapers.T / m.sampling_frequency, dtype=np.float64))
-        if getattr(m, "_finite_checked", True) is False:
-            m._finite_checked = True
-            if self.has_nonfinite(x, T * R * C, f64=True):
-                warnings.warn("Input time_series contains NaN or infinite values.\n"
-                              "This will produce invalid spectral estimates.", UserWarning, stacklevel=3)
-        F = N // 2 + 1
-        detrend = _lib.DETREND[m.detrend_type]
-        X = self.alloc(F * W * R * K * C * 16)
-        if bool(lib.sc_multitaper_fft_f64_supported(L, N)) and R <= 65535 and W <= 65535:
-            _lib.check(lib.sc_multitaper_fft_f64(x.ptr, T, R, C, L, step, W, N, h.ptr, K, detrend, X.ptr, self.stream),
-                       "sc_multitaper_fft_f64")
-        else:
-            batch = W * R * K * C
-            y = self.alloc(batch * N * 8)
-            _lib.check(lib.sc_taper_windows_f64(x.ptr, T, R, C, L, step, W, N, h.ptr, K, detrend, y.ptr, self.stream),
-                       "sc_taper_windows_f64")
-            plan = c_void_p()
-            _lib.check(lib.sc_fft_plan_create_f64(byref(plan), N, batch), "sc_fft_plan_create_f64")
-            try:
-                _lib.check(lib.sc_fft_execute_f64(plan, y.ptr, X.ptr, self.stream), "sc_fft_execute_f64")
-                self.synchronize()
-            finally:
-                lib.sc_fft_plan_destroy(plan)
-            y.free()
-        x.free()
-        h.free()
-        return NpSpectra(X=X, P=None, scale=None, F=F, W=W, R=R, K=K, C=C, C_alloc=C, N=N, f64=True, real_input=True, strides=None)
+        x = mem.upload(ts)
+        h = mem.upload(np.ascontiguousarray(np.asarray(m.tapers, dtype=np.float64).T / m.sampling_frequency, dtype=np.float64))
+        self._warn_nonfinite(m, x, f64=True)
+        m._finite_checked = True
+        return _stage_abc.spectra_f64(mem, x, h, T, R, C, m.n_time_samples_per_window, m.n_time_samples_per_step, m.n_time_windows,
+                                      m.n_fft_samples, _lib.DETREND[m.detrend_type])
 
     def upload_coefficients(self, coef, f64=False):
         """Reference-layout (W, R, K, N, C) complex coefficients -> device spectra that hold all N bins as given
-        (engine.upload_coefficients of the PyTorch host: same strides, the zero pad channel of an odd count in the float32 engine)."""
-        coef = np.asarray(coef)
-        W, R, K, N, C = coef.shape
-        if f64:
-            X = self.upload(np.ascontiguousarray(coef, dtype=np.complex128))
-            return NpSpectra(X=X, P=None, scale=None, F=N, W=W, R=R, K=K, C=C, C_alloc=C, N=N, f64=True, real_input=False,
-                             strides=(C, R * K * N * C, K * N * C, N * C))
-        coef = np.ascontiguousarray(coef, dtype=np.complex64)
-        if C % 2 and C + 1 <= 256:
-            coef = np.concatenate([coef, np.zeros(coef.shape[:-1] + (1,), dtype=np.complex64)], axis=-1)
-        Ca = coef.shape[-1]
-        X = self.upload(coef)
-        return NpSpectra(X=X, P=None, scale=None, F=N, W=W, R=R, K=K, C=C, C_alloc=Ca, N=N, f64=False, real_input=False,
-                         strides=(Ca, R * K * N * Ca, K * N * Ca, N * Ca))
+        (_stage_abc.upload_coefficients: the zero pad channel of an odd count in the float32 engine)."""
+        return _stage_abc.upload_coefficients(self.memory, coef, f64)
 
-    # ---- stages B and C -----------------------------------------------------------------------------------------
-    @staticmethod
-    def _desc(sp, expectation_type, padded, n_freq=None):
-        axes = EXPECTATION_AXES[expectation_type]
-        W, R, K, Ca = sp["W"], sp["R"], sp["K"], sp["C_alloc"]
-        sF, sW, sR, sK = sp.get("strides") or (W * R * K * Ca, R * K * Ca, K * Ca, Ca)
-        return SpectraDesc(n_freq=sp["F"] if n_freq is None else n_freq, n_windows=W, n_trials=R, n_tapers=K,
-                           n_signals=Ca if padded else sp["C"], stride_freq=sF, stride_window=sW, stride_trial=sR, stride_taper=sK,
-                           reduce_window=int(0 in axes), reduce_trial=int(1 in axes), reduce_taper=int(2 in axes),
-                           reserved=0)
+    def _accumulate_record(self, sp, expectation_type, planes, n_freq=None):
+        """accumulate() with the record as a DeviceArray: (record, n_observations)."""
+        if sp.C > 256 and sp.P is None:
+            raise ValueError(f"one launch of the complex64 / float64 stage-B kernels takes n_signals <= 256 (got {sp.C}): Connectivity of this host "
+                             "tiles more signals into channel blocks (numpy_api.Connectivity); NumpyHost.accumulate does not")
+        if sp.P is not None and not _stage_abc.fused2_takes(sp.desc(expectation_type, n_freq, padded=True), planes):
+            raise _lib.HipEngineError("planes-format spectra: this expectation type / plane set needs complex64 spectra "
+                                      "(call spectra() without planes_hint)")
+        return _stage_abc.accumulate(self.memory, sp, expectation_type, planes, n_freq)
 
     def accumulate(self, sp, expectation_type, planes, n_freq=None):
         """Stage B: un-normalised records [n_bins][floats_per_bin] on the device -- float32, or float64 from complex128 spectra
-        (the float64 engine: sc_accumulate_f64).  ``n_freq``: accumulate the first n_freq bins only."""
-        lib = self.lib
-        if sp["C"] > 256 and sp.get("P") is None:
-            raise ValueError(f"one launch of the complex64 / float64 stage-B kernels takes n_signals <= 256 (got {sp['C']}): Connectivity of this host "
-                             "tiles more signals into channel blocks (numpy_api.Connectivity); NumpyHost.accumulate does not")
-        d_real, d_pad = self._desc(sp, expectation_type, False, n_freq), self._desc(sp, expectation_type, True, n_freq)
-        n_bins, fpb, n_groups, n_obs = c_int64(), c_int64(), c_int64(), c_int64()
-        _lib.check(lib.sc_accum_layout(byref(d_real), planes, byref(n_bins), byref(fpb), byref(n_groups), byref(n_obs)),
-                   "sc_accum_layout")
-        if sp.get("f64"):
-            accum = self.alloc(n_bins.value * fpb.value * 8)
-            _lib.check(lib.sc_accumulate_f64(sp["X"].ptr, byref(d_real), planes, planes, accum.ptr, self.stream), "sc_accumulate_f64")
-            return accum, n_bins.value, n_obs.value
-        accum = self.alloc(n_bins.value * fpb.value * 4)
-        if sp.get("P") is not None:
-            # planes format (the families planes_format_applies admits are exactly what sc_fused2.hip accumulates)
-            if not lib.sc_fused2_supported(byref(d_pad), planes):
-                raise _lib.HipEngineError("planes-format spectra: this expectation type / plane set needs complex64 spectra "
-                                          "(call spectra() without planes_hint)")
-            ws_bytes = int(lib.sc_fused_workspace_bytes(byref(d_pad), planes))
-            ws = self.alloc(ws_bytes) if ws_bytes else None
-            _lib.check(lib.sc_fused2_csm_absim_f32(sp["P"].ptr, byref(d_pad), sp["scale"].ptr, planes, accum.ptr,
-                                                   ws.ptr if ws else None, ws_bytes, self.stream), "sc_fused2_csm_absim_f32")
-            if ws:
-                ws.free()
-            return accum, n_bins.value, n_obs.value
-        one_pass = int(lib.sc_fused_planes_covered(byref(d_pad), planes)) if lib.sc_fused_supported(sp["C_alloc"]) else 0
-        X, st = sp["X"].ptr, self.stream
-        if one_pass:
-            ws_bytes = int(lib.sc_fused_workspace_bytes(byref(d_pad), planes))
-            ws = self.alloc(ws_bytes) if ws_bytes else None
-            ws_ptr = ws.ptr if ws else None
-            if one_pass & _lib.PLANE_CSM:
-                _lib.check(lib.sc_fused_csm_absim_ws_f32(X, byref(d_pad), planes, accum.ptr, ws_ptr, ws_bytes, st),
-                           "sc_fused_csm_absim_ws_f32")
-            if one_pass & _lib.PLANE_SIGN_IM:
-                _lib.check(lib.sc_fused_sign_ws_f32(X, byref(d_pad), planes, accum.ptr, ws_ptr, ws_bytes, st),
-                           "sc_fused_sign_ws_f32")
-            if one_pass & _lib.PLANE_UNIT:
-                _lib.check(lib.sc_fused_unit_ws_f32(X, byref(d_pad), planes, accum.ptr, ws_ptr, ws_bytes, None, 0, st),
-                           "sc_fused_unit_ws_f32")
-            if ws:
-                ws.free()
-        elif planes & _lib.PLANE_CSM:
-            _lib.check(lib.sc_csm_accumulate_f32(X, byref(d_real), planes, accum.ptr, st), "sc_csm_accumulate_f32")
-            one_pass = _lib.PLANE_CSM
-        rest = planes & ~one_pass
-        if rest:
-            _lib.check(lib.sc_nonlinear_accumulate_f32(X, byref(d_real), planes, rest, accum.ptr, st),
-                       "sc_nonlinear_accumulate_f32")
-        return accum, n_bins.value, n_obs.value
+        (the float64 engine: sc_accumulate_f64).  ``n_freq``: accumulate the first n_freq bins only.  Returns (DeviceBuffer, n_bins,
+        n_observations)."""
+        rec, n_obs = self._accumulate_record(sp, expectation_type, planes, n_freq)
+        return rec.buf, rec.shape[0], n_obs
 
     # ---- stage D through this host (the drivers of _stage_d.py on float32 records) ------------------------------------------------
-    def _csm_records(self, time_series, expectation_type, multitaper_kwargs):
-        """(spectra geometry, CSM records as a DeviceArray, n_observations, kept axes) of a time series."""
+    def _request(self, time_series, expectation_type, multitaper_kwargs):
+        """The Multitaper of a request of the functional interface, checked before anything is allocated on the device."""
         from .transforms import Multitaper
         if expectation_type not in EXPECTATION_AXES:
             raise ValueError(f"Invalid expectation_type '{expectation_type}'. Must be one of: "
                              + ", ".join(f"'{k}'" for k in EXPECTATION_AXES))
         m = Multitaper(time_series, **multitaper_kwargs)
-        if np.asarray(m.time_series).shape[2] > 256:      # (before anything is allocated on the device)
+        if np.asarray(m.time_series).shape[2] > 256:
             raise ValueError(f"n_signals <= 256 through NumpyHost's functional interface (got {np.asarray(m.time_series).shape[2]}): "
                              "numpy_api.Connectivity (SC_HIP_HOST=numpy) tiles more signals into channel blocks")
+        return m
+
+    def _csm_records(self, time_series, expectation_type, multitaper_kwargs):
+        """(spectra geometry, CSM records as a DeviceArray, n_observations, kept axes) of a time series."""
+        m = self._request(time_series, expectation_type, multitaper_kwargs)
         # (complex64 spectra, like Connectivity._csm_records of the PyTorch host: these consumers read every bin of the CSM once, at
         #  window lengths and channel counts where the planes format buys nothing)
         sp = self.spectra(m, planes_hint=None)
-        accum, n_bins, n_obs = self.accumulate(sp, expectation_type, _lib.PLANE_CSM)
+        accum, n_obs = self._accumulate_record(sp, expectation_type, _lib.PLANE_CSM)
         sp.free()
         axes = EXPECTATION_AXES[expectation_type]
-        kept = tuple(n for i, n in enumerate((sp["W"], sp["R"], sp["K"])) if i not in axes)
-        return sp, DeviceArray(accum, (n_bins, accum.n_bytes // (n_bins * 4)), np.float32), n_obs, kept
+        kept = tuple(n for i, n in enumerate((sp.W, sp.R, sp.K)) if i not in axes)
+        return sp, accum, n_obs, kept
 
     MVAR_MEASURES = {"directed_transfer_function": _lib.MVAR_DTF, "directed_coherence": _lib.MVAR_DC,
                      "partial_directed_coherence": _lib.MVAR_PDC, "generalized_partial_directed_coherence": _lib.MVAR_GPDC,
@@ -549,7 +442,7 @@ class NumpyHost:
             raise ValueError(f"unknown MVAR measures {unknown}; available: {sorted(self.MVAR_MEASURES)}")
         _stage_d.check_max_iterations(max_iterations)
         sp, accum, n_obs, kept = self._csm_records(time_series, expectation_type, multitaper_kwargs)
-        C, F, N = sp["C"], sp["F"], sp["N"]
+        C, F, N = sp.C, sp.F, sp.n_fft
         if C > self.lib.sc_mvar_max_signals():
             raise ValueError(f"the full Wilson factorisation supports n_signals <= {self.lib.sc_mvar_max_signals()} (got {C})")
         G, _, _, summary = _stage_d.mvar_factor(self.memory, accum.shape[0] // F, N, C, accum=accum, n_freq_accum=F,
@@ -563,13 +456,13 @@ class NumpyHost:
         max_rank)) like the reference's ``Connectivity.global_coherence`` (connectivity.py:822-895): the leading eigenpairs of the
         cross-spectral matrix of every (window, two-sided bin) (sc_global_coherence_f64); always over trials and tapers."""
         sp, accum, n_obs, kept = self._csm_records(time_series, "trials_tapers", multitaper_kwargs)
-        C = sp["C"]
+        C = sp.C
         max_rank = int(max_rank)
-        if not 1 <= max_rank <= min(C, sp["R"] * sp["K"]):
-            raise ValueError(f"max_rank must be between 1 and min(n_signals, n_trials * n_tapers) = {min(C, sp['R'] * sp['K'])}")
+        if not 1 <= max_rank <= min(C, sp.R * sp.K):
+            raise ValueError(f"max_rank must be between 1 and min(n_signals, n_trials * n_tapers) = {min(C, sp.R * sp.K)}")
         if C > self.lib.sc_global_coherence_max_signals():
             raise ValueError(f"global_coherence supports n_signals <= {self.lib.sc_global_coherence_max_signals()}")
-        values, vectors = _stage_d.global_coherence(self.memory, accum, sp["W"], sp["F"], sp["N"], C, _lib.PLANE_CSM, n_obs, max_rank,
+        values, vectors = _stage_d.global_coherence(self.memory, accum, sp.W, sp.F, sp.n_fft, C, _lib.PLANE_CSM, n_obs, max_rank,
                                                     ascending=max_rank < C - 1)
         return self.memory.download(values), self.memory.download(vectors)
 
@@ -579,7 +472,7 @@ class NumpyHost:
         1161-1213; out[..., i, j] = j -> i, NaN elsewhere) for all channel pairs or the listed ``pairs``: cross-spectral records
         on the device, batched 2 x 2 Wilson factorisations (sc_granger_pairwise_f64), one download."""
         sp, accum, n_obs, kept = self._csm_records(time_series, expectation_type, multitaper_kwargs)
-        C, F, N = sp["C"], sp["F"], sp["N"]
+        C, F, N = sp.C, sp.F, sp.n_fft
         if pairs is None:
             pairs = [(i, j) for i in range(C) for j in range(i + 1, C)]
         pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
@@ -598,7 +491,7 @@ class NumpyHost:
         """NumPy time series -> (array (n_time_windows, n_frequencies, n_groups, n_groups), sorted labels) like the reference's
         ``Connectivity.canonical_coherence(group_labels)`` (connectivity.py:745-820, 1953-2032; always over trials and tapers)."""
         sp, accum, n_obs, kept = self._csm_records(time_series, "trials_tapers", multitaper_kwargs)
-        C, F, n_bins = sp["C"], sp["F"], accum.shape[0]
+        C, F, n_bins = sp.C, sp.F, accum.shape[0]
         group_labels = np.asarray(group_labels)
         if group_labels.shape != (C,):
             raise ValueError(f"group_labels needs one label per signal ({C}), got shape {group_labels.shape}")
@@ -616,54 +509,38 @@ class NumpyHost:
             sub, self.last_canonical_failures = _stage_d.canonical_coherence(self.memory, accum, C, _lib.PLANE_CSM, n_obs,
                                                                              [groups[k] for k in small])
             res[np.ix_(np.arange(n_bins), small, small)] = self.memory.download(sub)
-        return res.reshape(sp["W"], F, n_g, n_g), labels
+        return res.reshape(sp.W, F, n_g, n_g), labels
 
     def _planes_expectation(self, m, expectation_type, planes):
         """Would sc_fused2.hip take this request?  (asked BEFORE stage A picks the device format of the spectra)"""
         ts = np.asarray(m.time_series)
-        C = ts.shape[2]
-        C_alloc = C + 1 if (C % 2 and C + 1 <= 256) else C
-        geom = dict(F=m.n_fft_samples // 2 + 1, W=m.n_time_windows, R=ts.shape[1], K=np.asarray(m.tapers).shape[1], C=C, C_alloc=C_alloc)
-        return bool(self.lib.sc_fused2_supported(byref(self._desc(geom, expectation_type, True)), planes))
+        return _stage_abc.planes_request_ok(m.n_time_windows, ts.shape[1], np.asarray(m.tapers).shape[1], m.n_fft_samples,
+                                            _lib.padded_channels(ts.shape[2], 256), expectation_type, planes)
 
     def connectivity(self, time_series, measures=("coherence_magnitude",), expectation_type="trials_tapers", **multitaper_kwargs):
         """NumPy time series (n_time, n_trials, n_signals) -> {measure name: NumPy array} shaped like the reference's
         ``Connectivity.<measure>()`` results (non-negative frequencies)."""
-        from .transforms import Multitaper
-        if expectation_type not in EXPECTATION_AXES:
-            raise ValueError(f"Invalid expectation_type '{expectation_type}'. Must be one of: "
-                             + ", ".join(f"'{k}'" for k in EXPECTATION_AXES))
         unknown = [name for name in measures if name not in MEASURES]
-        if unknown:
+        if unknown and expectation_type in EXPECTATION_AXES:           # (an invalid expectation_type is reported first: _request)
             raise ValueError(f"unknown measures {unknown}; available: {sorted(MEASURES)}")
-        m = Multitaper(time_series, **multitaper_kwargs)
-        if np.asarray(m.time_series).shape[2] > 256:      # (before anything is allocated on the device)
-            raise ValueError(f"n_signals <= 256 through NumpyHost's functional interface (got {np.asarray(m.time_series).shape[2]}): "
-                             "numpy_api.Connectivity (SC_HIP_HOST=numpy) tiles more signals into channel blocks")
+        m = self._request(time_series, expectation_type, multitaper_kwargs)
         planes = 0
         for name in measures:
             planes |= _lib.MEASURE_PLANES[MEASURES[name]]
         # (the planes format holds observations as ONE run of rows: the expectation types that reduce every stored axis but
         #  the frequency, or a contiguous tail of them -- sc_fused2_supported decides; anything else takes complex64)
         sp = self.spectra(m, planes_hint=planes if self._planes_expectation(m, expectation_type, planes) else None)
-        accum, n_bins, n_obs = self.accumulate(sp, expectation_type, planes)
-        for key in ("X", "P", "scale"):
-            if sp.get(key) is not None:
-                sp[key].free()
-        C, F = sp["C"], sp["F"]
+        rec, n_obs = self._accumulate_record(sp, expectation_type, planes)
+        sp.free()
+        C, F = sp.C, sp.F
         axes = EXPECTATION_AXES[expectation_type]
-        kept = tuple(n for i, n in enumerate((sp["W"], sp["R"], sp["K"])) if i not in axes)
+        kept = tuple(n for i, n in enumerate((sp.W, sp.R, sp.K)) if i not in axes)
         out = {}
         for name in measures:
-            which = MEASURES[name]
-            tail = (C,) if which == _lib.M_POWER else (C, C)
-            dtype = np.complex128 if which in _lib.COMPLEX_MEASURES else np.float64
-            dev = self.alloc(n_bins * int(np.prod(tail)) * np.dtype(dtype).itemsize)
-            _lib.check(self.lib.sc_measure_f64(accum.ptr, n_bins, C, planes, n_obs, which, dev.ptr, self.stream),
-                       "sc_measure_f64")
-            out[name] = self.download(dev, kept + (F,) + tail, dtype)
-            dev.free()
-        accum.free()
+            dev = _stage_abc.measure(self.memory, rec, C, planes, n_obs, MEASURES[name], wide=True)
+            out[name] = self.download(dev.buf, kept + (F,) + dev.shape[1:], dev.dtype)
+            del dev
+        del rec
         out["frequencies"] = np.asarray(m.frequencies)[:F].copy()
         if F and out["frequencies"][-1] < 0:
             out["frequencies"][-1] = abs(out["frequencies"][-1])

@@ -17,6 +17,8 @@ from scipy.fft import fft as _host_fft
 from scipy.fft import fftfreq, ifft as _host_ifft, next_fast_len
 from scipy.linalg import eigh_tridiagonal
 
+from . import _stage_abc
+
 logger = getLogger(__name__)
 
 # The reference's backend plug point (transforms.py:405-439): SPECTRAL_CONNECTIVITY_ENABLE_GPU == "true" asks for the
@@ -298,8 +300,7 @@ _SHAPE_HELP_2D = (
     "or add the missing axis manually with np.newaxis.")
 
 
-_NONFINITE_WARNING = ("Input time_series contains NaN or infinite values.\n"
-                      "This will produce invalid spectral estimates.")
+_NONFINITE_WARNING = _stage_abc.NONFINITE_WARNING       # (one text for the constructor's scan on either host)
 
 
 class _DeviceSeries:
@@ -563,11 +564,9 @@ class Multitaper:
     # ---- device path ---------------------------------------------------------------------
     def check_device_path(self):
         """What device_spectra checks before it computes anything (Connectivity.from_multitaper defers the transform)."""
-        from . import _lib
+        from . import _lib, _stage_abc
         _lib.require_gpu()
-        if self.detrend_type not in _lib.DETREND:
-            raise ValueError(f"Invalid trend type '{self.detrend_type}' is not supported.\n"
-                             "Valid options are 'linear'/'l', 'constant'/'c' or None.")
+        _stage_abc.check_detrend(self.detrend_type)
 
     def settle_device_checks(self, precision):
         """The read-backs a transform with ``defer_checks=True`` left pending -- the NaN / infinity flag of the constructor's scan
@@ -585,15 +584,23 @@ class Multitaper:
         if flag is not None and vals[0] != 0.0:
             warnings.warn(_NONFINITE_WARNING, UserWarning, stacklevel=4)
         if quality is not None:
-            typical = vals[-1] * l2_min
-            if not typical >= _lib.PLANES_MIN_TYPICAL:
-                self.device_format_note = (
-                    f"the typical coefficient of a channel would be {typical:.3g} in the scaled units of the two-piece f16 "
-                    f"format (limit {_lib.PLANES_MIN_TYPICAL:g}: a sample far outside the channel's usual range): "
-                    "spectra kept as complex64")
-                logger.warning("spectral_connectivity_amd: " + self.device_format_note)
+            if self._planes_format_withdrawn(vals[-1] * l2_min):
                 self._device_spectra[precision] = redo()
                 return False
+        return True
+
+    def _planes_format_withdrawn(self, typical):
+        """The planes format takes ONE scale per channel from the range of its samples: a channel with an artefact hundreds of times
+        its typical amplitude would hold the quiet windows' coefficients near the f16 subnormals.  True (noted and logged) when the
+        ``typical`` coefficient the scale pass measured is below the limit: the caller transforms again, into complex64."""
+        from . import _lib
+        if typical >= _lib.PLANES_MIN_TYPICAL:
+            return False
+        self.device_format_note = (
+            f"the typical coefficient of a channel would be {typical:.3g} in the scaled units of the two-piece f16 "
+            f"format (limit {_lib.PLANES_MIN_TYPICAL:g}: a sample far outside the channel's usual range): "
+            "spectra kept as complex64")
+        logger.warning("spectral_connectivity_amd: " + self.device_format_note)
         return True
 
     def device_spectra(self, device=None, precision=None, planes_hint=None, defer_checks=False):
@@ -621,11 +628,8 @@ class Multitaper:
             self._device_spectra[precision] = numpy_api.multitaper_spectra(self, precision, planes_hint)
         if precision not in self._device_spectra:
             import torch
-            from . import _lib, engine
-            _lib.require_gpu()
-            if self.detrend_type not in _lib.DETREND:
-                raise ValueError(f"Invalid trend type '{self.detrend_type}' is not supported.\n"
-                                 "Valid options are 'linear'/'l', 'constant'/'c' or None.")
+            from . import _lib, _stage_abc, engine
+            self.check_device_path()
             if np.iscomplexobj(self.time_series):
                 # the reference's generic fft takes complex series (transforms.py:1402-1405): see _complex_device_spectra
                 self._device_spectra[precision] = self._complex_device_spectra(device, precision)
@@ -664,7 +668,8 @@ class Multitaper:
                 ts = self.time_series
                 n_signals = ts.shape[2]
                 # (an odd channel count rides on one zero pad channel -- up to the planes format's 1024 signals since round 6, 256 before)
-                n_alloc = n_signals + 1 if (n_signals % 2 and n_signals + 1 <= _lib.PLANES_FORMAT_MAX_CHANNELS) else n_signals
+                n_alloc = _lib.padded_channels(n_signals, _lib.PLANES_FORMAT_MAX_CHANNELS)
+                mem = engine.TorchMemory(dev)
                 if on_device is not None and ts.dtype == np.float32:
                     # already in HBM, float32: used in place (an odd channel count gets its zero pad channel in engine.multitaper_spectra)
                     x = on_device.contiguous()
@@ -675,20 +680,14 @@ class Multitaper:
                     # per-(trial, signal) constant out in float64 BEFORE the cast when a detrend is active -- every window's
                     # own detrend removes any constant, and a DC offset 1e5 times the signal (raw EEG / MEG) would otherwise
                     # cost the float32 copy all but two digits of the signal -- and appends the zero pad channel of odd counts
-                    xd = on_device.contiguous() if on_device is not None else torch.from_numpy(np.ascontiguousarray(ts)).to(dev)
+                    xd = on_device.contiguous() if on_device is not None else mem.upload(ts)
                     device_scan(xd)
-                    x = torch.empty(ts.shape[:2] + (n_alloc,), dtype=torch.float32, device=dev)
-                    _lib.check(_lib.load().sc_timeseries_to_f32(xd.data_ptr(), ts.shape[0], ts.shape[1], n_signals,
-                                                                int(self.detrend_type is not None), x.data_ptr(), n_alloc,
-                                                                torch.cuda.current_stream().cuda_stream), "sc_timeseries_to_f32")
+                    x = _stage_abc.series_to_f32(mem, xd, ts.shape[0], ts.shape[1], n_signals, n_alloc, self.detrend_type)
                     del xd
                 else:
-                    x_host = np.ascontiguousarray(np.asarray(ts), dtype=np.float32)
-                    if n_alloc != n_signals:
-                        # odd channel count: ONE all-zero channel is appended on the host, before the upload, so that the
-                        # rows of the spectra stay 16-byte aligned for the one-pass stage-B kernels (engine.DeviceSpectra)
-                        x_host = np.concatenate([x_host, np.zeros(x_host.shape[:2] + (1,), dtype=np.float32)], axis=2)
-                    x = torch.from_numpy(x_host).to(dev)
+                    # cast on the host, where an odd channel count gets its ONE all-zero channel before the upload, so that the
+                    # rows of the spectra stay 16-byte aligned for the one-pass stage-B kernels (engine.DeviceSpectra)
+                    x = _stage_abc.upload_series_f32(mem, ts, n_alloc, self.detrend_type)
                     device_scan(x)
                 h = torch.from_numpy(np.ascontiguousarray(tapers.T / self.sampling_frequency, dtype=np.float32)).to(dev)
                 sp = engine.multitaper_spectra(
@@ -707,20 +706,10 @@ class Multitaper:
                     checked = sp.P is not None and sp.quality is not None
                     self._deferred_checks[precision] = (pending_flag[0], sp.quality if checked else None,
                                                         sp.taper_l2_min if checked else None, redo_complex64)
-                elif sp.P is not None and sp.quality is not None:
-                    # The planes format takes ONE scale per channel from the range of its samples: a channel with an artefact
-                    # hundreds of times its typical amplitude would hold the quiet windows' coefficients near the f16
-                    # subnormals.  The scale pass measured the typical magnitude on the way; below the limit the transform
-                    # runs again into complex64 (one small read-back: the first transform of an object, never a step of a loop).
-                    typical = sp.planes_typical_coefficient()
-                    if not typical >= _lib.PLANES_MIN_TYPICAL:
-                        self.device_format_note = (
-                            f"the typical coefficient of a channel would be {typical:.3g} in the scaled units of the two-piece f16 "
-                            f"format (limit {_lib.PLANES_MIN_TYPICAL:g}: a sample far outside the channel's usual range): "
-                            "spectra kept as complex64")
-                        logger.warning("spectral_connectivity_amd: " + self.device_format_note)
-                        del sp
-                        sp = redo_complex64()
+                elif sp.P is not None and sp.quality is not None and self._planes_format_withdrawn(sp.planes_typical_coefficient()):
+                    # (one small read-back: the first transform of an object, never a step of a loop)
+                    del sp
+                    sp = redo_complex64()
                 self._device_spectra[precision] = sp
         if not defer_checks and self._deferred_checks:
             self.settle_device_checks(precision)          # (a caller that cannot compute again: settled before it sees the spectra)
@@ -733,7 +722,7 @@ class Multitaper:
         spectrum -- bins 0 .. N/2 as A + i B, the others from the conjugate mirrors of A and B -- into a DeviceSpectra with
         ``real_input=False`` (all N bins stored, like uploaded coefficients)."""
         import torch
-        from . import engine
+        from . import _lib, engine
         ts = np.asarray(self.time_series)
         C = ts.shape[2]
         with warnings.catch_warnings():
@@ -752,7 +741,7 @@ class Multitaper:
         N, F = sp2.n_fft, sp2.F
         A, B = X2[..., :C], X2[..., C:]
         mirror = torch.arange(N - F, 0, -1, device=X2.device)      # bin f = F .. N - 1 takes the conjugate of bin N - f
-        C_alloc = C if (sp2.f64 or C % 2 == 0 or C + 1 > 256) else C + 1
+        C_alloc = C if sp2.f64 else _lib.padded_channels(C, 256)
         X = torch.zeros((N,) + tuple(X2.shape[1:4]) + (C_alloc,), dtype=X2.dtype, device=X2.device)
         X[:F, ..., :C] = A + 1j * B
         if N > F:

@@ -27,6 +27,7 @@ SC_PRECISIONS_TESTS = {
     "test_global_coherence_any_rank_beyond_64_signals", "test_global_coherence_degenerate_eigenvalues_and_the_jacobi_cross_check",
     "test_f14_complex_valued_time_series", "test_silent_and_constant_channels_give_exact_zero_spectra",
     "test_granger_pairs_in_chunks", "test_granger_pairs_in_chunks_on_the_torch_free_host",
+    "test_both_hosts_accumulate_the_same_records_bit_for_bit",
 }
 
 RTOL = 1e-5
@@ -430,6 +431,50 @@ def test_granger_pairs_in_chunks_on_the_torch_free_host(sc, _engine_precision):
     x = chunk_series()
     r = chunked_calls.on_torch_free_host("test_gpu_parity", "granger_chunked_and_whole", _engine_precision, x=x)
     check_granger_chunked(r, x, _engine_precision, "torch-free")
+
+
+def host_records(x):
+    """Scenario of test_both_hosts_accumulate_the_same_records_bit_for_bit, run on either host: the raw accumulator records of one
+    series -- as float32, and as float64 (which the float32 engine converts on the device) -- for the three kernel families of
+    stage B."""
+    import spectral_connectivity_amd as pkg
+    from conftest import device_record
+    from spectral_connectivity_amd import _lib
+    families = {"cross": _lib.PLANE_CSM | _lib.PLANE_ABS_IM | _lib.PLANE_IM_SQ, "unit": _lib.PLANE_UNIT, "sign": _lib.PLANE_SIGN_IM}
+    cases = [(f"{dt.__name__}_{name}", x.astype(dt), 128, planes) for dt in (np.float32, np.float64) for name, planes in families.items()]
+    out = {}
+    for key, series, L, planes in cases:
+        m = pkg.Multitaper(series, sampling_frequency=500.0, time_halfbandwidth_product=3, n_time_samples_per_window=L,
+                           n_time_samples_per_step=L // 2)
+        c = pkg.Connectivity.from_multitaper(m)
+        c._device(planes_hint=planes)                  # (the transform picks the device format for these families, as a measure's request does)
+        out[key] = device_record(c, "trials_tapers", planes)
+    return out
+
+
+def test_both_hosts_accumulate_the_same_records_bit_for_bit(sc, _engine_precision):
+    """Stages A and B are one set of call sequences for both hosts (_stage_abc.py): the same series gives the same raw records,
+    bit for bit, in this process and in a child on the torch-free host -- float32 engine on complex64 spectra, on the planes
+    format (SC_PLANES_MIN_CHANNELS=2) and float64 engine; odd channel count (the pad channel), float32 and float64 input
+    (sc_timeseries_to_f32), the cross-spectral, unit-phasor and sign families.  Not compared: a window length that takes tapered
+    windows + rocFFT (224 samples), because the two processes run different rocFFT builds: libsc_hip.so binds to the
+    librocfft.so.0 already in the process, which is the one PyTorch ships (_lib.load imports torch first) on that host and the
+    ROCm installation's on the torch-free one."""
+    import os
+    rng = np.random.default_rng(41)
+    T, R, C = 512, 5, 7
+    x = rng.standard_normal((T, R, C)) + 0.6 * np.sin(2 * np.pi * 40 * np.arange(T) / 500.0)[:, None, None] * np.cos(np.arange(C))
+    here = host_records(x)
+    there = chunked_calls.on_torch_free_host("test_gpu_parity", "host_records", _engine_precision, x=x)
+    assert sorted(here) == sorted(there) and len(here) == 6
+    # (bit patterns, not values: the zero pad channel of the float32 engine makes the unit-phasor record's pad row and column 0 / 0 =
+    #  NaN like the reference's, in the tile padding no consumer reads -- equal bits on both hosts, but NaN != NaN as values)
+    bits = {4: np.uint32, 8: np.uint64}
+    equal = {key: here[key].shape == there[key].shape and here[key].dtype == there[key].dtype
+             and np.array_equal(here[key].view(bits[here[key].itemsize]), there[key].view(bits[there[key].itemsize])) for key in here}
+    print(f"records of both hosts, {_engine_precision}, planes format forced: {'SC_PLANES_MIN_CHANNELS' in os.environ}: {equal}; "
+          f"NaN entries: { {key: int(np.isnan(rec).sum()) for key, rec in here.items()} }")
+    assert all(equal.values()), [key for key, same in equal.items() if not same]
 
 
 def test_granger_from_uploaded_two_sided_coefficients(sc, golden):

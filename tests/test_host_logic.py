@@ -481,3 +481,238 @@ def test_max_iterations_is_checked_by_every_stage_d_path():
         with pytest.raises(ValueError, match="max_iterations must be between 1 and 1024"):
             _stage_d.check_max_iterations(bad)
     assert _stage_d.check_max_iterations(60) == 60
+
+
+class _RecordingLibrary:
+    """A stand-in for libsc_hip.so under the drivers of _stage_abc.py: every entry point returns 0 (or what ``answers`` names) and
+    logs (name, arguments) after checking the argument count against ``_lib.SYMBOLS``; a SpectraDesc passed by reference is logged as ("desc", n_signals, n_freq)."""
+
+    def __init__(self, **answers):
+        self.answers, self.calls = answers, []
+
+    def __getattr__(self, name):
+        def entry(*args):
+            from spectral_connectivity_amd import _lib
+            assert len(args) == len(_lib.SYMBOLS[name][1]), f"{name}: {len(args)} arguments, the ABI has {len(_lib.SYMBOLS[name][1])}"
+            seen = tuple(("desc", a._obj.n_signals, a._obj.n_freq) if hasattr(getattr(a, "_obj", None), "n_signals") else
+                         getattr(a, "value", a) for a in args)
+            self.calls.append((name, seen))
+            answer = self.answers.get(name, 0)
+            return answer(*args) if callable(answer) else answer
+        return entry
+
+    def names(self, *skip):
+        return [name for name, _ in self.calls if name not in skip]
+
+    def args(self, name):
+        return [a for n, a in self.calls if n == name]
+
+
+def _numpy_memory(dummy_above=1 << 22):
+    import contextlib
+    import ctypes
+
+    from spectral_connectivity_amd import _stage_abc
+
+    class Memory:
+        plans, workspaces = [], []
+
+        def empty(self, shape, dtype):
+            big = int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize > dummy_above
+            return np.empty((1,) if big else shape, dtype)          # (only its address is taken)
+
+        def ptr(self, a, first_row=0):
+            return ctypes.c_void_p(a.ctypes.data + first_row * (a.strides[0] if a.ndim else 0))
+
+        def stream(self):
+            return None
+
+        def is_f64(self, record):
+            return record.dtype == np.float64
+
+        def head(self, a, n):
+            return a[:n]
+
+        def twiddles(self, n_fft):
+            return np.empty(n_fft, np.complex64)
+
+        def workspace(self, n_bytes, owner=None):
+            self.workspaces.append(np.empty(n_bytes, np.uint8) if n_bytes > 0 else None)
+            return self.workspaces[-1]
+
+        @contextlib.contextmanager
+        def fft_plan(self, n_fft, batch, f64=False):
+            self.plans.append((n_fft, batch, f64))
+            yield 77
+
+        def spectra(self, X, dims, strides, n_fft, real_input, C_alloc=None, P=None, scale=None):
+            return _stage_abc.Spectra(X, dims, strides, n_fft, real_input, C_alloc, P, scale,
+                                      f64=X is not None and X.dtype == np.complex128)
+
+    return Memory()
+
+
+def test_stage_a_call_sequences(monkeypatch):
+    """_stage_abc.spectra_f32 / spectra_f64 against the recording library on plain NumPy memory: which entry points run, in which
+    order and with which sizes, for the planes format, the fused transforms and the tapered-windows + rocFFT fallbacks."""
+    from spectral_connectivity_amd import _lib, _stage_abc
+    T, R, K, C, Ca, L, step, N = 64, 2, 2, 3, 4, 32, 16, 32
+    W, F = 3, 17
+    x, h = np.zeros((T, R, Ca), np.float32), np.zeros((K, L), np.float32)
+    queries = ("sc_multitaper_fft_supported", "sc_multitaper_fft_planes_supported", "sc_planes_row_bytes", "sc_multitaper_fft_f64_supported")
+
+    def run(fn, *args, env=None, **answers):
+        kw = {k: answers.pop(k) for k in list(answers) if not k.startswith("sc_")}
+        lib, mem = _RecordingLibrary(**answers), _numpy_memory()
+        monkeypatch.setattr(_lib, "_lib", lib)
+        monkeypatch.delenv("SC_PLANES_FORMAT", raising=False)
+        monkeypatch.delenv("SC_PLANES_MIN_CHANNELS", raising=False)
+        if env:
+            monkeypatch.setenv("SC_PLANES_MIN_CHANNELS", env)
+        return lib, mem, fn(mem, *args, **kw)
+
+    f32_args = (x, h, T, R, Ca, C, L, step, W, N, _lib.DETREND["constant"])
+    cross = _lib.PLANE_CSM | _lib.PLANE_ABS_IM
+    # planes format: work-buffer size from the query, the scan, then the transform; quality still on the device
+    lib, mem, sp = run(_stage_abc.spectra_f32, *f32_args, cross, env="2", taper_norms=lambda: (1.5, 0.25), sc_multitaper_fft_supported=1,
+                       sc_multitaper_fft_planes_supported=1, sc_planes_row_bytes=24, sc_planes_scales_work_bytes=96)
+    assert lib.names(*queries) == ["sc_planes_scales_work_bytes", "sc_planes_scales_quality_f32", "sc_multitaper_fft_planes_f32"]
+    assert lib.args("sc_planes_scales_work_bytes") == [(T * R, Ca)]
+    scan = lib.args("sc_planes_scales_quality_f32")[0]
+    assert scan[1:6] == (T, R, Ca, 1, 1.5) and scan[8] == 96 and scan[9] == sp.quality.ctypes.data
+    assert lib.args("sc_multitaper_fft_planes_f32")[0][1:8] == (T, R, Ca, L, step, W, N)
+    assert sp.X is None and sp.P.nbytes == F * W * R * K * 24 and sp.scale.shape == (2 * Ca,) and sp.taper_l2_min == 0.25
+    assert (sp.F, sp.W, sp.R, sp.K, sp.C, sp.C_alloc, sp.n_fft, sp.strides) == (F, W, R, K, C, Ca, N, (W * R * K * Ca, R * K * Ca, K * Ca, Ca))
+    # the same request without the format's size / channel thresholds lifted, and without a hint: fused complex64
+    for hint in (cross, None):
+        lib, mem, sp = run(_stage_abc.spectra_f32, *f32_args, hint, sc_multitaper_fft_supported=1, sc_multitaper_fft_planes_supported=1)
+        assert lib.names(*queries) == ["sc_multitaper_fft_f32"] and sp.P is None and sp.quality is None
+        assert lib.args("sc_multitaper_fft_f32")[0][1:8] == (T, R, Ca, L, step, W, N) and lib.args("sc_multitaper_fft_f32")[0][12] == sp.X.ctypes.data
+        assert sp.X.shape == (F, W, R, K, Ca) and sp.X.dtype == np.complex64 and not sp.f64
+    # a length the fused kernel does not take: tapered windows, then the FFT through the adapter's plan
+    lib, mem, sp = run(_stage_abc.spectra_f32, *f32_args, cross, env="2", sc_multitaper_fft_supported=0, sc_multitaper_fft_planes_supported=1)
+    assert lib.names(*queries) == ["sc_taper_windows_f32", "sc_fft_execute"] and mem.plans == [(N, W * R * K * Ca, False)]
+    assert lib.args("sc_fft_execute")[0][0] == 77 and lib.args("sc_fft_execute")[0][2] == sp.X.ctypes.data
+    # float64 engine: the fused kernel; beyond 65535 trials the fallback although the kernel has the length (no such array is made)
+    x64, h64 = np.zeros((T, R, C)), np.zeros((K, L))
+    lib, mem, sp = run(_stage_abc.spectra_f64, x64, h64, T, R, C, L, step, W, N, 2, sc_multitaper_fft_f64_supported=1)
+    assert lib.names(*queries) == ["sc_multitaper_fft_f64"] and sp.f64 and sp.X.shape == (F, W, R, K, C) and sp.C_alloc == C
+    lib, mem, sp = run(_stage_abc.spectra_f64, x64[:, :1], h64, T, 65536, C, L, step, W, N, 2, sc_multitaper_fft_f64_supported=1)
+    assert lib.names(*queries) == ["sc_taper_windows_f64", "sc_fft_execute_f64"] and mem.plans == [(N, W * 65536 * K * C, True)]
+    assert sp.R == 65536 and sp.strides == (W * 65536 * K * C, 65536 * K * C, K * C, C)
+    lib, mem, sp = run(_stage_abc.spectra_f64, x64, h64, T, R, C, L, step, W, N, 2, sc_multitaper_fft_f64_supported=0)
+    assert lib.names(*queries) == ["sc_taper_windows_f64", "sc_fft_execute_f64"] and mem.plans == [(N, W * R * K * C, True)]
+
+
+def test_stage_b_call_sequences(monkeypatch):
+    """_stage_abc.accumulate against the recording library: the float64 call and its ``which``, the planes-format calls (folded with
+    the workspace, unfolded with the part count the library reports), the one-pass complex64 kernels with their leftover, the
+    per-plane kernels -- and which descriptor (pad channel counted or not) each call gets."""
+    from spectral_connectivity_amd import _lib, _stage_abc
+    F, W, R, K, C, Ca = 17, 3, 2, 2, 3, 4
+    n_bins, fpb, n_obs = 5, 8, 4
+    CSM, ABS, SQ, SIGN, UNIT = _lib.PLANE_CSM, _lib.PLANE_ABS_IM, _lib.PLANE_IM_SQ, _lib.PLANE_SIGN_IM, _lib.PLANE_UNIT
+    strides = _stage_abc.dense_strides(W, R, K, Ca)
+    padded, real = ("desc", Ca, F), ("desc", C, F)
+
+    def layout(d, planes, a, b, c, e):
+        a._obj.value, b._obj.value, c._obj.value, e._obj.value = n_bins, fpb, 1, n_obs
+        return 0
+
+    def run(sp, planes, **kw):
+        answers = {k: kw.pop(k) for k in list(kw) if k.startswith("sc_")}
+        lib, mem = _RecordingLibrary(sc_accum_layout=layout, **answers), _numpy_memory()
+        monkeypatch.setattr(_lib, "_lib", lib)
+        rec, got_obs = _stage_abc.accumulate(mem, sp, "trials_tapers", planes, **kw)
+        assert got_obs == n_obs and lib.names()[0] == "sc_accum_layout" and lib.args("sc_accum_layout")[0][0] == real
+        return lib, mem, rec
+
+    mem = _numpy_memory()
+    X64 = mem.spectra(np.zeros((F, W, R, K, C), np.complex128), (F, W, R, K, C), _stage_abc.dense_strides(W, R, K, C), 32, True)
+    X32 = mem.spectra(np.zeros((F, W, R, K, Ca), np.complex64), (F, W, R, K, C), strides, 32, True, C_alloc=Ca)
+    P32 = mem.spectra(None, (F, W, R, K, C), strides, 32, True, C_alloc=Ca, P=np.zeros(64, np.uint8), scale=np.zeros(2 * Ca, np.float32))
+    # float64 engine: everything, or the families the caller has not filled in ``out`` already
+    lib, _, rec = run(X64, CSM | ABS)
+    assert lib.names() == ["sc_accum_layout", "sc_accumulate_f64"] and rec.shape == (n_bins, fpb) and rec.dtype == np.float64
+    assert lib.args("sc_accumulate_f64")[0][1:4] == (real, CSM | ABS, CSM | ABS)
+    out = np.zeros((n_bins, fpb))
+    lib, _, rec = run(X64, CSM | ABS, which=ABS, out=out)
+    assert rec is out and lib.args("sc_accumulate_f64")[0][1:5] == (real, CSM | ABS, ABS, out.ctypes.data)
+    assert run(X64, CSM, which=0, out=out)[0].names() == ["sc_accum_layout"]
+    # planes format, folded: the adapter's workspace, its pointer and size
+    lib, mem, rec = run(P32, CSM | ABS, workspace_owner="owner", sc_fused2_supported=1, sc_fused_workspace_bytes=400)
+    assert lib.names() == ["sc_accum_layout", "sc_fused2_supported", "sc_fused_workspace_bytes", "sc_fused2_csm_absim_f32"]
+    call = lib.args("sc_fused2_csm_absim_f32")[0]
+    assert call[1] == padded and call[3:7] == (CSM | ABS, rec.ctypes.data, mem.workspaces[0].ctypes.data, 400) and rec.dtype == np.float32
+    # planes format, unfolded: room for 1 + 400 // 160 parts, two of them used
+    def two_parts(*args):
+        args[7]._obj.value = 2
+        return 0
+    lib, mem, rec = run(P32, CSM | ABS, fold=False, sc_fused2_supported=1, sc_fused_workspace_bytes=400, sc_fused2_csm_absim_parts_f32=two_parts)
+    assert lib.names()[-1] == "sc_fused2_csm_absim_parts_f32" and not mem.workspaces and rec.shape == (2, n_bins, fpb)
+    call = lib.args("sc_fused2_csm_absim_parts_f32")[0]
+    assert call[1] == padded and call[4] == rec.ctypes.data and call[5] == rec.ctypes.data + n_bins * fpb * 4 and call[6] == 2 * n_bins * fpb * 4
+    assert run(P32, CSM | ABS, fold=False, sc_fused2_supported=1, sc_fused_workspace_bytes=100)[0].names()[-1] == "sc_fused2_csm_absim_f32"
+    # one-pass complex64 kernels: what they cover on the padded descriptor, the leftover family on the real one
+    every = CSM | ABS | SIGN | UNIT | SQ
+    lib, mem, rec = run(X32, every, sc_fused_supported=1, sc_fused_planes_covered=every & ~SQ, sc_fused_workspace_bytes=64)
+    assert lib.names() == ["sc_accum_layout", "sc_fused_supported", "sc_fused_planes_covered", "sc_fused_workspace_bytes",
+                           "sc_fused_csm_absim_ws_f32", "sc_fused_sign_ws_f32", "sc_fused_unit_scratch_bytes", "sc_fused_unit_ws_f32",
+                           "sc_nonlinear_accumulate_f32"]
+    for name in ("sc_fused_csm_absim_ws_f32", "sc_fused_sign_ws_f32", "sc_fused_unit_ws_f32"):
+        assert lib.args(name)[0][1:6] == (padded, every, rec.ctypes.data, mem.workspaces[0].ctypes.data, 64), name
+    assert lib.args("sc_fused_unit_ws_f32")[0][6:8] == (None, 0) and lib.args("sc_fused_supported") == [(Ca,)]
+    assert lib.args("sc_nonlinear_accumulate_f32")[0][1:4] == (real, every, SQ)
+    # every plane through its own kernel on request: no unit-phasor MFMA pass
+    lib, _, _ = run(X32, every, use_fused=False)
+    assert lib.names() == ["sc_accum_layout", "sc_csm_accumulate_f32", "sc_nonlinear_accumulate_f32"]
+    assert lib.args("sc_csm_accumulate_f32")[0][1] == real and lib.args("sc_nonlinear_accumulate_f32")[0][1:4] == (real, every, every & ~CSM)
+    # a channel count the one-pass kernels do not take: CSM and the unit phasors on the f32 matrix cores, the rest on the VALU
+    lib, _, _ = run(X32, every, sc_fused_supported=0, sc_unit_scratch_bytes=48)
+    assert lib.names() == ["sc_accum_layout", "sc_fused_supported", "sc_csm_accumulate_f32", "sc_unit_scratch_bytes", "sc_unit_accumulate_f32",
+                           "sc_nonlinear_accumulate_f32"]
+    assert lib.args("sc_unit_accumulate_f32")[0][1] == real and lib.args("sc_unit_accumulate_f32")[0][5] == 48
+    assert lib.args("sc_nonlinear_accumulate_f32")[0][1:4] == (real, every, every & ~CSM & ~UNIT)
+
+
+def test_stage_c_call_sequences(monkeypatch):
+    """_stage_abc.measure / measure_multi against the recording library: shape and dtype of every kind of output, narrow and wide,
+    the forms that sum partial records while they read, and the one-launch epilogue falling back to single calls."""
+    from spectral_connectivity_amd import _lib, _stage_abc
+    n_bins, fpb, C, n_obs = 5, 8, 3, 4
+    lib, mem = _RecordingLibrary(), _numpy_memory()
+    monkeypatch.setattr(_lib, "_lib", lib)
+    rec = np.zeros((n_bins, fpb), np.float32)
+    for which, tail, kinds in ((_lib.M_POWER, (C,), (np.float32, np.float64)), (_lib.M_COHERENCY, (C, C), (np.complex64, np.complex128)),
+                               (_lib.M_WPLI, (C, C), (np.float32, np.float64))):
+        for wide in (False, True):
+            out = _stage_abc.measure(mem, rec, C, _lib.PLANE_CSM, n_obs, which, wide)
+            assert out.shape == (n_bins,) + tail and out.dtype == kinds[wide]
+            name, args = lib.calls[-1]
+            assert name == ("sc_measure_f64" if wide else "sc_measure_f32")
+            assert args[:7] == (rec.ctypes.data, n_bins, C, _lib.PLANE_CSM, n_obs, which, out.ctypes.data)
+    assert _stage_abc.measure(mem, np.zeros((n_bins, fpb)), C, _lib.PLANE_CSM, n_obs, _lib.M_POWER, True) is not None
+    assert lib.calls[-1][1][3] == _lib.PLANE_CSM | _lib.RECORD_F64
+    parts = np.zeros((3, n_bins, fpb), np.float32)
+    out = _stage_abc.measure(mem, parts[0], C, _lib.PLANE_CSM, n_obs, _lib.M_COHERENCY, True, parts=parts)
+    name, args = lib.calls[-1]
+    assert name == "sc_measure_parts" and out.dtype == np.complex128
+    assert args[:11] == (parts.ctypes.data, parts[1].ctypes.data, 3, n_bins * fpb, n_bins, C, _lib.PLANE_CSM, n_obs, _lib.M_COHERENCY,
+                         out.ctypes.data, 1)
+    # several measures: one launch for two to four real-valued C x C ones, single calls otherwise
+    two = [_lib.M_COHERENCE_MAGNITUDE, _lib.M_WPLI]
+    del lib.calls[:]
+    outs = _stage_abc.measure_multi(mem, rec, C, _lib.PLANE_CSM, n_obs, two, False)
+    assert lib.names() == ["sc_measure_multi_f32"] and [o.shape for o in outs] == [(n_bins, C, C)] * 2 and outs[0].dtype == np.float32
+    args = lib.calls[-1][1]
+    assert args[:6] == (rec.ctypes.data, n_bins, C, _lib.PLANE_CSM, n_obs, 2) and list(args[6]) == two
+    assert [args[7][k] for k in range(2)] == [o.ctypes.data for o in outs]
+    del lib.calls[:]
+    outs = _stage_abc.measure_multi(mem, parts[0], C, _lib.PLANE_CSM, n_obs, two[:1], True, parts=parts)
+    assert lib.names() == ["sc_measure_multi_parts"] and outs[0].dtype == np.float64
+    assert lib.calls[-1][1][:4] == (parts.ctypes.data, parts[1].ctypes.data, 3, n_bins * fpb) and lib.calls[-1][1][8] == 1
+    for which in (two[:1], two + [_lib.M_PLV, _lib.M_PLI, _lib.M_PPC], two + [_lib.M_COHERENCY]):
+        del lib.calls[:]
+        outs = _stage_abc.measure_multi(mem, rec, C, _lib.PLANE_CSM, n_obs, which, True)
+        assert lib.names() == ["sc_measure_f64"] * len(which) and [a[5] for a in lib.args("sc_measure_f64")] == which
+        assert [o.dtype for o in outs] == [np.complex128 if w == _lib.M_COHERENCY else np.float64 for w in which]
