@@ -194,13 +194,8 @@ __device__ __forceinline__ bf16x8 fu_ld8(const unsigned short* ptr) {
     return __builtin_bit_cast(bf16x8, u);
 }
 
-// Workgroup barrier that publishes LDS writes only.  __syncthreads() would also drain vmcnt, i.e. make
-// every wave sit out the HBM->LDS row loads that were just put in flight for a later chunk.
-#define FU_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-
 #define FU_MFMA(a, b, c) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
 
-static_assert(2 * 4 + 1 <= FU_FLUSH, "one fold slot per tile of a wave");
 // The two roles are separate functions so their accumulators never coexist in registers.
 // Both execute the same barrier sequence: one before the first chunk, one per chunk, then
 // 2*log2(waves per set).
@@ -532,7 +527,7 @@ __global__ void __launch_bounds__(FU_THREADS) fused_csm_absim_kernel(FusedArgs p
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // n_split workgroups per bin (consecutive workgroups land on consecutive XCDs); part k sums its
     // share of the observation chunks into its own record: part 0 into the caller's, the others into
-    // the workspace, folded in afterwards by fused_combine_kernel in a fixed order.
+    // the workspace, folded in afterwards by fused_fold_kernel in a fixed order.
     const int bin = blockIdx.x / p.n_split, part = blockIdx.x - bin * p.n_split;
     const int g = bin / p.F, f = bin - g * p.F;
     ScStage st = p.st;
@@ -558,27 +553,10 @@ __global__ void __launch_bounds__(FU_THREADS) fused_csm_absim_kernel(FusedArgs p
     }
 }
 
-// accum[bin][plane] += ws[0][bin][plane] + ws[1][bin][plane] + ... for the CSM (re, im) and (if present) |Im| planes
-__global__ void __launch_bounds__(256) fused_combine_kernel(FusedArgs p) {
+// accum[bin][plane] += ws[0][bin][plane] + ws[1][bin][plane] + ... for the record planes p.fold[] of a pass: the CSM
+// planes (re, im) and |Im s| of the headline pass, the one plane of a plane pass, whatever the small-channel kernel wrote
+__global__ void __launch_bounds__(256) fused_fold_kernel(FusedArgs p) {
     const int64_t plane = (int64_t)p.n_tiles * SC_TILE_ELEMS;      // floats per plane (multiple of 256)
-    const int64_t per_bin = (p.abs_plane >= 0 ? 3 : 2) * plane / 4;   // float4 items per bin
-    const int64_t total = per_bin * p.n_bins;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t bin = i / per_bin, e = (i - bin * per_bin) * 4;
-        const int64_t off = bin * p.floats_per_bin +
-                            (e < 2 * plane ? (int64_t)p.csm_plane * plane + e : (int64_t)p.abs_plane * plane + (e - 2 * plane));
-        float4 a = *reinterpret_cast<const float4*>(p.accum + off);
-        for (int k = 0; k + 1 < p.n_split; ++k) {
-            const float4 b = *reinterpret_cast<const float4*>(p.ws + (int64_t)k * p.n_bins * p.floats_per_bin + off);
-            a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
-        }
-        *reinterpret_cast<float4*>(p.accum + off) = a;
-    }
-}
-
-// the same fold for an arbitrary list of planes (small-channel kernel)
-__global__ void __launch_bounds__(256) planes_combine_kernel(FusedArgs p) {
-    const int64_t plane = (int64_t)p.n_tiles * SC_TILE_ELEMS;
     const int64_t per_bin = p.n_fold * plane / 4;                  // float4 items per bin
     const int64_t total = per_bin * p.n_bins;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
@@ -594,50 +572,33 @@ __global__ void __launch_bounds__(256) planes_combine_kernel(FusedArgs p) {
     }
 }
 
-int sc_internal_fused_combine(const FusedArgs& a, int op, hipStream_t stream) {
+int sc_internal_fused_combine(const FusedArgs& a, hipStream_t stream) {
     if (a.n_split > 1) {
-        if (op == FU_OP_ABS || op == FU_OP_UNIT) hipLaunchKernelGGL(fused_combine_kernel, dim3(2048), dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL(planes_combine_kernel, dim3(2048), dim3(256), 0, stream, a);     // one plane: a.fold
+        hipLaunchKernelGGL(fused_fold_kernel, dim3(2048), dim3(256), 0, stream, a);
         SC_CHECK_HIP(hipGetLastError());
     }
     return SC_OK;
 }
 
-template <int NB32, int COL_LO, int ROW_HI, int OP>
-static int launch_fused_op(const FusedArgs& a, bool combine, hipStream_t stream) {
-    size_t shmem = (size_t)2 * a.st.CP * FU_CSTRIDE * 2;
-    const size_t red = (size_t)4 * FU_MAXB * 16 * 64 * sizeof(float);
-    if (shmem < red) shmem = red;
-    shmem += (size_t)FU_OC * FU_RAW_ROW * sizeof(float);
-    auto k = fused_csm_absim_kernel<NB32, COL_LO, ROW_HI, OP>;
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    hipLaunchKernelGGL(k, dim3((unsigned)(a.n_bins * a.n_split)), dim3(FU_THREADS), shmem, stream, a);
-    SC_CHECK_HIP(hipGetLastError());
-    return combine ? sc_internal_fused_combine(a, OP, stream) : SC_OK;
-}
-
 // One pass of the matrix-core kernel: op = FU_OP_ABS is the headline launch (CSM planes, and |Im s| if a.abs_plane >= 0);
-// FU_OP_SQ / FU_OP_SIGN are plane passes (a.csm_plane = -1, a.abs_plane = the plane to fill): the abs waves accumulate
-// d^2 / sign(d) of the same per-observation matrix-core products, the CSM waves only stage.
-// The launch shapes that exist (staged blocks, first block column, block rows): the triangles of 1 ... 4 blocks for up
-// to 128 channels, and the staircases launch_fused_all covers 129 ... 256 channels with.
-#define FU_SHAPES(X) X(1, 0, 1) X(2, 0, 2) X(3, 0, 3) X(4, 0, 4) X(4, 2, 2) X(3, 1, 3) X(4, 2, 4) X(4, 1, 4) X(4, 1, 1)
-static int launch_fused(const FusedArgs& a, int op, hipStream_t stream, bool combine) {
-    const int shape = a.NB32 * 100 + a.shape_col_lo * 10 + a.shape_row_hi;
-#define FU_CASE(NB32, COL_LO, ROW_HI)                                                                          \
-    case NB32 * 100 + COL_LO * 10 + ROW_HI:                                                                    \
-        if (op == FU_OP_SQ) return launch_fused_op<NB32, COL_LO, ROW_HI, FU_OP_SQ>(a, combine, stream);        \
-        if (op == FU_OP_SIGN) return launch_fused_op<NB32, COL_LO, ROW_HI, FU_OP_SIGN>(a, combine, stream);    \
-        if (op == FU_OP_UNIT) return launch_fused_op<NB32, COL_LO, ROW_HI, FU_OP_UNIT>(a, combine, stream);    \
-        return launch_fused_op<NB32, COL_LO, ROW_HI, FU_OP_ABS>(a, combine, stream);
-    switch (shape) {
-        FU_SHAPES(FU_CASE)
-    default:
-        sc_set_error("fused kernel: no launch shape (%d staged blocks, column %d, %d rows)", a.NB32, a.shape_col_lo, a.shape_row_hi);
-        return SC_EINVAL;
+// FU_OP_SQ / FU_OP_SIGN are plane passes (fu_plane_pass: a.csm_plane = -1, a.abs_plane = the plane to fill): the abs waves
+// accumulate d^2 / sign(d) of the same per-observation matrix-core products, the CSM waves only stage.
+struct FusedLaunch {
+    static constexpr bool UNIT = true, PLANES_SHAPES = false;
+    static constexpr const char* NAME = "fused kernel";
+    template <int NB32, int COL_LO, int ROW_HI, int OP>
+    static int launch(const FusedArgs& a, hipStream_t stream) {
+        size_t shmem = (size_t)2 * a.st.CP * FU_CSTRIDE * 2;
+        const size_t red = (size_t)4 * FU_MAXB * 16 * 64 * sizeof(float);
+        if (shmem < red) shmem = red;
+        shmem += (size_t)FU_OC * FU_RAW_ROW * sizeof(float);
+        auto k = fused_csm_absim_kernel<NB32, COL_LO, ROW_HI, OP>;
+        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+        hipLaunchKernelGGL(k, dim3((unsigned)(a.n_bins * a.n_split)), dim3(FU_THREADS), shmem, stream, a);
+        SC_CHECK_HIP(hipGetLastError());
+        return SC_OK;
     }
-#undef FU_CASE
-}
+};
 
 // ---- up to 48 channels (58 for the planes with no matrix-core form): f32 VALU kernel -------------------------
 // The MFMA kernel above stages 32-row chunks of 32-channel blocks whatever C is, so its cost per observation row
@@ -817,10 +778,7 @@ static void launch_small_inst(const FusedArgs& a, hipStream_t stream) {
 }
 
 static int launch_small(const FusedArgs& a_in, bool normalize, hipStream_t stream) {
-    FusedArgs a = a_in;
-    a.n_fold = 0;
-    if (a.csm_plane >= 0) { a.fold[a.n_fold++] = a.csm_plane; a.fold[a.n_fold++] = a.csm_plane + 1; }
-    if (a.abs_plane >= 0) a.fold[a.n_fold++] = a.abs_plane;
+    FusedArgs a = a_in;                       // (a.fold: the headline's planes; the ones that ride along are folded with them)
     if (a.sq_plane >= 0) a.fold[a.n_fold++] = a.sq_plane;
     if (a.sign_plane >= 0) a.fold[a.n_fold++] = a.sign_plane;
     if (normalize) launch_small_inst<false, false, false, true>(a, stream);
@@ -829,11 +787,7 @@ static int launch_small(const FusedArgs& a_in, bool normalize, hipStream_t strea
     else if (a.abs_plane >= 0) launch_small_inst<true, false, false, false>(a, stream);
     else launch_small_inst<false, false, false, false>(a, stream);
     SC_CHECK_HIP(hipGetLastError());
-    if (a.n_split > 1) {
-        hipLaunchKernelGGL(planes_combine_kernel, dim3(2048), dim3(256), 0, stream, a);
-        SC_CHECK_HIP(hipGetLastError());
-    }
-    return SC_OK;
+    return sc_internal_fused_combine(a, stream);
 }
 
 // d_X may be NULL when only the shape is known: alignment is then assumed.
@@ -887,6 +841,15 @@ int sc_internal_fused_pick_split(int n_bins, int n_obs) {
     if (e && atoi(e) >= 1 && atoi(e) <= 24 && (atoi(e) == 1 || nc / atoi(e) >= 1)) best = atoi(e);
     return best;
 }
+// The parts per bin of one call: as many of the picked ones as the workspace allows (none: one workgroup per bin).
+int sc_internal_fused_set_parts(FusedArgs* a, int n_obs, void* d_workspace, int64_t workspace_bytes) {
+    int S = d_workspace ? sc_internal_fused_pick_split(a->n_bins, n_obs) : 1;
+    while (S > 1 && (int64_t)(S - 1) * fu_part_bytes(*a) > workspace_bytes) --S;
+    SC_REQUIRE(S == 1 || ((uintptr_t)d_workspace % 16) == 0, "workspace must be 16-byte aligned");
+    a->n_split = S;
+    a->ws = (float*)d_workspace;
+    return SC_OK;
+}
 
 // The CSM waves' share of a launch: R = the tile rows that have tiles, row r with the columns max(r, col_lo) ... NB-1.
 // Five or more rows: wave w takes rows w and R-1-w (long with short: the triangle's 9 tiles per wave at 128 channels);
@@ -916,64 +879,27 @@ void sc_internal_fu_assign_rows(FusedArgs* a) {
     a->seg0 = packed[0]; a->seg1 = packed[1]; a->seg2 = packed[2]; a->seg3 = packed[3];
 }
 
-// One launch that stages the nb (<= 4) 32-channel blocks `blocks` (ascending block numbers of the record's channels) and
-// owns the products (bi <= bj, bj >= col_lo, bi < row_hi) of them.
-static FusedArgs fu_args_blocks(const FusedArgs& full, const int* blocks, int nb, int col_lo, int row_hi) {
+// One launch of the plan: the rows are read from the first staged block on (off32 relative to it), as a stage of the
+// staged channels alone.
+static FusedArgs fu_args_blocks(const FusedArgs& full, const FuLaunch& l) {
     FusedArgs a = full;
-    const int C = full.st.C, c_lo = blocks[0] * 32;
-    a.st.base = full.st.base + c_lo;
-    int staged = 0, n_last = 0;
-    a.map.off32 = a.map.n32 = a.map.t32 = 0u;
-    for (int b = 0; b < nb; ++b) {
-        const int c = blocks[b] * 32;
-        n_last = C - c < 32 ? C - c : 32;
-        a.map.off32 |= (unsigned)(blocks[b] - blocks[0]) << (8 * b);
-        a.map.n32 |= (unsigned)n_last << (8 * b);
-        a.map.t32 |= (unsigned)(blocks[b] * 2) << (8 * b);
-        staged += n_last;
-    }
-    a.st.C = staged;
-    a.NB32 = nb;
-    a.NB = 2 * (nb - 1) + (n_last + 15) / 16;      // 16-channel tiles that exist (the last block may be partial)
-    a.shape_col_lo = col_lo;
-    a.shape_row_hi = row_hi;
-    a.n_blocks32 = fu_nblocks(nb, col_lo, row_hi);
-    a.n_sets = fu_nsets(nb, col_lo, row_hi);
-    a.st.CP = nb * 32;
+    fu_fill_block_map(&a, full.st.C, l, l.blocks[0]);
+    a.st.base = full.st.base + l.blocks[0] * 32;
+    a.st.C = 0;
+    for (int b = 0; b < l.nb; ++b) a.st.C += fu_byte(a.map.n32, b);
     a.st.RS = sc_row_stride(a.st.CP);
-    a.map.NBr = sc_n_blocks(C);
-    a.map.col_lo = 2 * col_lo;
-    a.map.row_hi = 2 * row_hi;
-    sc_internal_fu_assign_rows(&a);
     return a;
 }
-static int launch_fused(const FusedArgs& a, int op, hipStream_t stream, bool combine);
-// Every tile of the record once.  Up to 128 channels: one launch, the triangle of its 1 ... 4 blocks.  Above, a launch
-// can stage four of the n = 5 ... 8 blocks at a time, and the n (n + 1) / 2 block products are dealt over launches so
-// that few blocks are staged twice (each staging reads its channels from HBM again):
-//   n = 5   triangle {0,1,2};  {0,1} x {3,4};  {2} x {3,4} + triangle {3,4}                        15 products, 10 staged
-//   n = 6   triangle {0,1,2,3};  {0,1} x {4,5} + triangle {4,5};  {2,3} x {4,5}                     21 products, 12 staged
-//   n = 7   triangle {0,1,2,3};  {0} x {4,5,6} + triangle {4,5,6};  {1}, {2}, {3} x {4,5,6}         28 products, 20 staged
-//   n = 8   triangle {0..3};  triangle {4..7};  {0,1}, {2,3} x {4,5}, {6,7}                         36 products, 24 staged
-// (round 2 ran every count in 129 ... 255 as n = 8: 160 channels cost what 256 do).  The split-bin partial records are
-// folded once at the end.
+// Every tile of the record once (fu_plan; at most eight blocks: fused_ok), then the split-bin partial records folded once.
 static int launch_fused_all(const FusedArgs& full, int op, hipStream_t s) {
-    const int C = full.st.C, n = (C + 31) / 32;
-    struct Plan { int nb, blocks[4], col_lo, row_hi; };
-    static const Plan tri[4] = {{1, {0}, 0, 1}, {2, {0, 1}, 0, 2}, {3, {0, 1, 2}, 0, 3}, {4, {0, 1, 2, 3}, 0, 4}};
-    static const Plan p5[] = {{3, {0, 1, 2}, 0, 3}, {4, {0, 1, 3, 4}, 2, 2}, {3, {2, 3, 4}, 1, 3}};
-    static const Plan p6[] = {{4, {0, 1, 2, 3}, 0, 4}, {4, {0, 1, 4, 5}, 2, 4}, {4, {2, 3, 4, 5}, 2, 2}};
-    static const Plan p7[] = {{4, {0, 1, 2, 3}, 0, 4}, {4, {0, 4, 5, 6}, 1, 4}, {4, {1, 4, 5, 6}, 1, 1},
-                              {4, {2, 4, 5, 6}, 1, 1}, {4, {3, 4, 5, 6}, 1, 1}};
-    static const Plan p8[] = {{4, {0, 1, 2, 3}, 0, 4}, {4, {4, 5, 6, 7}, 0, 4}, {4, {0, 1, 4, 5}, 2, 2},
-                              {4, {0, 1, 6, 7}, 2, 2}, {4, {2, 3, 4, 5}, 2, 2}, {4, {2, 3, 6, 7}, 2, 2}};
-    const Plan* plan = n <= 4 ? &tri[n - 1] : n == 5 ? p5 : n == 6 ? p6 : n == 7 ? p7 : p8;
-    const int n_launch = n <= 4 ? 1 : n == 5 ? 3 : n == 6 ? 3 : n == 7 ? 5 : 6;
+    FuLaunch plan[FU_PLAN_MAX_LAUNCHES];
+    const int n_launch = fu_plan((full.st.C + 31) / 32, plan);
     int rc = SC_OK;
-    for (int l = 0; l < n_launch && rc == SC_OK; ++l)
-        rc = launch_fused(fu_args_blocks(full, plan[l].blocks, plan[l].nb, plan[l].col_lo, plan[l].row_hi), op, s, false);
-    if (rc == SC_OK) rc = sc_internal_fused_combine(full, op, s);
-    return rc;
+    for (int l = 0; l < n_launch && rc == SC_OK; ++l) {
+        const FusedArgs a = fu_args_blocks(full, plan[l]);
+        rc = fu_dispatch<FusedLaunch>(a, a, op, s);
+    }
+    return rc == SC_OK ? sc_internal_fused_combine(full, s) : rc;
 }
 
 enum { FU_MODE_CSM = 0, FU_MODE_UNIT = 1, FU_MODE_SIGN = 2 };
@@ -988,32 +914,20 @@ static int fused_setup(const void* d_X, const sc_spectra_desc* desc, uint32_t pl
         sc_set_error("fused CSM+|Im| kernel needs an even n_signals <= 256 and 16-byte aligned rows (got C=%d)", ax->C);
         return SC_EUNSUPPORTED;
     }
-    a->NB = sc_n_blocks(ax->C);
-    a->n_tiles = sc_n_tiles(a->NB);
-    a->NB32 = (ax->C + 31) / 32;
+    fu_record_geometry(a, *ax, planes);
     a->n_blocks32 = a->NB32 * (a->NB32 + 1) / 2;
-    a->n_sets = 1;                            // (per launch: fu_args_blocks)
-    a->n_bins = ax->n_groups * ax->F;
-    a->F = ax->F;
-    a->floats_per_bin = (int64_t)sc_plane_count(planes) * a->n_tiles * SC_TILE_ELEMS;
-    a->csm_plane = sc_plane_offset(planes, SC_PLANE_CSM);
-    a->abs_plane = (planes & SC_PLANE_ABS_IM) ? sc_plane_offset(planes, SC_PLANE_ABS_IM) : -1;   // -1: CSM only
-    a->sq_plane = -1;
-    a->sign_plane = -1;
+    a->n_sets = 1;                            // (per launch: fu_fill_block_map)
     if (mode == FU_MODE_UNIT) {   // sum s / |s| = the CSM of x / |x|: the same kernels, pointed at the unit-phasor planes
         a->csm_plane = sc_plane_offset(planes, SC_PLANE_UNIT);
-        a->abs_plane = -1;
+        a->abs_plane = a->sq_plane = a->sign_plane = -1;
     } else if (mode == FU_MODE_SIGN) {
-        a->csm_plane = -1;
-        a->abs_plane = -1;
-        a->sign_plane = sc_plane_offset(planes, SC_PLANE_SIGN_IM);
-    } else if ((planes & SC_PLANE_ABS_IM) && (planes & SC_PLANE_IM_SQ)) {
-        // rides along on the small-channel kernel; a plane pass of the matrix-core kernel above its range
-        a->sq_plane = sc_plane_offset(planes, SC_PLANE_IM_SQ);
+        a->csm_plane = a->abs_plane = a->sq_plane = -1;
+    } else {
+        // (Im s)^2 only with |Im s|: it rides along on the small-channel kernel; a plane pass of the matrix-core kernel above its range
+        a->sign_plane = -1;
+        if (a->abs_plane < 0) a->sq_plane = -1;
     }
-    a->nl_op = FU_OP_ABS;
-    a->n_split = 1;
-    a->ws = nullptr;
+    fu_headline_fold(a);
     return SC_OK;
 }
 
@@ -1022,8 +936,7 @@ extern "C" int64_t sc_fused_workspace_bytes(const sc_spectra_desc* desc, uint32_
     ScAxes ax;
     const int mode = (planes & SC_PLANE_CSM) ? FU_MODE_CSM : (planes & SC_PLANE_UNIT) ? FU_MODE_UNIT : FU_MODE_SIGN;
     if (fused_setup(nullptr, desc, planes, mode, &a, &ax) != SC_OK) return 0;
-    const int S = sc_internal_fused_pick_split(a.n_bins, ax.n_obs);
-    return (int64_t)(S - 1) * a.n_bins * a.floats_per_bin * (int64_t)sizeof(float);
+    return (int64_t)(sc_internal_fused_pick_split(a.n_bins, ax.n_obs) - 1) * fu_part_bytes(a);
 }
 
 static int fused_run(const void* d_X, const sc_spectra_desc* desc, uint32_t planes, int mode, float* d_accum,
@@ -1047,29 +960,15 @@ static int fused_run(const void* d_X, const sc_spectra_desc* desc, uint32_t plan
         const char* dbg = sc_switch(SC_SW_FUSED_DEBUG);
         a.debug_skip = dbg ? atoi(dbg) : 0;
     }
-    // as many parts per bin as the workspace allows (none: one workgroup per bin)
-    int S = sc_internal_fused_pick_split(a.n_bins, ax.n_obs);
-    const int64_t part_bytes = (int64_t)a.n_bins * a.floats_per_bin * (int64_t)sizeof(float);
-    if (!d_workspace) S = 1;
-    while (S > 1 && (int64_t)(S - 1) * part_bytes > workspace_bytes) --S;
-    SC_REQUIRE(S == 1 || ((uintptr_t)d_workspace % 16) == 0, "workspace must be 16-byte aligned");
-    a.n_split = S;
-    a.ws = (float*)d_workspace;
+    const int rc_parts = sc_internal_fused_set_parts(&a, ax.n_obs, d_workspace, workspace_bytes);
+    if (rc_parts != SC_OK) return rc_parts;
     hipStream_t s = (hipStream_t)stream;
     const char* no_small = sc_switch(SC_SW_FUSED_NO_SMALL);       // diagnostic: every shape through the matrix-core kernel
     if (!(no_small && atoi(no_small)) &&
         (small_ok(ax, a.abs_plane >= 0) || (a.sq_plane >= 0 && small_ok_sq(ax)) || (mode == FU_MODE_SIGN && small_ok_sign(ax))))
         return launch_small(a, unit, s);
-    if (mode == FU_MODE_SIGN) {
-        // plane pass: sign(d) of the per-observation matrix-core products, summed as integers by the abs waves
-        FusedArgs b = a;
-        b.csm_plane = -1;
-        b.abs_plane = a.sign_plane;
-        b.nl_op = FU_OP_SIGN;
-        b.fold[0] = b.abs_plane;
-        b.n_fold = 1;
-        return launch_fused_all(b, FU_OP_SIGN, s);
-    }
+    // plane pass: sign(d) of the per-observation matrix-core products, summed as integers by the abs waves
+    if (mode == FU_MODE_SIGN) return launch_fused_all(fu_plane_pass(a, a.sign_plane, FU_OP_SIGN), FU_OP_SIGN, s);
     // unit phasors (PLV / PPC): the staging waves normalise the rows on the way into LDS (FU_OP_UNIT) -- no normalised
     // copy of the spectra, no scratch (d_scratch / scratch_bytes are accepted and ignored)
     (void)d_scratch; (void)scratch_bytes;
@@ -1077,13 +976,7 @@ static int fused_run(const void* d_X, const sc_spectra_desc* desc, uint32_t plan
     if (rc_main != SC_OK || a.sq_plane < 0) return rc_main;
     // debiased wPLI: sum (Im s)^2 as a second pass of the same kernel (the abs waves hold 80 accumulator registers
     // per plane; two planes do not fit next to the matrix-core role's)
-    FusedArgs b = a;
-    b.csm_plane = -1;
-    b.abs_plane = a.sq_plane;
-    b.nl_op = FU_OP_SQ;
-    b.fold[0] = b.abs_plane;
-    b.n_fold = 1;
-    return launch_fused_all(b, FU_OP_SQ, s);
+    return launch_fused_all(fu_plane_pass(a, a.sq_plane, FU_OP_SQ), FU_OP_SQ, s);
 }
 
 extern "C" int sc_fused_csm_absim_ws_f32(const void* d_X, const sc_spectra_desc* desc, uint32_t planes,

@@ -382,9 +382,6 @@ __device__ __forceinline__ h16x8 f2_frag(lds_u8* base, int p) {
 }
 
 #define F2_MFMA(a, b, c) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0)
-// Every wave has waited for its own HBM -> LDS loads (vmcnt) before it gets here; the barrier itself publishes LDS writes
-// only (a __syncthreads() would also wait for the fold atomics the CSM waves have just sent to L2: ~1 us per chunk).
-#define F2_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 // Loads of one chunk (32 instructions of 1 KB): the eight |Im s| waves (4 .. 11; no other memory traffic of theirs is in
 // flight, so their vmcnt counts these loads exactly) fill plane (w - 4) % 4 of the observation groups o7 = 4 ((w - 4) / 4) .. + 3.
@@ -492,7 +489,6 @@ __device__ __forceinline__ void f2_wait_loads(int outstanding) {
     }
 }
 
-static_assert(2 * 4 + 1 <= FU_FLUSH, "one fold slot per tile of a wave");
 // Matrix-core role: wave w owns the tiles fu_assign_rows gave it (tile rows w and R - 1 - w of the triangle).  Per tile and
 // chunk 12 v_mfma_f32_16x16x32_f16: the cross terms h h, h m, m h x {Re Re, Im Im, Im Re, (-Re) Im} (16 with the m m term);
 // every operand fragment is two transposing LDS loads, no VALU.
@@ -825,8 +821,8 @@ __global__ void __launch_bounds__(FU_THREADS) fused2_kernel(Fused2Args a) {
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 // What the planes-format kernels fill: the CSM planes, |Im s| with them, (Im s)^2 with both (a second pass of the same kernel:
 // the |Im s| waves square the per-observation products instead), and sign(Im s) on its own (a pass that sums signs as
-// integers) -- up to 1024 signals (129 ... 256: the launches of sc_fused.hip's launch_fused_all, each staging four 32-channel
-// blocks; beyond: the general plan of fused2_launch_all), observations of a bin one linear run of rows.
+// integers) -- up to 1024 signals (above 128: the launches of fu_plan, each staging up to four 32-channel blocks),
+// observations of a bin one linear run of rows.
 #define F2_MAX_SIGNALS 1024      // 32 blocks of 32 channels (the block map packs a block's 16-tile row into 8 bits: 127 blocks at most)
 static bool fused2_families_ok(uint32_t fam) {
     return fam == SC_PLANE_CSM || fam == (SC_PLANE_CSM | SC_PLANE_ABS_IM) ||
@@ -849,21 +845,10 @@ static int fused2_setup(const sc_spectra_desc* desc, uint32_t planes, Fused2Args
     Fused2Args& a = *out;
     FusedArgs& f = a.f;
     f.st.base = nullptr; f.st.ax = ax; f.st.obs_stride = sc_stage_linear_stride(ax); f.st.C = ax.C; f.st.n_obs = ax.n_obs;
-    f.NB32 = (ax.C + 31) / 32;                  // of the whole record; a launch stages up to four (fused2_args_blocks)
+    fu_record_geometry(&f, ax, planes);
+    fu_headline_fold(&f);
     f.st.CP = f.NB32 * 32; f.st.RS = 0;
-    f.NB = sc_n_blocks(ax.C);
-    f.n_tiles = sc_n_tiles(f.NB);
-    f.n_bins = ax.n_groups * ax.F;
-    f.F = ax.F;
-    f.floats_per_bin = (int64_t)sc_plane_count(planes) * f.n_tiles * SC_TILE_ELEMS;
-    f.csm_plane = (planes & SC_PLANE_CSM) ? sc_plane_offset(planes, SC_PLANE_CSM) : -1;
-    f.abs_plane = (planes & SC_PLANE_ABS_IM) ? sc_plane_offset(planes, SC_PLANE_ABS_IM) : -1;
-    f.sq_plane = (planes & SC_PLANE_IM_SQ) ? sc_plane_offset(planes, SC_PLANE_IM_SQ) : -1;
-    f.sign_plane = (planes & SC_PLANE_SIGN_IM) ? sc_plane_offset(planes, SC_PLANE_SIGN_IM) : -1;
-    f.n_fold = 0;
-    f.nl_op = FU_OP_ABS;
-    f.n_split = 1; f.ws = nullptr; f.debug_skip = 0;
-    f.map.NBr = f.NB;
+    f.debug_skip = 0;
     a.row_bytes = sc_planes_row_bytes(ax.C);
     a.obs_rows = f.st.obs_stride;
     a.terms4 = ax.n_obs < 256 ? 1 : 0;
@@ -873,103 +858,43 @@ static int fused2_setup(const sc_spectra_desc* desc, uint32_t planes, Fused2Args
     return SC_OK;
 }
 
-// One launch that stages the nb (<= 4) 32-channel blocks `blocks` (ascending block numbers of the record's channels) and owns
-// the products (bi <= bj, bj >= col_lo, bi < row_hi) of them (same scheme as fu_args_blocks of sc_fused.hip; the loader takes a
-// block's rows from tile off32 of the observation row).
-static Fused2Args fused2_args_blocks(const Fused2Args& full, const int* blocks, int nb, int col_lo, int row_hi) {
+// One launch of the plan: the loader takes a block's rows from tile off32 of the observation row (absolute).
+static Fused2Args fused2_args_blocks(const Fused2Args& full, const FuLaunch& l) {
     Fused2Args a = full;
-    FusedArgs& f = a.f;
-    const int C = full.f.st.C;
-    int n_last = 0;
-    f.map.off32 = f.map.n32 = f.map.t32 = 0u;
-    for (int b = 0; b < nb; ++b) {
-        const int c = blocks[b] * 32;
-        n_last = C - c < 32 ? C - c : 32;
-        f.map.off32 |= (unsigned)blocks[b] << (8 * b);
-        f.map.n32 |= (unsigned)n_last << (8 * b);
-        f.map.t32 |= (unsigned)(blocks[b] * 2) << (8 * b);
-    }
-    f.NB32 = nb;
-    f.NB = 2 * (nb - 1) + (n_last + 15) / 16;      // 16-channel tiles that exist among the staged blocks
-    f.shape_col_lo = col_lo;
-    f.shape_row_hi = row_hi;
-    f.n_blocks32 = fu_nblocks(nb, col_lo, row_hi);
-    f.n_sets = fu_nsets(nb, col_lo, row_hi);
-    f.st.CP = nb * 32;
-    f.map.col_lo = 2 * col_lo;
-    f.map.row_hi = 2 * row_hi;
-    sc_internal_fu_assign_rows(&f);
+    fu_fill_block_map(&a.f, full.f.st.C, l, 0);
     // measured at the cfg3 volume: 128 channels 3.71 vs 3.82 ms with the CSM waves loading, 64 channels 3.23 vs 2.98
-    a.loader_csm = nb >= 3 ? 1 : 0;
+    a.loader_csm = l.nb >= 3 ? 1 : 0;
     return a;
 }
 
-#define F2_SHAPES(X) X(1, 0, 1) X(2, 0, 2) X(3, 0, 3) X(4, 0, 4) X(4, 2, 2) X(3, 1, 3) X(4, 2, 4) X(4, 1, 4) X(4, 1, 1) X(3, 2, 2)
-template <int NB32, int COL_LO, int ROW_HI, int OP>
-static void fused2_launch_op(const Fused2Args& a, hipStream_t s) {
-    auto k = fused2_kernel<NB32, COL_LO, ROW_HI, OP>;
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F2_LDS);
-    hipLaunchKernelGGL(k, dim3((unsigned)(a.f.n_bins * a.f.n_split)), dim3(FU_THREADS), F2_LDS, s, a);
-}
-static int fused2_launch(const Fused2Args& a, int op, hipStream_t s) {
-    const int shape = a.f.NB32 * 100 + a.f.shape_col_lo * 10 + a.f.shape_row_hi;
-#define F2_CASE(NB32, COL_LO, ROW_HI)                                                              \
-    case NB32 * 100 + COL_LO * 10 + ROW_HI:                                                        \
-        if (op == FU_OP_SQ) fused2_launch_op<NB32, COL_LO, ROW_HI, FU_OP_SQ>(a, s);                \
-        else if (op == FU_OP_SIGN) fused2_launch_op<NB32, COL_LO, ROW_HI, FU_OP_SIGN>(a, s);       \
-        else fused2_launch_op<NB32, COL_LO, ROW_HI, FU_OP_ABS>(a, s);                              \
-        break;
-    switch (shape) {
-        F2_SHAPES(F2_CASE)
-    default:
-        sc_set_error("planes-format stage B: no launch shape (%d staged blocks, column %d, %d rows)", a.f.NB32, a.f.shape_col_lo, a.f.shape_row_hi);
-        return SC_EINVAL;
+struct Fused2Launch {
+    static constexpr bool UNIT = false, PLANES_SHAPES = true;
+    static constexpr const char* NAME = "planes-format stage B";
+    template <int NB32, int COL_LO, int ROW_HI, int OP>
+    static int launch(const Fused2Args& a, hipStream_t s) {
+        auto k = fused2_kernel<NB32, COL_LO, ROW_HI, OP>;
+        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F2_LDS);
+        hipLaunchKernelGGL(k, dim3((unsigned)(a.f.n_bins * a.f.n_split)), dim3(FU_THREADS), F2_LDS, s, a);
+        SC_CHECK_HIP(hipGetLastError());
+        return SC_OK;
     }
-#undef F2_CASE
-    SC_CHECK_HIP(hipGetLastError());
-    return SC_OK;
-}
-// every tile of the record once (the launch plans of sc_fused.hip: launch_fused_all)
-static int fused2_launch_all(const Fused2Args& full, int op, hipStream_t s) {
-    const int C = full.f.st.C, n = (C + 31) / 32;
-    struct Plan { int nb, blocks[4], col_lo, row_hi; };
-    static const Plan tri[4] = {{1, {0}, 0, 1}, {2, {0, 1}, 0, 2}, {3, {0, 1, 2}, 0, 3}, {4, {0, 1, 2, 3}, 0, 4}};
-    static const Plan p5[] = {{3, {0, 1, 2}, 0, 3}, {4, {0, 1, 3, 4}, 2, 2}, {3, {2, 3, 4}, 1, 3}};
-    static const Plan p6[] = {{4, {0, 1, 2, 3}, 0, 4}, {4, {0, 1, 4, 5}, 2, 4}, {4, {2, 3, 4, 5}, 2, 2}};
-    static const Plan p7[] = {{4, {0, 1, 2, 3}, 0, 4}, {4, {0, 4, 5, 6}, 1, 4}, {4, {1, 4, 5, 6}, 1, 1},
-                              {4, {2, 4, 5, 6}, 1, 1}, {4, {3, 4, 5, 6}, 1, 1}};
-    static const Plan p8[] = {{4, {0, 1, 2, 3}, 0, 4}, {4, {4, 5, 6, 7}, 0, 4}, {4, {0, 1, 4, 5}, 2, 2},
-                              {4, {0, 1, 6, 7}, 2, 2}, {4, {2, 3, 4, 5}, 2, 2}, {4, {2, 3, 6, 7}, 2, 2}};
+};
+// One pass: every tile of the record once (fu_plan), then (fold) the split-bin partial records folded into the caller's.
+static int fused2_launch_all(const Fused2Args& full, int op, bool fold, hipStream_t s) {
+    FuLaunch plan[FU_PLAN_MAX_LAUNCHES];
+    const int n_launch = fu_plan((full.f.st.C + 31) / 32, plan);
     int rc = SC_OK;
-    if (n > 8) {
-        // More than 256 signals (round 6; before: the host tiled the channels in blocks of 128 and paid a gathered 256-channel triangle per
-        // block pair, on the complex64 kernels).  Groups of four consecutive blocks take their triangle; two halves (pairs of blocks) of
-        // DIFFERENT groups take their 64 x 64 rectangle; with an odd block count the last block is a group (or the third block of one)
-        // of its own and meets every pair outside its group as a 64 x 32 rectangle.  Every 32 x 32 block product exactly once.
-        const int n_pairs = n / 2, lone = (n & 1) ? n - 1 : -1;
-        for (int g0 = 0; g0 < n && rc == SC_OK; g0 += 4) {
-            const int nbg = n - g0 < 4 ? n - g0 : 4;
-            Plan t = {nbg, {g0, g0 + 1, g0 + 2, g0 + 3}, 0, nbg};
-            rc = fused2_launch(fused2_args_blocks(full, t.blocks, t.nb, t.col_lo, t.row_hi), op, s);
-        }
-        for (int hi = 0; hi < n_pairs && rc == SC_OK; ++hi) {
-            for (int hj = hi + 1; hj < n_pairs && rc == SC_OK; ++hj) {
-                if (hi / 2 == hj / 2) continue;                    // the two halves of one group: inside its triangle
-                const int b[4] = {2 * hi, 2 * hi + 1, 2 * hj, 2 * hj + 1};
-                rc = fused2_launch(fused2_args_blocks(full, b, 4, 2, 2), op, s);
-            }
-            if (lone >= 0 && hi / 2 != lone / 4 && rc == SC_OK) {
-                const int b[3] = {2 * hi, 2 * hi + 1, lone};
-                rc = fused2_launch(fused2_args_blocks(full, b, 3, 2, 2), op, s);
-            }
-        }
-        return rc;
+    for (int l = 0; l < n_launch && rc == SC_OK; ++l) {
+        const Fused2Args a = fused2_args_blocks(full, plan[l]);
+        rc = fu_dispatch<Fused2Launch>(a, a.f, op, s);
     }
-    const Plan* plan = n <= 4 ? &tri[n - 1] : n == 5 ? p5 : n == 6 ? p6 : n == 7 ? p7 : p8;
-    const int n_launch = n <= 4 ? 1 : n == 5 ? 3 : n == 6 ? 3 : n == 7 ? 5 : 6;
-    for (int l = 0; l < n_launch && rc == SC_OK; ++l)
-        rc = fused2_launch(fused2_args_blocks(full, plan[l].blocks, plan[l].nb, plan[l].col_lo, plan[l].row_hi), op, s);
-    return rc;
+    return rc == SC_OK && fold ? sc_internal_fused_combine(full.f, s) : rc;
+}
+// a plane pass (fu_plane_pass) of the planes kernel: the CSM waves only load
+static int fused2_plane_pass(const Fused2Args& a, int plane, int op, hipStream_t s) {
+    Fused2Args b = a;
+    b.f = fu_plane_pass(a.f, plane, op);
+    return fused2_launch_all(b, op, true, s);
 }
 
 extern "C" int sc_fused2_supported(const sc_spectra_desc* desc, uint32_t planes) {
@@ -998,13 +923,8 @@ static int fused2_run(const void* d_P, const sc_spectra_desc* desc, const float*
         const char* t4 = sc_switch(SC_SW_FUSED2_TERMS);
         if (t4) a.terms4 = atoi(t4) == 4 ? 1 : 0;
     }
-    int S = sc_internal_fused_pick_split(f.n_bins, ax.n_obs);
-    const int64_t part_bytes = (int64_t)f.n_bins * f.floats_per_bin * (int64_t)sizeof(float);
-    if (!d_workspace) S = 1;
-    while (S > 1 && (int64_t)(S - 1) * part_bytes > workspace_bytes) --S;
-    SC_REQUIRE(S == 1 || ((uintptr_t)d_workspace % 16) == 0, "workspace must be 16-byte aligned");
-    f.n_split = S;
-    f.ws = (float*)d_workspace;
+    const int rc_parts = sc_internal_fused_set_parts(&f, ax.n_obs, d_workspace, workspace_bytes);
+    if (rc_parts != SC_OK) return rc_parts;
     {
         // Fold interval of the two-level summation: 512 observations (16 matrix instructions per accumulator between folds).
         // Round 5 measured what longer intervals buy and cost at cfg3 (three parts of 2333 observations; profiles/r05_fused2_fold_ab.txt):
@@ -1018,34 +938,13 @@ static int fused2_run(const void* d_P, const sc_spectra_desc* desc, const float*
     hipStream_t s = (hipStream_t)stream;
     const bool parts_ok = n_parts && ax.C <= 128 && f.sq_plane < 0 && f.sign_plane < 0;
     if (n_parts) *n_parts = 1;
-    if (f.sign_plane >= 0) {
-        // sign(Im s) summed as integers by the |Im s| waves; the CSM waves only load
-        Fused2Args b = a;
-        b.f.csm_plane = -1;
-        b.f.abs_plane = f.sign_plane;
-        b.f.nl_op = FU_OP_SIGN;
-        b.f.fold[0] = b.f.abs_plane; b.f.n_fold = 1;
-        const int rc2 = fused2_launch_all(b, FU_OP_SIGN, s);
-        return rc2 != SC_OK ? rc2 : sc_internal_fused_combine(b.f, FU_OP_SIGN, s);
-    }
-    {
-        Fused2Args m = a;
-        m.f.sq_plane = -1;
-        const int rc2 = fused2_launch_all(m, FU_OP_ABS, s);
-        if (rc2 != SC_OK) return rc2;
-        if (parts_ok) { *n_parts = f.n_split; return SC_OK; }      // the caller's epilogue sums the parts
-        const int rc3 = sc_internal_fused_combine(m.f, FU_OP_ABS, s);
-        if (rc3 != SC_OK || f.sq_plane < 0) return rc3;
-    }
+    // sign(Im s) summed as integers by the |Im s| waves
+    if (f.sign_plane >= 0) return fused2_plane_pass(a, f.sign_plane, FU_OP_SIGN, s);
+    const int rc2 = fused2_launch_all(a, FU_OP_ABS, !parts_ok, s);
+    if (rc2 == SC_OK && parts_ok) *n_parts = f.n_split;               // the caller's epilogue sums the parts
+    if (rc2 != SC_OK || f.sq_plane < 0) return rc2;
     // debiased wPLI: sum (Im s)^2 as a second pass (the |Im s| waves hold 80 accumulator registers per plane)
-    Fused2Args b = a;
-    b.f.csm_plane = -1;
-    b.f.abs_plane = f.sq_plane;
-    b.f.sq_plane = -1;
-    b.f.nl_op = FU_OP_SQ;
-    b.f.fold[0] = b.f.abs_plane; b.f.n_fold = 1;
-    const int rc4 = fused2_launch_all(b, FU_OP_SQ, s);
-    return rc4 != SC_OK ? rc4 : sc_internal_fused_combine(b.f, FU_OP_SQ, s);
+    return fused2_plane_pass(a, f.sq_plane, FU_OP_SQ, s);
 }
 extern "C" int sc_fused2_csm_absim_f32(const void* d_P, const sc_spectra_desc* desc, const float* d_scale, uint32_t planes,
                                        float* d_accum, void* d_workspace, int64_t workspace_bytes, void* stream) {

@@ -1,8 +1,10 @@
 // sc_fused_common.h -- what the two one-pass stage-B kernels share (sc_fused.hip: complex64 spectra, split into bf16 pieces
 // while staging; sc_fused2.hip: spectra that stage A already wrote as bf16 pieces): launch arguments, the staged-block
-// map, the 32x32 block tables of the |Im s| role and its accumulate step, and the host helpers of the split-bin scheme.
+// map and its filler, the 32x32 block tables of the |Im s| role and its accumulate step, the (shape, op) dispatch, the
+// record geometry, the plane passes and the host helpers of the split-bin scheme.  The launch plan is sc_fused_plan.h's.
 #pragma once
 #include "sc_stage.h"
+#include "sc_fused_plan.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
@@ -19,7 +21,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // blocks of 32: local block b holds n32[b] channels (even; every block ahead of the last staged one is full) starting
 // off32[b] elements from st.base, and its two 16-channel tiles are tiles t32[b], t32[b] + 1 of the record (NBr = tile
 // rows of the record).  One contiguous range is every launch up to 128 channels; 129 ... 256 channels are covered by
-// several launches whose staged blocks come from up to two ranges (see launch_fused_all).  Which of the staged blocks'
+// several launches whose staged blocks come from up to two ranges (see fu_plan).  Which of the staged blocks'
 // products a launch owns is a staircase of the local upper triangle: tile (r, c), r <= c, is active when c >= col_lo and
 // r < row_hi (in 16-channel tiles; the whole triangle: col_lo = 0, row_hi = NB).
 // The per-block values are packed one byte each (block b in bits 8 b ... 8 b + 7: one bit-field extract for a per-lane
@@ -42,7 +44,7 @@ struct FusedArgs {
     int shape_col_lo, shape_row_hi;   // the launch's 32x32 blocks: bi <= bj, bj >= shape_col_lo, bi < shape_row_hi
     int csm_plane, abs_plane;
     int sq_plane, sign_plane;   // small-channel kernel only: sum (Im s)^2, sum sign(Im s); -1 = absent
-    int fold[6], n_fold;        // small-channel kernel only: the record planes a launch writes (folded over the parts)
+    int fold[6], n_fold;        // the record planes a pass writes: what fused_fold_kernel folds over the parts
     int nl_op;           // what the abs waves accumulate from the per-observation d = Im(x_i conj x_j) into record plane
                          // `abs_plane`: FU_OP_ABS |d| (with the CSM planes, one pass), FU_OP_SQ d^2, FU_OP_SIGN sign(d)
                          // (plane passes: csm_plane = -1, the four CSM waves only stage)
@@ -82,6 +84,14 @@ __device__ __forceinline__ int fu_lane() {
     return l;
 }
 enum { FU_OP_ABS = 0, FU_OP_SQ = 1, FU_OP_SIGN = 2, FU_OP_UNIT = 3 };     // UNIT: CSM role only, rows normalised at staging
+
+// Workgroup barrier that publishes LDS writes only.  __syncthreads() would also drain vmcnt, i.e. make every wave sit out
+// the HBM->LDS row loads that were just put in flight for a later chunk (sc_fused2.hip: every wave has waited for its OWN
+// loads before it gets here; a __syncthreads() would also wait for the fold atomics the CSM waves have just sent to L2:
+// ~1 us per chunk).
+#define FU_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+#define F2_BARRIER() FU_BARRIER()
+static_assert(2 * 4 + 1 <= FU_FLUSH, "one fold slot per tile of a wave");
 
 // ---- VALU role ---------------------------------------------------------------------------------
 // Upper-triangular 32x32 blocks, row-major: t -> (BI, BJ).  Tables are compile-time (template on
@@ -191,7 +201,107 @@ __device__ __forceinline__ void fu_accumulate16(f32x16& acc, const f32x16& d) {
 }
 
 
-// host helpers defined in sc_fused.hip
+// ---- host side ----------------------------------------------------------------------------------
+// defined in sc_fused.hip
 int sc_internal_fused_pick_split(int n_bins, int n_obs);              // workgroups per bin
+int sc_internal_fused_set_parts(FusedArgs* a, int n_obs, void* d_workspace, int64_t workspace_bytes);   // n_split, ws of a call
 void sc_internal_fu_assign_rows(FusedArgs* a);                         // tiles of the four CSM waves
-int sc_internal_fused_combine(const FusedArgs& a, int op, hipStream_t stream);   // fold the parts' records (n_split > 1)
+int sc_internal_fused_combine(const FusedArgs& a, hipStream_t stream); // fold the parts' records (n_split > 1)
+
+// bytes of one part's records: the workspace holds those of parts 1 ... n_split - 1
+inline int64_t fu_part_bytes(const FusedArgs& a) { return (int64_t)a.n_bins * a.floats_per_bin * (int64_t)sizeof(float); }
+
+// The record of `planes` for the shape `ax`: tiles, bins, floats per bin, where its planes sit (-1: absent), one part.
+inline void fu_record_geometry(FusedArgs* a, const ScAxes& ax, uint32_t planes) {
+    auto offset = [&](uint32_t plane) { return (planes & plane) ? sc_plane_offset(planes, plane) : -1; };
+    a->NB = sc_n_blocks(ax.C);
+    a->n_tiles = sc_n_tiles(a->NB);
+    a->NB32 = (ax.C + 31) / 32;                 // of the whole record; a launch stages up to four (fu_fill_block_map)
+    a->map.NBr = a->NB;
+    a->n_bins = ax.n_groups * ax.F;
+    a->F = ax.F;
+    a->floats_per_bin = (int64_t)sc_plane_count(planes) * a->n_tiles * SC_TILE_ELEMS;
+    a->csm_plane = offset(SC_PLANE_CSM);
+    a->abs_plane = offset(SC_PLANE_ABS_IM);
+    a->sq_plane = offset(SC_PLANE_IM_SQ);
+    a->sign_plane = offset(SC_PLANE_SIGN_IM);
+    a->nl_op = FU_OP_ABS;
+    a->n_split = 1;
+    a->ws = nullptr;
+}
+// what the headline pass writes, hence folds: the CSM planes (re, im) and |Im s| as far as present
+inline void fu_headline_fold(FusedArgs* a) {
+    a->n_fold = 0;
+    if (a->csm_plane >= 0) { a->fold[a->n_fold++] = a->csm_plane; a->fold[a->n_fold++] = a->csm_plane + 1; }
+    if (a->abs_plane >= 0) a->fold[a->n_fold++] = a->abs_plane;
+}
+// A plane pass of the matrix-core kernels: the |Im s| waves accumulate op(d) -- FU_OP_SQ d^2, FU_OP_SIGN sign(d) as
+// integers -- of the same per-observation products into record plane `plane`, the CSM waves only stage (load).
+// (sq_plane / sign_plane stay: only the small-channel kernel reads them, and it has no plane passes.)
+inline FusedArgs fu_plane_pass(const FusedArgs& a, int plane, int op) {
+    FusedArgs b = a;
+    b.csm_plane = -1;
+    b.abs_plane = plane;
+    b.nl_op = op;
+    b.fold[0] = plane;
+    b.n_fold = 1;
+    return b;
+}
+
+// The block map of one launch of the record of C channels (`a` arrives as the full record's arguments): staged blocks,
+// tiles, owned products, the CSM waves' tiles.  off32 counts from block `off32_origin`.
+inline void fu_fill_block_map(FusedArgs* a, int C, const FuLaunch& l, int off32_origin) {
+    int n_last = 0;
+    a->map.off32 = a->map.n32 = a->map.t32 = 0u;
+    for (int b = 0; b < l.nb; ++b) {
+        const int c = l.blocks[b] * 32;
+        n_last = C - c < 32 ? C - c : 32;
+        a->map.off32 |= (unsigned)(l.blocks[b] - off32_origin) << (8 * b);
+        a->map.n32 |= (unsigned)n_last << (8 * b);
+        a->map.t32 |= (unsigned)(l.blocks[b] * 2) << (8 * b);
+    }
+    a->NB32 = l.nb;
+    a->NB = 2 * (l.nb - 1) + (n_last + 15) / 16;      // 16-channel tiles that exist among the staged blocks (the last may be partial)
+    a->shape_col_lo = l.col_lo;
+    a->shape_row_hi = l.row_hi;
+    a->n_blocks32 = fu_nblocks(l.nb, l.col_lo, l.row_hi);
+    a->n_sets = fu_nsets(l.nb, l.col_lo, l.row_hi);
+    a->st.CP = l.nb * 32;
+    a->map.col_lo = 2 * l.col_lo;
+    a->map.row_hi = 2 * l.row_hi;
+    sc_internal_fu_assign_rows(a);
+}
+
+// The launch shapes that exist (staged blocks, first block column, block rows): the triangles of 1 ... 4 blocks for up to
+// 128 channels and the staircases fu_plan covers 129 ... 256 channels with; the planes kernel alone has the lone block's
+// rectangle of the plan beyond.
+#define FU_SHAPES(X) X(1, 0, 1) X(2, 0, 2) X(3, 0, 3) X(4, 0, 4) X(4, 2, 2) X(3, 1, 3) X(4, 2, 4) X(4, 1, 4) X(4, 1, 1)
+#define FU_SHAPES_PLANES(X) X(3, 2, 2)
+// (shape, op) -> instantiation.  K is the kernel's side of it: K::launch<NB32, COL_LO, ROW_HI, OP>(args, stream), K::NAME for
+// the message, and whether it has the FU_OP_UNIT instantiations (K::UNIT) and the planes-only shapes (K::PLANES_SHAPES).
+template <class K, int NB32, int COL_LO, int ROW_HI, class Args>
+static int fu_dispatch_op(const Args& a, int op, hipStream_t s) {
+    if (op == FU_OP_SQ) return K::template launch<NB32, COL_LO, ROW_HI, FU_OP_SQ>(a, s);
+    if (op == FU_OP_SIGN) return K::template launch<NB32, COL_LO, ROW_HI, FU_OP_SIGN>(a, s);
+    if constexpr (K::UNIT) {
+        if (op == FU_OP_UNIT) return K::template launch<NB32, COL_LO, ROW_HI, FU_OP_UNIT>(a, s);
+    }
+    return K::template launch<NB32, COL_LO, ROW_HI, FU_OP_ABS>(a, s);
+}
+template <class K, class Args>
+static int fu_dispatch(const Args& a, const FusedArgs& f, int op, hipStream_t s) {
+#define FU_CASE(NB32, COL_LO, ROW_HI) \
+    case NB32 * 100 + COL_LO * 10 + ROW_HI: return fu_dispatch_op<K, NB32, COL_LO, ROW_HI>(a, op, s);
+#define FU_CASE_PLANES(NB32, COL_LO, ROW_HI)                                                              \
+    case NB32 * 100 + COL_LO * 10 + ROW_HI:                                                               \
+        if constexpr (K::PLANES_SHAPES) return fu_dispatch_op<K, NB32, COL_LO, ROW_HI>(a, op, s);         \
+        else break;
+    switch (f.NB32 * 100 + f.shape_col_lo * 10 + f.shape_row_hi) {
+        FU_SHAPES(FU_CASE)
+        FU_SHAPES_PLANES(FU_CASE_PLANES)
+    }
+#undef FU_CASE
+#undef FU_CASE_PLANES
+    sc_set_error("%s: no launch shape (%d staged blocks, column %d, %d rows)", K::NAME, f.NB32, f.shape_col_lo, f.shape_row_hi);
+    return SC_EINVAL;
+}

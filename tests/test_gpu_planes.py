@@ -361,6 +361,78 @@ def test_stage_b_on_planes_three_term_sweep(n_obs, C, debug_env):
           + ", ".join(f"{k}: {v[0]:.2f} / {v[1]:.1e}" for k, v in worst.items()))
 
 
+@pytest.mark.parametrize("kernel,block_counts", [("complex64", (1, 2, 3, 4, 5, 6, 7, 8)), ("planes", (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 13))])
+def test_every_launch_plan_of_both_matrix_core_kernels(kernel, block_counts, debug_env):
+    """Every launch plan of csrc/sc_fused_plan.h on both matrix-core stage-B kernels (sc_fused.hip on complex64 spectra, with
+    SC_FUSED_NO_SMALL so that one block reaches it too; sc_fused2.hip on the planes format) against float64 sums of the same
+    complex64-rounded coefficients: n 32-channel blocks, 32 n - 18 signals (the last block partial: a single 16-channel tile) --
+    the triangles of 1 ... 4 blocks, the tables of 5 ... 8 (six blocks, shape (4, 2, 4), had no test on the planes kernel),
+    and on the planes kernel the general plan with the lone block as a group of its own (9, 13), as the third block of a group
+    (11) and without one (10).  Two bins of 70 observations (three 32-row chunks, the last partial), whole and split over two
+    workgroups (beyond 256 signals the workspace query grants no partial records: those run whole both times); the records CSM + |Im s| + (Im s)^2 (headline pass and a plane pass) and sign(Im s) (a plane pass).
+    Bounds, un-normalised sums over the upper triangle -- cross-spectra and |Im s|: those of
+    test_stage_b_on_planes_three_term_sweep on the planes kernel (3e-6 |S_ij| + 2e-7 sqrt(P_i P_j); 1e-5 relative), those of
+    test_gpu_parity.test_fused_stage_b_equals_separate_kernels on the complex64 kernel (close32 with 2e-6: 2e-6 |ref| + 2e-6
+    max |ref| per plane).  (Im s)^2 and sign(Im s) have no bound against float64 sums elsewhere: twice the worst error of
+    these kernels before the launch plan moved to its header, measured on MI355X with these seeds -- (Im s)^2 relative
+    error 2.92e-7 (complex64 kernel, eight blocks) and 4.82e-7 (planes kernel, three blocks): bounds 5.9e-7 and 9.7e-7; the sign
+    sums came out exact at every shape (no observation has an Im s within rounding of zero): bound 0."""
+    import sys, os
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from conftest import unpack_record_planes
+    from fp64_device_ref import sums_fp64
+    dev = _dev()
+    F, W, R, K = 2, 1, 70, 1
+    SQ_BOUND, SIGN_BOUND = {"complex64": 5.9e-7, "planes": 9.7e-7}[kernel], 0.0
+    if kernel == "complex64":
+        debug_env("SC_FUSED_NO_SMALL", 1)
+    worst = {}
+    for n in block_counts:
+        C = 32 * n - 18
+        rng = np.random.default_rng(7000 + C)
+        coef = rng.standard_normal((F, W, R, K, C)) + 1j * rng.standard_normal((F, W, R, K, C))
+        coef = coef + 0.4 * coef[..., :1]                              # a shared component (before the scales: no cancelling pairs)
+        coef = coef * (0.2 + rng.random(C)) * 10.0 ** rng.integers(-3, 4, C)
+        X = torch.from_numpy(coef.astype(np.complex64)).to(dev)
+        sp = _planes_from_complex64(X, C) if kernel == "planes" else \
+            engine.DeviceSpectra(X, (F, W, R, K, C), (W * R * K * C, R * K * C, K * C, C), 2 * (F - 1), True, C_alloc=C)
+        X64 = X.to(torch.complex128)
+        csm, ab = sums_fp64(X64)
+        S, A = csm.cpu().numpy().reshape(F, C, C), ab.cpu().numpy().reshape(F, C, C)
+        x = X64.reshape(F, R, C)
+        d = x.imag[:, :, :, None] * x.real[:, :, None, :] - x.real[:, :, :, None] * x.imag[:, :, None, :]      # Im(x_i conj x_j) per observation
+        Q, G = (d * d).sum(1).cpu().numpy(), torch.sign(d).sum(1).cpu().numpy()
+        del d
+        Pw = np.real(np.einsum("fii->fi", S))
+        pair = np.sqrt(Pw[:, :, None] * Pw[:, None, :])
+        upper = np.triu(np.ones((C, C), dtype=bool))
+        strict = np.triu(np.ones((C, C), dtype=bool), 1)
+        for split in (1, 2):
+            debug_env("SC_FUSED_SPLIT", split)
+            planes3 = _lib.PLANE_CSM | _lib.PLANE_ABS_IM | _lib.PLANE_IM_SQ
+            accum, n_obs = engine.accumulate(sp, "trials_tapers", planes3, use_fused=True)
+            sign, _ = engine.accumulate(sp, "trials_tapers", _lib.PLANE_SIGN_IM, use_fused=True)
+            assert n_obs == R and accum.dim() == 2 and sign.dim() == 2
+            rec = unpack_record_planes(accum.cpu().numpy(), C)                              # [F, 4, C, C]: re, im, |Im s|, (Im s)^2
+            sg = unpack_record_planes(sign.cpu().numpy(), C)[:, 0]
+            got_S = rec[:, 0] + 1j * rec[:, 1]
+            if kernel == "planes":
+                e_csm = (np.abs(got_S - S)[:, upper] / (3e-6 * np.abs(S)[:, upper] + 2e-7 * pair[:, upper])).max()
+                e_abs = (np.abs(rec[:, 2] - A)[:, strict] / A[:, strict]).max() / 1e-5
+            else:
+                e_csm = (np.abs(got_S - S)[:, upper] / (2e-6 * np.abs(S)[:, upper] + 2e-6 * np.abs(S)[:, upper].max())).max()
+                e_abs = (np.abs(rec[:, 2] - A)[:, strict] / (2e-6 * A[:, strict] + 2e-6 * A[:, strict].max())).max()
+            e_sq = (np.abs(rec[:, 3] - Q)[:, strict] / Q[:, strict]).max()
+            e_sign = np.abs(sg - G)[:, strict].max()
+            worst[(n, split)] = (e_csm, e_abs, e_sq, e_sign)
+    print(f"\n  {kernel} kernel, (blocks, parts): cross-spectra err / bound, |Im s| err / bound, (Im s)^2 relative error, sign sums off by")
+    for k, v in worst.items():
+        print(f"    {k}: {v[0]:.3f}  {v[1]:.3f}  {v[2]:.2e}  {v[3]:g}")
+    for k, (e_csm, e_abs, e_sq, e_sign) in worst.items():
+        assert e_csm <= 1.0 and e_abs <= 1.0, (kernel, k, e_csm, e_abs)
+        assert e_sq <= SQ_BOUND and e_sign <= SIGN_BOUND, (kernel, k, e_sq, e_sign)
+
+
 @pytest.mark.parametrize("artefact,offset", [(30.0, 0.0), (100.0, 0.0), (1e3, 0.0), (1e5, 0.0), (1e7, 0.0), (0.0, 3e3), (100.0, 3e3)])
 def test_one_artefact_sample_or_a_dc_offset_in_a_channel(artefact, offset):
     """The format has ONE scale per channel.  (a) One sample 30 ... 1e7 times the channel's standard deviation (an electrode pop) in

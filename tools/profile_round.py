@@ -62,7 +62,7 @@ open(os.path.join(P, ROUND + "_bench_kernel_stats.txt"), "w").write("\n".join(hd
 
 fetch, write = pmc("fetch.txt", "FETCH_SIZE"), pmc("write.txt", "WRITE_SIZE")
 rows = [("fused2_kernel", "_Z13fused2_kernel", True), ("fused_csm_absim_kernel", "_Z22fused_csm_absim", True),
-        ("fused_combine_kernel", "_Z20fused_combine", True), ("planes_absmax_kernel", "_Z20planes_absmax", True),
+        ("fused_fold_kernel", "_Z17fused_fold", True), ("planes_absmax_kernel", "_Z20planes_absmax", True),
         ("mtfft_long_kernel", "_Z17mtfft_long", False), ("mtfft16_kernel", "_Z14mtfft16", False), ("measure_tile_multi_kernel", "measure_tile_multi", False)]
 txt = ["# rocprofv3 --kernel-trace --pmc FETCH_SIZE  /  --pmc WRITE_SIZE (separate passes, MI355X_MICROARCH.md), python bench.py --steps 2",
        "# --warmup 1 --timed-only (cfg3, 1x MI355X), round " + ROUND[1:].lstrip("0") + " (tools/profile_round.sh).  Counter values are KB per dispatch.  gfx950 correction: FETCH_SIZE",
@@ -82,7 +82,7 @@ stage_b = "fused2_kernel" if "fused2_kernel" in traffic else "fused_csm_absim_ke
 if stage_b in traffic:
     rec = {"kernel_source_hash": kernel_source_hash(),
            "source": "profiles/" + ROUND + "_hbm_traffic.txt (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, FETCH x2 on gfx950)",
-           "cfg3": {"fused_stage_b": traffic[stage_b] + traffic.get("fused_combine_kernel", 0.0),
+           "cfg3": {"fused_stage_b": traffic[stage_b] + traffic.get("fused_fold_kernel", 0.0),
                     "planes_scales": traffic.get("planes_absmax_kernel"),
                     "mtfft_fused": traffic.get("mtfft_long_kernel", traffic.get("mtfft16_kernel")),
                     "measure_epilogue": traffic.get("measure_tile_multi_kernel")}}

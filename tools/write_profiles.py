@@ -18,7 +18,7 @@ s2 = st2["roofline"]["stage_ms"]
 out = ["# rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 2   (cfg3, 1x MI355X, round 1 final; tools/final_profile.sh)",
        "# bench.py HIP-event durations in the same run: mtfft %.3f ms, fused (+combine) %.3f ms, 2x measure %.3f ms; step %.2f ms"
        % (s2["mtfft_fused"], s2["fused_csm_absim"], s2["measure_epilogue"], st2["ms_per_step"]),
-       "# (the fused stage of bench.py = fused_csm_absim_kernel + fused_combine_kernel; averages below include the 2 warm-up launches)"]
+       "# (the fused stage of bench.py = fused_csm_absim_kernel + fused_fold_kernel; averages below include the 2 warm-up launches)"]
 out += lines("kernel_stats.txt")[:6]
 open(os.path.join(P, "r01_bench_kernel_stats.txt"), "w").write("\n".join(out) + "\n")
 
