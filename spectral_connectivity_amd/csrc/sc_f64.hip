@@ -292,10 +292,12 @@ __global__ void __launch_bounds__(256) nonlinear_f64_kernel(F64Args p) {
 #pragma unroll
             for (int e4 = 0; e4 < 4; ++e4) {
                 const int e = wave * 4 + e4;
-                const double v = red[(0 * 16 + e) * 64 + lane] + red[(1 * 16 + e) * 64 + lane] +
-                                 red[(2 * 16 + e) * 64 + lane] + red[(3 * 16 + e) * 64 + lane];
+                double v = red[(0 * 16 + e) * 64 + lane] + red[(1 * 16 + e) * 64 + lane] +
+                           red[(2 * 16 + e) * 64 + lane] + red[(3 * 16 + e) * 64 + lane];
                 const int i = BI[s] * 32 + li * 4 + (e >> 2), jx = BJ[s] * 32 + lj * 4 + (e & 3);
                 const int ti = i >> 4, tj = jx >> 4;
+                // Im(x conj x) = 0: the contracted y x - x y leaves the rounding of the product, and sign() makes +-1 of it
+                if (i == jx && plane < sc_plane_offset(p.planes, SC_PLANE_UNIT)) v = 0.0;
                 if (ti <= tj && tj < p.NB)
                     out[(int64_t)sc_tile_index(ti, tj, p.NB) * SC_TILE_ELEMS + (i & 15) * 16 + (jx & 15)] = v;
             }
@@ -438,7 +440,9 @@ __global__ void __launch_bounds__(256, 2) nonlinear_f64_block_kernel(F64Args p) 
             const int ti = i >> 4, tj = jx >> 4;
             if (ti <= tj && tj < p.NB) {
                 double* tile = out + (int64_t)sc_tile_index(ti, tj, p.NB) * SC_TILE_ELEMS;
-                tile[(i & 15) * 16 + (jx & 15)] = acc[a * 8 + b];
+                // (the diagonal: Im(x conj x) = 0 -- the contracted y x - x y leaves the rounding of the product, and sign()
+                // makes +-1 of it)
+                tile[(i & 15) * 16 + (jx & 15)] = (DIAG && i == jx) ? 0.0 : acc[a * 8 + b];
                 // the lower half of a diagonal 16 x 16 tile (no consumer reads it -- they mirror the upper half -- but it
                 // is not left uninitialised): |Im s| and (Im s)^2 are symmetric, sign(Im s) antisymmetric
                 if (DIAG && a < b && ti == tj)

@@ -2,7 +2,9 @@
 transform, complex128 spectra, cross-spectra on the fp64 matrix cores, double records, float64 measures -- against the
 golden vectors of the real reference and the NumPy oracle, ELEMENTWISE and RELATIVE, no absolute floor beyond 1e-13 of
 the array maximum (the reference's own rounding).  The float32 engine's tests (test_gpu_parity.py ...) state the f32
-bounds; here the bar is the reference's arithmetic itself."""
+bounds; here the bar is the reference's arithmetic itself.  Stage B of this engine at record level -- every launch plan of
+csrc/sc_f64.hip, split bins, the SC_F64_* switches, against extended-precision sums with derived bounds -- is in
+tests/test_gpu_fp64_stage_b.py."""
 import numpy as np
 import pytest
 
