@@ -585,6 +585,28 @@ int sc_imaginary_interaction_f64(const void* d_accum, int64_t n_bins, int64_t n_
                                  int n_groups, int max_group_size, double* d_mic, double* d_mim,
                                  int32_t* d_fail, void* stream);
 
+/* ---- partial and multiple coherence (fp64, from the accumulated CSM; sc_partial.hip; additive, ABI v8) ----
+ * The coherence of two signals after the linear influence of all the other signals is removed, and the share of a signal's
+ * power that all the others explain linearly (the reference has neither).  Per bin record, with S the normalised Hermitian
+ * n_signals x n_signals cross-spectral matrix and G = S^-1:
+ *     partial coherency              gamma_ij = -G_ij / sqrt(G_ii G_jj)     Hermitian; two signals: S_01 / sqrt(S_00 S_11)
+ *     partial coherence magnitude    |gamma_ij|                             in [0, 1], not squared
+ *     multiple coherence magnitude   R_i = sqrt(max(0, 1 - 1 / (S_ii G_ii)))   in [0, 1)
+ * All three are unchanged under S -> D S D (D a positive diagonal); the kernel inverts the unit-diagonal D^-1/2 S D^-1/2, D = diag S,
+ * by a Cholesky factorisation, one 256-thread workgroup per record with the whole problem in LDS (17 C^2 / 2 bytes and a
+ * few rows: 136 KB at 128 signals) -- no workspace.  2 <= n_signals <= sc_partial_coherence_max_signals() = 128.
+ *   d_accum       records with SC_PLANE_CSM, n_bins of them (as sc_canonical_coherence_f64; same checks and error codes,
+ *                 SC_EINVAL also for n_signals outside the range and for three NULL outputs)
+ *   d_coherency   complex128 [n_bins][n_signals][n_signals] or NULL, NaN diagonal
+ *   d_magnitude   double [n_bins][n_signals][n_signals] or NULL, symmetric, NaN diagonal
+ *   d_multiple    double [n_bins][n_signals] or NULL
+ *   d_fail        int32 [1]: number of records without an inverse -- a channel without (finite) power, or a Cholesky pivot of
+ *                 the scaled matrix that is not finite or <= n_signals 2^-52; NaN in all of their outputs */
+int sc_partial_coherence_max_signals(void);
+int sc_partial_coherence_f64(const void* d_accum, int64_t n_bins, int64_t n_signals, uint32_t planes,
+                             int64_t n_observations, void* d_coherency /*complex128*/, double* d_magnitude,
+                             double* d_multiple, int32_t* d_fail, void* stream);
+
 /* ---- delete-one jackknife of power and coherence (sc_jackknife.hip; additive, ABI v8) ------------------------
  * Standard errors that rest on the data (Thomson & Chave 1991; Chronux coherencyc / mtspectrumc with err = [2 p]); the
  * reference has only the closed forms of statistics.py.  Per kept index and bin the delete units u = 1 .. n hold g

@@ -168,6 +168,9 @@ SYMBOLS = {
                                            c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sc_imaginary_interaction_f64": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_void_p, c_void_p,
                                              c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sc_partial_coherence_max_signals": (c_int, []),
+    "sc_partial_coherence_f64": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
     "sc_jackknife_layout": (c_int, [POINTER(SpectraDesc), c_uint32, c_int, c_int64_p, c_int64_p, c_int64_p, c_int64_p]),
     "sc_jackknife_workspace_bytes": (c_int64, [POINTER(SpectraDesc), c_uint32, c_int, c_int64, c_int64]),
     "sc_jackknife_f32": (c_int, [c_void_p, POINTER(SpectraDesc), c_void_p, c_uint32, c_uint32, c_int, c_int64, c_int64, c_int64,

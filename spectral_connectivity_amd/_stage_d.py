@@ -233,6 +233,22 @@ def imaginary_interaction(mem, accum, n_signals, planes, n_obs, members, sizes):
     return mic, mim, mem.read_int(fail)
 
 
+def partial_coherence(mem, accum, n_signals, planes, n_obs, want):
+    """Partial and multiple coherence of every bin record (sc_partial.hip).  ``want``: names out of "coherency", "magnitude",
+    "multiple" -- one call serves them all.  Returns ({name: device array}, n_fail): coherency complex128 and magnitude float64
+    [n_bins, C, C], multiple float64 [n_bins, C]."""
+    n_bins = accum.shape[0]
+    shapes = {"coherency": ((n_bins, n_signals, n_signals), np.complex128), "magnitude": ((n_bins, n_signals, n_signals), np.float64),
+              "multiple": ((n_bins, n_signals), np.float64)}
+    out = {name: mem.empty(*shapes[name]) for name in want}
+    fail = mem.zeros((1,), np.int32)
+    _lib.check(_lib._handle().sc_partial_coherence_f64(mem.ptr(accum), n_bins, n_signals, _planes(mem, accum, planes), n_obs,
+                                                       _ptr(mem, out.get("coherency")), _ptr(mem, out.get("magnitude")),
+                                                       _ptr(mem, out.get("multiple")), mem.ptr(fail), mem.stream()),
+               "sc_partial_coherence_f64")
+    return out, mem.read_int(fail)
+
+
 def jackknife(mem, spectra, expectation_type, total, planes, measures, over, n_units_total, n_freq=None, unit_range=None):
     """Delete-one jackknife sums (sc_jackknife.hip): ONE pass over the complex64 / complex128 spectra (``spectra.X``, described by
     ``spectra.desc``) for every measure of the mask ``measures`` (_lib.JACKKNIFE_MEASURES) against the total CSM record ``total``

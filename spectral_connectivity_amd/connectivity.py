@@ -695,6 +695,75 @@ class Connectivity:
         shape = self._kept_shape() + (self._n_freq, G, G)
         return engine.to_host(mic).reshape(shape), engine.to_host(mim).reshape(shape), labels
 
+    # ---- partial and multiple coherence (Bendat & Piersol 1986, ch. 7; Dahlhaus 2000) ----------------------------
+    def partial_coherency(self):
+        """Coherency of each pair of signals after the linear influence of ALL other signals is removed from both:
+        -G_ij / sqrt(G_ii G_jj) with G the inverse of the cross-spectral matrix.  Where two signals are coherent only because both
+        see a third recorded signal, it is 0 while ``coherency()`` is not; with two signals it is ``coherency()``.
+
+        Returns complex128 [kept axes..., n_frequencies, n_signals, n_signals], Hermitian with a NaN diagonal; the expectation
+        is the object's ``expectation_type``.  Up to sc_partial_coherence_max_signals() = 128 signals (sc_partial.hip;
+        ValueError beyond).  The cross-spectral matrix of fewer observations than signals is singular: everything is NaN (one
+        warning, no device work); a matrix the device cannot invert -- a channel without power, two identical channels, a
+        condition number beyond 1 / (n_signals 2^-52) after scaling to a unit diagonal -- gives NaN in its bin (one warning
+        counts them).  No bias correction, and no choice of the signals to condition on: always all the others.
+        """
+        return self._partial_coherence("coherency")
+
+    def partial_coherence_magnitude(self):
+        """|partial_coherency()|, in [0, 1] and not squared: float64 [kept axes..., n_frequencies, n_signals, n_signals],
+        symmetric with a NaN diagonal.  Computes and limits as partial_coherency."""
+        return self._partial_coherence("magnitude")
+
+    def multiple_coherence_magnitude(self):
+        """The share of each signal's power that all the other signals explain linearly, as a magnitude:
+        sqrt(1 - 1 / (S_ii G_ii)) in [0, 1), float64 [kept axes..., n_frequencies, n_signals].  Computes and limits as
+        partial_coherency."""
+        return self._partial_coherence("multiple")
+
+    def _partial_shape(self, name):
+        """(n_signals after the range check, the signal axes, the whole shape, the dtype) of the output ``name`` of
+        sc_partial_coherence_f64."""
+        C = self._shape5[4]
+        limit = int(_lib.load().sc_partial_coherence_max_signals())
+        if not 2 <= C <= limit:
+            raise ValueError(f"partial and multiple coherence take between 2 and {limit} signals (got {C})")
+        tail = (C,) if name == "multiple" else (C, C)
+        return C, tail, self._kept_shape() + (self._n_freq,) + tail, np.complex128 if name == "coherency" else np.float64
+
+    def _partial_few_observations(self, n_total, C):
+        if n_total < C:
+            logger.warning(f"partial coherence: the cross-spectral matrix of {C} signals from {n_total} observations is singular "
+                           "(fewer observations than signals): NaN")
+        return n_total < C
+
+    def _partial_failed(self, n_fail):
+        if n_fail:
+            logger.warning(f"partial coherence: {n_fail} cross-spectral matrices have no inverse (a channel without power, or not "
+                           "positive definite to rounding): NaN output")
+
+    def _partial_coherence(self, name):
+        from . import engine
+        import torch
+        C, tail, shape, dtype = self._partial_shape(name)
+        accum, n_obs, _ = self._csm_records("interaction", two_sided=False)
+        n_total = self._n_observations_total(n_obs)
+        if self._partial_few_observations(n_total, C):
+            return np.full(shape, np.nan, dtype=dtype)
+        lo, hi, per = self._canonical_bins(accum.shape[0])
+        n_fail = 0
+        if hi > lo:
+            res, n_fail = engine.partial_coherence(accum[lo:hi], C, _lib.PLANE_CSM, n_total, (name,))
+            out = res[name]
+        else:                                  # more processes than bins: this one has nothing to evaluate
+            out = torch.empty((0,) + tail, dtype=engine._TORCH_DTYPES[dtype], device=accum.device)
+        if name == "coherency":                # (gathered as pairs of doubles: not every backend moves complex tensors)
+            out = torch.view_as_complex(self._canonical_gather(torch.view_as_real(out), accum.shape[0], per).contiguous())
+        else:
+            out = self._canonical_gather(out, accum.shape[0], per)
+        self._partial_failed(n_fail)
+        return engine.to_host(out).reshape(shape)
+
     # ---- delete-one jackknife standard errors (Thomson & Chave 1991; Chronux err = [2 p]) --------------------
     def jackknife(self, measures=("coherence_magnitude",), over="trials"):
         """Delete-one jackknife of power and coherence on their variance-stabilising scales: standard errors that rest on the data

@@ -498,6 +498,12 @@ def imaginary_interaction(accum, n_signals, planes, n_obs, members, sizes):
     return _stage_d.imaginary_interaction(TorchMemory(accum.device), accum, n_signals, planes, n_obs, members, sizes)
 
 
+def partial_coherence(accum, n_signals, planes, n_obs, want):
+    """Partial and multiple coherence of every bin record (sc_partial.hip): _stage_d.partial_coherence.  Returns ({name: tensor}
+    for the names of ``want`` out of "coherency", "magnitude", "multiple", n_fail)."""
+    return _stage_d.partial_coherence(TorchMemory(accum.device), accum, n_signals, planes, n_obs, want)
+
+
 def jackknife(spectra, expectation_type, total, planes, measures, over, n_units_total, n_freq=None, unit_range=None):
     """Delete-one jackknife sums (sc_jackknife.hip) of the spectra against the total CSM record ``total`` (partial records are
     folded first): _stage_d.jackknife.  Returns (float64 device tensor laid out as _lib.jackknife_blocks says, n_bins)."""

@@ -283,3 +283,14 @@ class Connectivity(_TorchHostConnectivity):
             self._interaction_failed(n_fail)
         shape = self._kept_shape() + (self._n_freq, G, G)
         return mic.reshape(shape), mim.reshape(shape), labels
+
+    def _partial_coherence(self, name):
+        C, _, shape, dtype = self._partial_shape(name)
+        rec, n_obs, _ = self._csm_records("interaction", two_sided=False)
+        n_total = self._n_observations_total(n_obs)
+        if self._partial_few_observations(n_total, C):
+            return np.full(shape, np.nan, dtype=dtype)
+        mem = self._memory()
+        res, n_fail = _stage_d.partial_coherence(mem, rec, C, _lib.PLANE_CSM, n_total, (name,))
+        self._partial_failed(n_fail)
+        return mem.download(res[name]).reshape(shape)

@@ -41,6 +41,7 @@ _NOT_IN_DATASET = {
     "generalized_partial_directed_coherence", "direct_directed_transfer_function",
     "blockwise_spectral_granger_prediction", "conditional_spectral_granger_prediction",
     "maximized_imaginary_coherence", "multivariate_interaction_measure", "jackknife",
+    "partial_coherency", "partial_coherence_magnitude", "multiple_coherence_magnitude",
 }
 _MT_SKIP = {"time_series", "fft", "tapers", "frequencies", "time"}
 
@@ -73,7 +74,7 @@ def _to_dataarray(xr, m, connectivity, method, signal_names, squeeze, **kwargs):
     values = getattr(connectivity, method)(**kwargs)
     if n_signals > 2 and squeeze:
         logger.warning(f"Squeeze is on, but there are {n_signals} pairs!")
-    if method == "power":
+    if method in ("power", "multiple_coherence_magnitude"):
         out = xr.DataArray(values, coords=[connectivity.time, connectivity.frequencies, names],
                            dims=["time", "frequency", "source"])
     elif n_signals == 2 and squeeze:
