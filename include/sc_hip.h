@@ -323,7 +323,7 @@ int sc_fused2_csm_absim_parts_f32(const void* d_P, const sc_spectra_desc* desc, 
                                   float* d_accum, void* d_workspace, int64_t workspace_bytes, int* n_parts, void* stream);
 /* shader clock (GHz) the device sustained during the last sc_fused2_csm_absim_f32 launch (in-kernel cycle / real-time counters) */
 int sc_debug_fused2_clock(double* ghz);
-/* The diagnostic switches of the library (SC_FUSED_DEBUG, SC_FUSED_SPLIT, SC_MTFFT_DEBUG, SC_WILSON_FFT, ...: ablation tools and
+/* The diagnostic switches of the library (SC_FUSED_DEBUG, SC_FUSED_SPLIT, SC_FUSED_SPLIT_TAIL, SC_MTFFT_DEBUG, SC_WILSON_FFT, ...: ablation tools and
  * the tests of alternative kernels) are environment variables read once when the library is loaded; a host that changes one
  * afterwards calls this to have them read again.  No reference counterpart (the reference has no native code). */
 int sc_debug_reload_env(void);

@@ -525,19 +525,15 @@ __global__ void __launch_bounds__(FU_THREADS) fused_csm_absim_kernel(FusedArgs p
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // n_split workgroups per bin (consecutive workgroups land on consecutive XCDs); part k sums its
-    // share of the observation chunks into its own record: part 0 into the caller's, the others into
-    // the workspace, folded in afterwards by fused_fold_kernel in a fixed order.
-    const int bin = blockIdx.x / p.n_split, part = blockIdx.x - bin * p.n_split;
+    // n_split workgroups per bin (fu_part_range); part k sums its share of the observation chunks into its own record:
+    // part 0 into the caller's, the others into the workspace, folded in afterwards by fused_fold_kernel in a fixed order.
+    const FuPart pr = fu_part_range(p, blockIdx.x);
+    const int bin = pr.bin, o_lo = pr.o_lo;
     const int g = bin / p.F, f = bin - g * p.F;
     ScStage st = p.st;
     st.base = p.st.base + (int64_t)f * st.ax.sF + sc_group_offset(st.ax, g);
-    const int nc = (p.st.n_obs + FU_OC - 1) / FU_OC;
-    const int o_lo = (int)((int64_t)part * nc / p.n_split) * FU_OC;
-    const int o_hi = (int)((int64_t)(part + 1) * nc / p.n_split) * FU_OC;
-    st.n_obs = o_hi < p.st.n_obs ? o_hi : p.st.n_obs;
-    float* rec = (part == 0 ? p.accum : p.ws + (int64_t)(part - 1) * p.n_bins * p.floats_per_bin) +
-                 (int64_t)bin * p.floats_per_bin;
+    st.n_obs = pr.o_hi;
+    float* rec = fu_part_record(p, pr);
     // LDS: the two plane buffers at offset 0 (also the scratch of the final tree reduction), then the f32
     // landing rows of the direct HBM->LDS loads
     unsigned short* planes = reinterpret_cast<unsigned short*>(smem);
@@ -621,16 +617,12 @@ template <bool ABS, bool SQ, bool SGN, bool NORM>
 __global__ void __launch_bounds__(SM_THREADS) small_csm_absim_kernel(FusedArgs p) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x;
-    const int bin = blockIdx.x / p.n_split, part = blockIdx.x - bin * p.n_split;
+    const FuPart pr = fu_part_range(p, blockIdx.x);
+    const int bin = pr.bin, o_lo = pr.o_lo, o_hi = pr.o_hi;
     const int g = bin / p.F, f = bin - g * p.F;
     ScStage st = p.st;
     st.base = p.st.base + (int64_t)f * st.ax.sF + sc_group_offset(st.ax, g);
-    const int nc32 = (p.st.n_obs + FU_OC - 1) / FU_OC;
-    const int o_lo = (int)((int64_t)part * nc32 / p.n_split) * FU_OC;
-    int o_hi = (int)((int64_t)(part + 1) * nc32 / p.n_split) * FU_OC;
-    if (o_hi > p.st.n_obs) o_hi = p.st.n_obs;
-    float* rec = (part == 0 ? p.accum : p.ws + (int64_t)(part - 1) * p.n_bins * p.floats_per_bin) +
-                 (int64_t)bin * p.floats_per_bin;
+    float* rec = fu_part_record(p, pr);
 
     const int C = st.C, B = C >> 1, nbk = B * (B + 1) / 2;     // C even: 2 x 2 blocks of pairs (bi <= bj)
     const int S = SM_THREADS / nbk;                             // observation slices (>= 1: nbk <= 300)
@@ -811,13 +803,18 @@ extern "C" int sc_fused_supported(int64_t n_signals) {
     return (n_signals >= 2 && n_signals <= 256 && (n_signals % 2) == 0) ? 1 : 0;
 }
 
-// Workgroups per bin.  One workgroup fills a CU (LDS), so n_bins workgroups run in ceil(n_bins / n_cu)
-// rounds and the last round may be nearly empty (903 bins on 256 CUs: 4 rounds for 3.53 rounds of
-// work).  Splitting every bin's observations over S workgroups shortens the rounds; pick the S
-// with the fewest (rounds / S), keeping >= 16 chunks per part (S <= 24: few bins with many observations).
-int sc_internal_fused_pick_split(int n_bins, int n_obs) {
+// The parts of a bin (sc_fused_split.h: equal parts, or equal big parts and a short tail part dispatched last) for the device's
+// compute-unit count.  SC_FUSED_SPLIT=n fixes n equal parts, SC_FUSED_SPLIT=n with SC_FUSED_SPLIT_TAIL=t n parts of which the last
+// has t chunks (diagnostics: tests and A/Bs force plans that their shapes would never be given).  The plan of the last shape is
+// kept per thread: sc_fused_workspace_bytes and every launch ask for it, and a step asks for the same one every time.
+void sc_internal_fused_pick_split(int n_bins, int n_obs, FuSplitPlan* plan) {
     const char* e = sc_switch(SC_SW_FUSED_SPLIT);
     const int nc = (n_obs + FU_OC - 1) / FU_OC;
+    if (e) {
+        const char* t = sc_switch(SC_SW_FUSED_SPLIT_TAIL);
+        const int tail = t ? atoi(t) : 0;
+        if (fu_split_forced(nc, atoi(e), tail > 0 ? tail : 0, plan)) return;
+    }
     static int cu_of_device[64] = {0};          // compute units per device, queried once
     int dev = 0, n_cu = 256;
     if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
@@ -827,26 +824,23 @@ int sc_internal_fused_pick_split(int n_bins, int n_obs) {
         }
         n_cu = cu_of_device[dev];
     }
-    int best = 1;
-    double best_cost = 1e30;
-    for (int S = 1; S <= 24; ++S) {
-        if (S > 1 && nc / S < 16) break;
-        // rounds of workgroups x (chunks of a part + ~3 chunks' worth of prologue, record write and drain) x 2 % per extra
-        // partial record the epilogue / combine reads.  Fitted on 125 ... 1000 trials of cfg3 (round 4: with the flat 1.5 % per
-        // part of before, 250 trials took three parts and ran 5 % slower than one)
-        const double rounds = (double)(((int64_t)n_bins * S + n_cu - 1) / n_cu);
-        const double cost = rounds * ((double)nc / S + 3.0) * (1.0 + 0.02 * (S - 1));
-        if (cost < best_cost - 1e-9) { best_cost = cost; best = S; }
+    static thread_local struct { int n_bins, nc, n_cu; FuSplitPlan plan; } last = {0, 0, 0, {}};
+    if (last.n_bins != n_bins || last.nc != nc || last.n_cu != n_cu) {
+        fu_split_plan(n_bins, nc, n_cu, &last.plan);
+        last.n_bins = n_bins; last.nc = nc; last.n_cu = n_cu;
     }
-    if (e && atoi(e) >= 1 && atoi(e) <= 24 && (atoi(e) == 1 || nc / atoi(e) >= 1)) best = atoi(e);
-    return best;
+    *plan = last.plan;
 }
-// The parts per bin of one call: as many of the picked ones as the workspace allows (none: one workgroup per bin).
+// The parts per bin of one call: the picked ones if the workspace holds their records, else as many equal parts as it does
+// (none: one workgroup per bin).
 int sc_internal_fused_set_parts(FusedArgs* a, int n_obs, void* d_workspace, int64_t workspace_bytes) {
-    int S = d_workspace ? sc_internal_fused_pick_split(a->n_bins, n_obs) : 1;
+    FuSplitPlan plan = fu_one_part(n_obs);
+    if (d_workspace) sc_internal_fused_pick_split(a->n_bins, n_obs, &plan);
+    int S = plan.n_parts;
     while (S > 1 && (int64_t)(S - 1) * fu_part_bytes(*a) > workspace_bytes) --S;
+    if (S != plan.n_parts) fu_split_fill(&plan, (n_obs + FU_OC - 1) / FU_OC, S, 0);
     SC_REQUIRE(S == 1 || ((uintptr_t)d_workspace % 16) == 0, "workspace must be 16-byte aligned");
-    a->n_split = S;
+    fu_set_plan(a, plan);
     a->ws = (float*)d_workspace;
     return SC_OK;
 }
@@ -936,7 +930,9 @@ extern "C" int64_t sc_fused_workspace_bytes(const sc_spectra_desc* desc, uint32_
     ScAxes ax;
     const int mode = (planes & SC_PLANE_CSM) ? FU_MODE_CSM : (planes & SC_PLANE_UNIT) ? FU_MODE_UNIT : FU_MODE_SIGN;
     if (fused_setup(nullptr, desc, planes, mode, &a, &ax) != SC_OK) return 0;
-    return (int64_t)(sc_internal_fused_pick_split(a.n_bins, ax.n_obs) - 1) * fu_part_bytes(a);
+    FuSplitPlan plan;
+    sc_internal_fused_pick_split(a.n_bins, ax.n_obs, &plan);
+    return (int64_t)(plan.n_parts - 1) * fu_part_bytes(a);
 }
 
 static int fused_run(const void* d_X, const sc_spectra_desc* desc, uint32_t planes, int mode, float* d_accum,

@@ -773,14 +773,11 @@ __global__ void __launch_bounds__(FU_THREADS) fused2_kernel(Fused2Args a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int clock_slot = blockIdx.x == 0 ? 0 : (blockIdx.x == gridDim.x / 2 ? 1 : (blockIdx.x == gridDim.x - 1 ? 2 : -1));
     if (clock_slot >= 0 && tid == 0) f2_clock_stamp(clock_slot, 0);
-    const int bin = blockIdx.x / p.n_split, part = blockIdx.x - bin * p.n_split;
+    const FuPart pr = fu_part_range(p, blockIdx.x);
+    const int bin = pr.bin, o_lo = pr.o_lo;
     const int g = bin / p.F, f = bin - g * p.F;
-    const int nc = (p.st.n_obs + FU_OC - 1) / FU_OC;
-    const int o_lo = (int)((int64_t)part * nc / p.n_split) * FU_OC;
-    int o_hi = (int)((int64_t)(part + 1) * nc / p.n_split) * FU_OC;
-    if (o_hi > p.st.n_obs) o_hi = p.st.n_obs;
-    const int n_part = o_hi - o_lo;
-    float* rec = (part == 0 ? p.accum : p.ws + (int64_t)(part - 1) * p.n_bins * p.floats_per_bin) + (int64_t)bin * p.floats_per_bin;
+    const int n_part = pr.o_hi - o_lo;
+    float* rec = fu_part_record(p, pr);
     const unsigned char* part_base = a.P + ((int64_t)f * p.st.ax.sF + sc_group_offset(p.st.ax, g) + (int64_t)o_lo * a.obs_rows) * a.row_bytes;
     lds_u8* lds = (lds_u8*)smem;
     constexpr int NHALF = NB32 <= 2 ? 2 : 1, CH = FU_OC * NHALF;

@@ -1,10 +1,12 @@
 // sc_fused_common.h -- what the two one-pass stage-B kernels share (sc_fused.hip: complex64 spectra, split into bf16 pieces
 // while staging; sc_fused2.hip: spectra that stage A already wrote as bf16 pieces): launch arguments, the staged-block
 // map and its filler, the 32x32 block tables of the |Im s| role and its accumulate step, the (shape, op) dispatch, the
-// record geometry, the plane passes and the host helpers of the split-bin scheme.  The launch plan is sc_fused_plan.h's.
+// record geometry, the plane passes and the host helpers of the split-bin scheme.  The launch plan is sc_fused_plan.h's, the
+// parts a bin is split into sc_fused_split.h's.
 #pragma once
 #include "sc_stage.h"
 #include "sc_fused_plan.h"
+#include "sc_fused_split.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
@@ -50,7 +52,12 @@ struct FusedArgs {
                          // (plane passes: csm_plane = -1, the four CSM waves only stage)
     unsigned seg0, seg1, seg2, seg3, seg_n;   // tiles of CSM wave w (fu_assign_rows): segw = row A | first column A << 4 |
                          // row B << 8 | first column B << 12; byte w of seg_n = count A | count B << 4
-    int n_split;         // workgroups per bin: part k sums the chunks [k NC / n_split, (k+1) NC / n_split)
+    int n_split;         // workgroups per bin: part k sums the chunks [fu_split_bound(k), fu_split_bound(k + 1)) (fu_part_range)
+    int n_big;           // the first n_big parts of ALL bins are dispatched ahead of the rest (FuSplitPlan: n_split for equal parts,
+                         // n_split - 1 with a tail part)
+    int n_chunks, tail;  // the plan's bounds in closed form: the n_big parts share the first n_chunks - tail chunks equally, the tail
+                         // part (tail > 0) has the rest.  (A bounds array in the kernel arguments, read with a scalar load that depends
+                         // on the block number, cost every workgroup its latency: stage B 3.55 -> 3.57 ms at cfg3 with unchanged parts.)
     float* ws;           // partial records of parts 1 .. n_split-1: [n_split-1][n_bins][floats_per_bin]
     int debug_skip;      // profiling aid (env SC_FUSED_DEBUG, bit mask; results are WRONG when set):
                          // 1 = CSM waves skip their MFMAs, 2 = abs waves skip theirs, 8 = no HBM loads after chunk 0
@@ -82,6 +89,23 @@ __device__ __forceinline__ int fu_lane() {
     int l;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
     return l;
+}
+// Block -> (bin, part) and the part's observations [o_lo, o_hi): blocks 0 ... n_bins n_big - 1 are the big parts in (bin, part)
+// order, the blocks behind them the tail parts of the bins (n_big = n_split: no tail, every block in the first range).  Part 0
+// writes the caller's record, part k the k-th of the workspace.
+struct FuPart { int bin, part, o_lo, o_hi; };
+__device__ __forceinline__ FuPart fu_part_range(const FusedArgs& p, int block) {
+    FuPart r;
+    const int n_front = p.n_bins * p.n_big;
+    r.bin = block < n_front ? block / p.n_big : block - n_front;
+    r.part = block < n_front ? block - r.bin * p.n_big : p.n_split - 1;
+    r.o_lo = fu_split_bound(r.part, p.n_big, p.n_chunks, p.tail) * FU_OC;
+    r.o_hi = fu_split_bound(r.part + 1, p.n_big, p.n_chunks, p.tail) * FU_OC;
+    if (r.o_hi > p.st.n_obs) r.o_hi = p.st.n_obs;
+    return r;
+}
+__device__ __forceinline__ float* fu_part_record(const FusedArgs& p, const FuPart& r) {
+    return (r.part == 0 ? p.accum : p.ws + (int64_t)(r.part - 1) * p.n_bins * p.floats_per_bin) + (int64_t)r.bin * p.floats_per_bin;
 }
 enum { FU_OP_ABS = 0, FU_OP_SQ = 1, FU_OP_SIGN = 2, FU_OP_UNIT = 3 };     // UNIT: CSM role only, rows normalised at staging
 
@@ -203,14 +227,25 @@ __device__ __forceinline__ void fu_accumulate16(f32x16& acc, const f32x16& d) {
 
 // ---- host side ----------------------------------------------------------------------------------
 // defined in sc_fused.hip
-int sc_internal_fused_pick_split(int n_bins, int n_obs);              // workgroups per bin
-int sc_internal_fused_set_parts(FusedArgs* a, int n_obs, void* d_workspace, int64_t workspace_bytes);   // n_split, ws of a call
+void sc_internal_fused_pick_split(int n_bins, int n_obs, FuSplitPlan* plan);   // the parts of a bin (sc_fused_split.h, the switches)
+int sc_internal_fused_set_parts(FusedArgs* a, int n_obs, void* d_workspace, int64_t workspace_bytes);   // n_split, parts, ws of a call
 void sc_internal_fu_assign_rows(FusedArgs* a);                         // tiles of the four CSM waves
 int sc_internal_fused_combine(const FusedArgs& a, hipStream_t stream); // fold the parts' records (n_split > 1)
 
 // bytes of one part's records: the workspace holds those of parts 1 ... n_split - 1
 inline int64_t fu_part_bytes(const FusedArgs& a) { return (int64_t)a.n_bins * a.floats_per_bin * (int64_t)sizeof(float); }
 
+inline void fu_set_plan(FusedArgs* a, const FuSplitPlan& plan) {
+    a->n_split = plan.n_parts;
+    a->n_big = plan.tail ? plan.n_parts - 1 : plan.n_parts;
+    a->n_chunks = plan.bound[plan.n_parts];
+    a->tail = plan.tail;
+}
+inline FuSplitPlan fu_one_part(int n_obs) {
+    FuSplitPlan plan;
+    fu_split_fill(&plan, (n_obs + FU_OC - 1) / FU_OC, 1, 0);
+    return plan;
+}
 // The record of `planes` for the shape `ax`: tiles, bins, floats per bin, where its planes sit (-1: absent), one part.
 inline void fu_record_geometry(FusedArgs* a, const ScAxes& ax, uint32_t planes) {
     auto offset = [&](uint32_t plane) { return (planes & plane) ? sc_plane_offset(planes, plane) : -1; };
@@ -226,7 +261,7 @@ inline void fu_record_geometry(FusedArgs* a, const ScAxes& ax, uint32_t planes) 
     a->sq_plane = offset(SC_PLANE_IM_SQ);
     a->sign_plane = offset(SC_PLANE_SIGN_IM);
     a->nl_op = FU_OP_ABS;
-    a->n_split = 1;
+    fu_set_plan(a, fu_one_part(ax.n_obs));
     a->ws = nullptr;
 }
 // what the headline pass writes, hence folds: the CSM planes (re, im) and |Im s| as far as present

@@ -1,8 +1,8 @@
 // sc_measure.hip -- measures epilogue: accumulated sums -> connectivity measures.
 //
-// One workgroup per (bin, upper-triangular 16x16 tile): the tile's planes are read once, coalesced,
-// the measure is evaluated for the tile and for its mirror image (conjugate / sign rules per measure),
-// and both 16x16 output blocks are written as 64-byte rows (the mirror through an LDS transpose).
+// One workgroup per (bin, upper-triangular 16x16 tile) -- the several-measures kernel: per 32x32 block of four --: the tile's
+// planes are read once, coalesced, the measure is evaluated for the tile and for its mirror image (conjugate / sign rules per
+// measure), and both output blocks are written row by row (the mirror through an LDS transpose).
 // Divides by n_observations (AFTER any cross-GPU sum) and applies the reference's algebra literally,
 // in fp64 (the epilogue touches W*F*C^2 elements once; it is HBM-bound and tiny next to stage B):
 //   coherency   connectivity.py:632-657   S_ij / max(sqrt(P_i P_j), eps), diagonal NaN
@@ -55,6 +55,7 @@ struct MeasureArgs {
     int n_multi;                 // measure_tile_multi_kernel: the real-valued measures of one launch ...
     int multi[SC_MEASURE_MULTI_MAX];
     void* multi_out[SC_MEASURE_MULTI_MAX];      // ... and where each goes
+    int vec_out;                 // ... in 4-entry stores: n_signals a multiple of 4 and every output 16-byte aligned (OutT 32-byte: 32)
 };
 
 template <typename Rec>
@@ -226,75 +227,111 @@ __global__ void __launch_bounds__(256) measure_tile_kernel(MeasureArgs a) {
     }
 }
 
-// Several real-valued measures of the same record in ONE launch: the tile's planes are read once (every plane any of the
-// measures needs), each measure is evaluated for the tile and its mirror image like measure_tile_kernel does.
-#ifndef MEASURE_MULTI_TPW
-#define MEASURE_MULTI_TPW 1       // tiles per workgroup.  (Four -- "a tile is too little per launch slot" -- measured slower: two measures
-                                  // at the cfg3 shape 0.139 ms with 4, 0.142 with 2, 0.143 with 9, 0.118 with ONE: the tiles of a
-                                  // workgroup run one after the other, each behind its own loads, and 32 508 small workgroups hide
-                                  // that latency better than 8 127 longer ones; tools/measure_ab.py over variant libraries)
-#endif
+// Several real-valued measures of the same record in ONE launch.  A workgroup owns a 32 x 32 block of channel pairs (bi <= bj,
+// 32-channel blocks, upper triangle row-major): one wave per 16 x 16 tile of it, a lane four consecutive entries of a tile row --
+// 16-byte loads, a wave's load instruction one contiguous kilobyte, and every plane of every part a lane needs is requested
+// before the first is used (a part's loads go out together; "four tiles per workgroup, one after the other" lost to one tile per
+// workgroup in round 4 because each tile waited behind its own loads).  The 64 diagonal powers of the block's rows and columns
+// are read once, by wave 0, and shared through LDS.  The values go through LDS as well, so that a store instruction writes
+// whole rows of the block -- 128-byte lines for the direct block and for the mirrored one alike (the one-tile kernel wrote
+// 64-byte half lines).  Arithmetic as before: parts summed in part order in the records' own precision, measure_value on the
+// upper entry, the entry (j, i) taken from (i, j) -- every real-valued measure is even or odd under (i, j) -> (j, i) (conjugated
+// s, swapped powers), bit for bit what measure_value(measure_mirror(v)) returns, inside a diagonal tile too.
+// cfg3, coherence + wPLI (tools/measure_ab.py over the two libraries, profiles/tapered_split_ab.txt): 0.110 / 0.121 / 0.137 ms from
+// one / two / three records against 0.114 / 0.146 / 0.190 of the one-tile kernel.
 template <typename OutT, typename AccT, bool PARTS = false>
 __global__ void __launch_bounds__(256) measure_tile_multi_kernel(MeasureArgs a) {
-    __shared__ MeasureIn raw[256];
-    __shared__ double mir[256];
-    const int tid = threadIdx.x, ii = tid >> 4, jj = tid & 15;
+    typedef AccT AccV __attribute__((ext_vector_type(4)));
+    typedef OutT OutV __attribute__((ext_vector_type(4)));
+    __shared__ OutT val[SC_MEASURE_MULTI_MAX][32][33];
+    __shared__ double pw[64];
+    const int tid = threadIdx.x, q = tid >> 6, lane = tid & 63, ii = lane >> 2, j4 = (lane & 3) * 4;
     const int64_t bin = blockIdx.x;
-    using Rec = typename RecSel<AccT, PARTS>::type;
-    const Rec rec = make_rec<AccT, PARTS>(a) + bin * a.floats_per_bin;
+    int bi = 0, len = (a.NB + 1) / 2, t = blockIdx.y;                    // upper-triangular 32 x 32 block (bi <= bj), row-major
+    while (t >= len) { t -= len; ++bi; --len; }
+    const int bj = bi + t;
+    const int ti = 2 * bi + (q >> 1), tj = 2 * bj + (q & 1);             // this wave's tile
+    const bool have = ti <= tj && tj < a.NB;
     const int64_t plane = (int64_t)a.n_tiles * SC_TILE_ELEMS;
-    const int64_t obase = bin * (int64_t)a.C * a.C;
-    int ti = 0, len = a.NB, t = blockIdx.y * MEASURE_MULTI_TPW;          // upper-triangular tile (ti <= tj), row-major
-    while (t >= len) { t -= len; ++ti; --len; }
-    for (int u = 0; u < MEASURE_MULTI_TPW; ++u) {
-        const int tile_id = blockIdx.y * MEASURE_MULTI_TPW + u;
-        if (tile_id >= a.n_tiles) break;
-        const int tj = ti + t;
-        const Rec tile = rec + ((int64_t)tile_id * SC_TILE_ELEMS + ii * 16 + jj);
-        MeasureIn v = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        if (a.p_csm >= 0) {
-            v.s_re = (double)tile[a.p_csm * plane];
-            v.s_im = (double)tile[(a.p_csm + 1) * plane];
-            v.p_i = (double)rec[a.p_csm * plane + (int64_t)sc_tile_index(ti, ti, a.NB) * SC_TILE_ELEMS + ii * 17];
-            v.p_j = (double)rec[a.p_csm * plane + (int64_t)sc_tile_index(tj, tj, a.NB) * SC_TILE_ELEMS + jj * 17];
-        }
-        if (a.p_abs >= 0) v.sa = (double)tile[a.p_abs * plane];
-        if (a.p_sq >= 0) v.sq = (double)tile[a.p_sq * plane];
-        if (a.p_sign >= 0) v.sg = (double)tile[a.p_sign * plane];
-        if (a.p_unit >= 0) {
-            v.u_re = (double)tile[a.p_unit * plane];
-            v.u_im = (double)tile[(a.p_unit + 1) * plane];
-        }
-        const bool dtile = ti == tj;
-        if (dtile) {
-            raw[tid] = v;
-            __syncthreads();
-            if (ii > jj) v = measure_mirror(raw[jj * 16 + ii]);
-            __syncthreads();
-        }
-        const int i = ti * 16 + ii, j = tj * 16 + jj;
-        for (int m = 0; m < a.n_multi; ++m) {
-            OutT* outf = (OutT*)a.multi_out[m];
-            const int w = a.multi[m];
-#ifdef MEASURE_AB_NOMATH      // (A/B: what the loads, the LDS mirror and the stores cost without the fp64 algebra; results wrong)
-            const double direct = v.s_re + v.sa + w;
-#else
-            const double direct = measure_value(w, a.n_obs, a.rn_obs, v, i == j).x;
-#endif
-            if (i < a.C && j < a.C) outf[obase + (int64_t)i * a.C + j] = (OutT)direct;
-            if (!dtile) {
-                // entry (j, i): every real-valued measure is even or odd under (i, j) -> (j, i) (conjugated s, swapped
-                // powers), bit for bit what measure_value(measure_mirror(v)) returns -- the fp64 algebra (sqrt, divisions)
-                // is what this kernel spends its time on, so it runs once per pair
-                const double sgn = (w == SC_M_COHERENCE_PHASE || w == SC_M_PLI || w == SC_M_WPLI) ? -1.0 : 1.0;
-                mir[jj * 16 + ii] = sgn * direct;
-                __syncthreads();
-                const int r = tj * 16 + ii, c = ti * 16 + jj;
-                if (r < a.C && c < a.C) outf[obase + (int64_t)r * a.C + c] = (OutT)mir[tid];
-                __syncthreads();
+    const int64_t toff = have ? (int64_t)sc_tile_index(ti, tj, a.NB) * SC_TILE_ELEMS + ii * 16 + j4 : 0;
+    // wave 0: lane l < 32 the power of channel l of block bi, the others of channel l - 32 of block bj
+    const int pch = (lane < 32 ? 32 * bi : 32 * bj - 32) + lane, ptile = pch >> 4;
+    const bool pw_ok = q == 0 && a.p_csm >= 0 && ptile < a.NB;
+    const int64_t poff = pw_ok ? a.p_csm * plane + (int64_t)sc_tile_index(ptile, ptile, a.NB) * SC_TILE_ELEMS + (pch & 15) * 17 : 0;
+    const int n_parts = PARTS ? a.n_parts : 1;
+    const AccV zero = {0, 0, 0, 0};
+    AccV s_re = zero, s_im = zero, s_sa = zero, s_sq = zero, s_sg = zero, s_ur = zero, s_ui = zero;
+    AccT s_pw = 0;
+    for (int k = 0; k < n_parts; ++k) {
+        const AccT* r = (k == 0 ? (const AccT*)a.accum.p : (const AccT*)a.rest + (int64_t)(k - 1) * a.part_stride) + bin * a.floats_per_bin;
+        AccV l_re = zero, l_im = zero, l_sa = zero, l_sq = zero, l_sg = zero, l_ur = zero, l_ui = zero;
+        AccT l_pw = 0;
+        if (have) {
+            if (a.p_csm >= 0) {
+                l_re = *reinterpret_cast<const AccV*>(r + a.p_csm * plane + toff);
+                l_im = *reinterpret_cast<const AccV*>(r + (a.p_csm + 1) * plane + toff);
+            }
+            if (a.p_abs >= 0) l_sa = *reinterpret_cast<const AccV*>(r + a.p_abs * plane + toff);
+            if (a.p_sq >= 0) l_sq = *reinterpret_cast<const AccV*>(r + a.p_sq * plane + toff);
+            if (a.p_sign >= 0) l_sg = *reinterpret_cast<const AccV*>(r + a.p_sign * plane + toff);
+            if (a.p_unit >= 0) {
+                l_ur = *reinterpret_cast<const AccV*>(r + a.p_unit * plane + toff);
+                l_ui = *reinterpret_cast<const AccV*>(r + (a.p_unit + 1) * plane + toff);
             }
         }
-        if (++t >= len) { t = 0; ++ti; --len; }
+        if (pw_ok) l_pw = r[poff];
+        if (k == 0) { s_re = l_re; s_im = l_im; s_sa = l_sa; s_sq = l_sq; s_sg = l_sg; s_ur = l_ur; s_ui = l_ui; s_pw = l_pw; }
+        else { s_re += l_re; s_im += l_im; s_sa += l_sa; s_sq += l_sq; s_sg += l_sg; s_ur += l_ur; s_ui += l_ui; s_pw += l_pw; }
+    }
+    if (q == 0) pw[lane] = (double)s_pw;
+    __syncthreads();
+    const int r_blk = (q >> 1) * 16 + ii, i = 32 * bi + r_blk;
+    if (have) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c_blk = (q & 1) * 16 + j4 + e, j = 32 * bj + c_blk;
+            if (i > j) continue;                                         // lower half of a diagonal tile: from its mirror
+            MeasureIn v = {(double)s_re[e], (double)s_im[e], pw[r_blk], pw[32 + c_blk], (double)s_sa[e], (double)s_sq[e], (double)s_sg[e],
+                           (double)s_ur[e], (double)s_ui[e]};
+            for (int m = 0; m < a.n_multi; ++m) {
+#ifdef MEASURE_AB_NOMATH      // (A/B: what the loads, the LDS transpose and the stores cost without the fp64 algebra; results wrong)
+                val[m][r_blk][c_blk] = (OutT)(v.s_re + v.sa + a.multi[m]);
+#else
+                val[m][r_blk][c_blk] = (OutT)measure_value(a.multi[m], a.n_obs, a.rn_obs, v, i == j).x;
+#endif
+            }
+        }
+    }
+    __syncthreads();
+    // rows of the block, eight lanes a row: the direct block at (bi, bj), then (bi < bj) the mirrored one at (bj, bi)
+    const int r = tid >> 3, c0 = (tid & 7) * 4;
+    const int64_t obase = bin * (int64_t)a.C * a.C;
+    auto put = [&](OutT* out, int row, int col, const OutT x[4]) {
+        if (row >= a.C) return;
+        OutT* dst = out + obase + (int64_t)row * a.C + col;
+        if (a.vec_out) {                                                 // C a multiple of 4: col < C means col + 3 < C
+            if (col >= a.C) return;
+            const OutV xv = {x[0], x[1], x[2], x[3]};
+            *reinterpret_cast<OutV*>(dst) = xv;          // (streaming stores measured the same: DESIGN 4.4)
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (col + e < a.C) dst[e] = x[e];
+        }
+    };
+    for (int m = 0; m < a.n_multi; ++m) {
+        const int w = a.multi[m];
+        const OutT sgn = (w == SC_M_COHERENCE_PHASE || w == SC_M_PLI || w == SC_M_WPLI) ? (OutT)-1 : (OutT)1;
+        OutT* out = (OutT*)a.multi_out[m];
+        OutT x[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[e] = (bi < bj || r <= c0 + e) ? val[m][r][c0 + e] : sgn * val[m][c0 + e][r];
+        put(out, 32 * bi + r, 32 * bj + c0, x);
+        if (bi < bj) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x[e] = sgn * val[m][c0 + e][r];
+            put(out, 32 * bj + r, 32 * bi + c0, x);
+        }
     }
 }
 
@@ -360,7 +397,16 @@ static int measure_multi_run(const void* d_accum, int64_t n_bins, int64_t n_sign
     a.measure = measures[0];
     a.total = n_bins * n_signals * n_signals;
     SC_REQUIRE(n_bins < (int64_t)1 << 31 && a.n_tiles <= 65535, "output too large for one launch");
-    const dim3 grid((unsigned)n_bins, (unsigned)((a.n_tiles + MEASURE_MULTI_TPW - 1) / MEASURE_MULTI_TPW));
+    // 4-element loads of the records: their tiles start at multiples of 256 elements
+    const uintptr_t rec_align = 4 * (a.accum.f64 ? sizeof(double) : sizeof(float));
+    SC_REQUIRE((uintptr_t)d_accum % rec_align == 0 && (n_parts == 1 || ((uintptr_t)d_rest % rec_align == 0 && part_stride % 4 == 0)),
+               "records must be aligned to four of their elements");
+    const uintptr_t out_align = 4 * (wide ? sizeof(double) : sizeof(float));
+    a.vec_out = n_signals % 4 == 0 ? 1 : 0;
+    for (int m = 0; m < n_measures; ++m)
+        if ((uintptr_t)d_outs[m] % out_align) a.vec_out = 0;
+    const int nb32 = (a.NB + 1) / 2;
+    const dim3 grid((unsigned)n_bins, (unsigned)(nb32 * (nb32 + 1) / 2));
     hipStream_t st = (hipStream_t)stream;
     if (n_parts > 1) {
         if (a.accum.f64) {

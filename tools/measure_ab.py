@@ -1,4 +1,5 @@
-"""Epilogue alone at the cfg3 shape (coherence magnitude + wPLI from one record): median of 20 launches, ms."""
+"""Epilogue alone at the cfg3 shape (coherence magnitude + wPLI from one record, or -- `measure_ab.py N` -- from N
+partial records, as stage B leaves them on the headline path): median of 20 launches, ms."""
 import os
 import sys
 import time
@@ -15,6 +16,9 @@ X = torch.view_as_complex(torch.randn((F, W, R, K, C, 2), dtype=torch.float32, d
 sp = engine.DeviceSpectra(X, (F, W, R, K, C), (W * R * K * C, R * K * C, K * C, C), 256, True, C_alloc=C)
 planes = _lib.PLANE_CSM | _lib.PLANE_ABS_IM
 accum, n = engine.accumulate(sp, "trials_tapers", planes)
+n_parts = int(sys.argv[1]) if len(sys.argv) > 1 else 1
+if n_parts > 1:
+    accum = torch.stack([accum] * n_parts).contiguous()
 ts = []
 for rep in range(24):
     torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -23,4 +27,4 @@ for rep in range(24):
     if rep == 0:
         chk = [float(o.double().nan_to_num().abs().sum()) for o in out]
     out = None
-print(f"measure_multi(coherence magnitude, wPLI): {np.median(ts[4:]) * 1e3:.3f} ms   checksums {chk}")
+print(f"measure_multi(coherence magnitude, wPLI), {n_parts} part(s): {np.median(ts[4:]) * 1e3:.3f} ms   checksums {chk}")
