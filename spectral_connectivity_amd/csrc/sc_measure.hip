@@ -15,6 +15,11 @@
 
 #define SC_EPS64 2.220446049250313e-16
 
+// Products and sums are fused where one expression writes them, a * b + c, and nowhere else: the default lets the optimiser fuse
+// what it finds after inlining, so the same measure_value rounded differently from one kernel instantiation to the next (PLV of a
+// double record: the parts-summing one-launch kernel against the one-tile kernel, last bit).
+#pragma clang fp contract(on)
+
 // records as float (f32 engine) or double (f64 engine) elements: the element type is a template parameter of the kernels
 // here (the epilogue is launched on the headline path; a run-time switch per load cost 20 %)
 template <typename AccT>
@@ -114,6 +119,11 @@ __device__ inline double measure_rcp(double x) {
     return r;
 }
 
+// clip(x, 0, 1) and max(x, eps) as NumPy's: a NaN stays a NaN (fmin / fmax return their other argument, which turned the coherence
+// of a non-finite channel into 0 or 1)
+__device__ inline double measure_clip01(double x) { return x < 0.0 ? 0.0 : (x > 1.0 ? 1.0 : x); }
+__device__ inline double measure_floor_eps(double x) { return x < SC_EPS64 ? SC_EPS64 : x; }
+
 // one measure of one entry; complex measures return (re, im), real ones (value, 0)
 __device__ inline double2 measure_value(int measure, double n, double rn, MeasureIn v, bool diag) {
     const double NaN = nan("");
@@ -130,19 +140,19 @@ __device__ inline double2 measure_value(int measure, double n, double rn, Measur
     case SC_M_COHERENCE_PHASE: {
         // 1 / max(sqrt(p_i p_j), eps) as ONE reciprocal square root (v_rsq_f64 + refinement) instead of a square root and a division
         const double pp = p_i * p_j;
-        const double rden = pp > SC_EPS64 * SC_EPS64 ? rsqrt(pp) : 1.0 / SC_EPS64;
+        const double rden = pp <= SC_EPS64 * SC_EPS64 ? 1.0 / SC_EPS64 : rsqrt(pp);      // (a NaN product: NaN, like max(sqrt(NaN), eps))
         double c_re = s_re * rden, c_im = s_im * rden;
         if (diag) { c_re = NaN; c_im = NaN; }
         if (measure == SC_M_COHERENCY) return make_double2(c_re, c_im);
         if (measure == SC_M_COHERENCE_MAGNITUDE) {
             const double mag = c_re * c_re + c_im * c_im;
-            return make_double2((diag ? NaN : fmin(fmax(mag, 0.0), 1.0)), 0.0);
+            return make_double2((diag ? NaN : measure_clip01(mag)), 0.0);
         }
         return make_double2((diag ? NaN : atan2(c_im, c_re)), 0.0);
     }
     case SC_M_IMAGINARY_COHERENCE: {
-        const double den = fmax(sqrt(p_i * p_j), SC_EPS64);
-        return make_double2(fmin(fmax(fabs(s_im / den), 0.0), 1.0), 0.0);
+        const double den = measure_floor_eps(sqrt(p_i * p_j));
+        return make_double2(measure_clip01(fabs(s_im / den)), 0.0);
     }
     case SC_M_PLV:
         return make_double2((sqrt(v.u_re * v.u_re + v.u_im * v.u_im) * rn), 0.0);
