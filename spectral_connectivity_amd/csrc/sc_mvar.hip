@@ -1229,15 +1229,28 @@ __global__ void m_transfer(const cd* G, const double* hinv, cd* H, double* sq, i
     if (threadIdx.x == 0) sq[p * F + f] = red[0];
 }
 
+// The normalisations of the five measures are sums of C (dDTF: F C) non-negative terms, one thread per sum, in a fixed order.  A plain
+// running sum drifts by ~sqrt(C / 36) roundings (DTF against the host's from the same H: 13 x 2^-52 at 260 signals; against the reference
+// 17.6 at 512, where NumPy's pairwise sums stay at 5); the compensated sum keeps them within a rounding or two of exact at every size
+// (2.4 and 6.4: profiles/mvar_measure_accuracy.txt).
+struct MvSum {
+    double s = 0.0, c = 0.0;
+    __device__ __forceinline__ void add(double x) {
+        const double y = x - c, t = s + y;
+        c = (t - s) - y;
+        s = t;
+    }
+};
+
 // inflow over frequencies and sources: tot[p][i] = sum_f sum_j |H_ij|^2 (dDTF, connectivity.py:1420-1422)
 __global__ void m_inflow_all(const cd* H, double* tot, int64_t F, int C) {
     const int64_t p = blockIdx.x;
     const int E = C * C;
     for (int i = threadIdx.x; i < C; i += blockDim.x) {
-        double a = 0.0;
+        MvSum a;
         for (int64_t f = 0; f < F; ++f)
-            for (int j = 0; j < C; ++j) { const cd v = H[(p * F + f) * E + i * C + j]; a += v.x * v.x + v.y * v.y; }
-        tot[p * C + i] = a;
+            for (int j = 0; j < C; ++j) { const cd v = H[(p * F + f) * E + i * C + j]; a.add(v.x * v.x + v.y * v.y); }
+        tot[p * C + i] = a.s;
     }
 }
 
@@ -1257,22 +1270,22 @@ __global__ void m_measure(const cd* H, const cd* Amv, const double* sigma, const
     }
     __syncthreads();
     for (int r = threadIdx.x; r < C; r += blockDim.x) {
-        double a = 0.0;
+        MvSum a;
         if (which == SC_MVAR_DTF) {
-            for (int j = 0; j < C; ++j) a += pw[r * C + j];                       // inflow into i = r
+            for (int j = 0; j < C; ++j) a.add(pw[r * C + j]);                     // inflow into i = r
         } else if (which == SC_MVAR_DC) {
             const double nv = sigma[p * E + r * C + r];
-            for (int j = 0; j < C; ++j) a += nv * pw[r * C + j];
+            for (int j = 0; j < C; ++j) a.add(nv * pw[r * C + j]);
         } else if (which == SC_MVAR_PDC || which == SC_MVAR_DDTF) {
             if (which == SC_MVAR_DDTF) {                                          // PDC needs |A|^2 column sums
-                for (int i = 0; i < C; ++i) { const cd v = Amv[b * E + i * C + r]; a += v.x * v.x + v.y * v.y; }
+                for (int i = 0; i < C; ++i) { const cd v = Amv[b * E + i * C + r]; a.add(v.x * v.x + v.y * v.y); }
             } else {
-                for (int i = 0; i < C; ++i) a += pw[i * C + r];                   // outflow from j = r
+                for (int i = 0; i < C; ++i) a.add(pw[i * C + r]);                 // outflow from j = r
             }
         } else {                                                                  // gPDC
-            for (int i = 0; i < C; ++i) a += pw[i * C + r] / sigma[p * E + i * C + i];
+            for (int i = 0; i < C; ++i) a.add(pw[i * C + r] / sigma[p * E + i * C + i]);
         }
-        nrm[r] = a;
+        nrm[r] = a.s;
     }
     __syncthreads();
     for (int e = threadIdx.x; e < E; e += blockDim.x) {
