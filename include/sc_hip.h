@@ -3,7 +3,8 @@
  *
  * This is the drop-in boundary for ONE path of the reference: time series ->
  * DPSS-tapered sliding-window FFT -> cross-spectral matrix -> expectation ->
- * coherence / PLI / wPLI / PLV / PPC (-> pairwise spectral Granger, canonical coherence).
+ * coherence / PLI / wPLI / PLV / PPC (-> pairwise spectral Granger, canonical coherence;
+ * delete-one jackknife standard errors of power, coherence and the phase-lag family).
  * It replaces the reference's array-backend plug point, the import-time switch
  * `xp = cupy | numpy` plus `fft/ifft/...` (transforms.py:405-439, connectivity.py:31-65,
  * minimum_phase_decomposition.py:14-26), for the call sites listed per function below.
@@ -646,6 +647,59 @@ int sc_jackknife_f32(const void* d_X /*float2*/, const sc_spectra_desc* desc, co
 int sc_jackknife_f64(const void* d_X /*double2*/, const sc_spectra_desc* desc, const void* d_total, uint32_t planes,
                      uint32_t measures, int over, int64_t unit_begin, int64_t unit_end, int64_t n_units_total, double* d_out,
                      void* d_workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- delete-one jackknife of the phase-lag family (sc_jackknife.hip, jk_phase_kernel; additive, ABI v8) -----
+ * The same pass, units, `over`, unit range, workspace scheme and output triple (theta, sum_u d_u, sum_u d_u^2) as sc_jackknife_*
+ * above, for the measures the reference has no statistics for (FieldTrip: ft_connectivity_wpli's jackknife).  Per observation
+ * Im s = Im(x_i conj(x_j)); a unit's sums a_u = sum Im s, b_u = sum |Im s|, c_u = sum sign(Im s), q_u = sum (Im s)^2 (summed in the
+ * spectra's precision, c_u an integer) are taken from the totals A, B, N, Q -- the planes SC_PLANE_CSM (im), _ABS_IM, _SIGN_IM and
+ * _IM_SQ of d_total -- and with n = n_units_total g observations (n' = (n_units_total - 1) g for a delete-one set), all on the
+ * identity scale and in fp64:
+ *     SC_JACKKNIFE_PHASE_PLI             theta = N / n                                               antisymmetric
+ *     SC_JACKKNIFE_PHASE_WPLI            theta = (A / n) / w, w = B / n, w = 1 where w < 2^-52       antisymmetric
+ *     SC_JACKKNIFE_PHASE_DEBIASED_PLI2   theta = (n (N / n)^2 - 1) / (n - 1)                         symmetric
+ *     SC_JACKKNIFE_PHASE_DEBIASED_WPLI2  theta = (A^2 - Q) / (B^2 - Q), NaN where B^2 - Q == 0       symmetric
+ * (the full estimates are sc_measure_*'s SC_M_PLI, _WPLI, _DEBIASED_PLI2, _DEBIASED_WPLI2 off the diagonal).
+ *   d_out   for each requested measure in the order above three double [n_bins][C][C] arrays, diagonal NaN; a NaN d_u makes the
+ *           entry's sums NaN.
+ *   planes  of d_total; it must hold what the requested measures read: PLI and debiased PLI^2 SC_PLANE_SIGN_IM, wPLI
+ *           SC_PLANE_CSM | _ABS_IM, debiased wPLI^2 SC_PLANE_CSM | _ABS_IM | _IM_SQ (float records, or double with SC_RECORD_F64).
+ * SC_EINVAL (with sc_last_error) before any launch for: an empty or unknown mask, a bad `over`, a kept trial axis under
+ * over = trials, fewer than two units, a unit range outside the spectra, a workspace that is too small, a NULL argument, a
+ * missing plane, and a debiased measure whose delete-one sets hold fewer than two observations. */
+#define SC_JACKKNIFE_PHASE_PLI 0x1u
+#define SC_JACKKNIFE_PHASE_WPLI 0x2u
+#define SC_JACKKNIFE_PHASE_DEBIASED_PLI2 0x4u
+#define SC_JACKKNIFE_PHASE_DEBIASED_WPLI2 0x8u
+int sc_jackknife_phase_layout(const sc_spectra_desc* desc, uint32_t measures, int over, int64_t* n_bins, int64_t* n_units,
+                              int64_t* unit_size, int64_t* out_doubles);
+int64_t sc_jackknife_phase_workspace_bytes(const sc_spectra_desc* desc, uint32_t measures, int over, int64_t unit_begin,
+                                           int64_t unit_end);
+int sc_jackknife_phase_f32(const void* d_X /*float2*/, const sc_spectra_desc* desc, const void* d_total, uint32_t planes,
+                           uint32_t measures, int over, int64_t unit_begin, int64_t unit_end, int64_t n_units_total, double* d_out,
+                           void* d_workspace, int64_t workspace_bytes, void* stream);
+int sc_jackknife_phase_f64(const void* d_X /*double2*/, const sc_spectra_desc* desc, const void* d_total, uint32_t planes,
+                           uint32_t measures, int over, int64_t unit_begin, int64_t unit_end, int64_t n_units_total, double* d_out,
+                           void* d_workspace, int64_t workspace_bytes, void* stream);
+
+/* The total record of sc_jackknife_phase_* from the spectra themselves (jk_phase_totals_kernel): the sums A, B, Q, N over the units
+ * [unit_begin, unit_end) of THIS process, as a record of DOUBLES in the accumulator layout with the families `planes` (a non-empty
+ * set of SC_PLANE_CSM -- its real plane is 0 --, _ABS_IM, _IM_SQ, _SIGN_IM; hand it on with SC_RECORD_F64 set).  Each total is the
+ * fp64 sum of exactly the per-unit sums sc_jackknife_phase_* subtracts from it, whatever the engine: the float32 engine's own
+ * records sum thousands of observations in float32, an error in A that the debiased wPLI^2 of a pair with a wPLI near 0 multiplies
+ * by B / A (measured: its standard error 6.0e-6 off at 1000 trials), and they take sum Im s and sum |Im s|
+ * from different kernels, so that a pair whose Im s never changes sign is not exactly +-1.  Records of different processes add.
+ *   d_record     double [n_bins][planes][tiles][16][16] (n_bins and the elements per bin: sc_accum_layout), written whole
+ *   d_workspace  sc_jackknife_phase_totals_workspace_bytes (0 unless the units are split over several workgroups)
+ * SC_EINVAL before any launch as for sc_jackknife_phase_* (planes instead of measures). */
+int64_t sc_jackknife_phase_totals_workspace_bytes(const sc_spectra_desc* desc, uint32_t planes, int over, int64_t unit_begin,
+                                                  int64_t unit_end);
+int sc_jackknife_phase_totals_f32(const void* d_X /*float2*/, const sc_spectra_desc* desc, uint32_t planes, int over,
+                                  int64_t unit_begin, int64_t unit_end, double* d_record, void* d_workspace,
+                                  int64_t workspace_bytes, void* stream);
+int sc_jackknife_phase_totals_f64(const void* d_X /*double2*/, const sc_spectra_desc* desc, uint32_t planes, int over,
+                                  int64_t unit_begin, int64_t unit_end, double* d_record, void* d_workspace,
+                                  int64_t workspace_bytes, void* stream);
 
 /* ---- host-pointer side of the boundary: memory, copies, streams (sc_memory.hip, ABI v3) ---------------------
  * What the reference's CuPy backend does with `xp.asarray(time_series)` on the way in and `.get()` on the way out

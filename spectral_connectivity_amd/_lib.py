@@ -177,6 +177,17 @@ SYMBOLS = {
                                  c_void_p, c_void_p, c_int64, c_void_p]),
     "sc_jackknife_f64": (c_int, [c_void_p, POINTER(SpectraDesc), c_void_p, c_uint32, c_uint32, c_int, c_int64, c_int64, c_int64,
                                  c_void_p, c_void_p, c_int64, c_void_p]),
+    "sc_jackknife_phase_layout": (c_int, [POINTER(SpectraDesc), c_uint32, c_int, c_int64_p, c_int64_p, c_int64_p, c_int64_p]),
+    "sc_jackknife_phase_workspace_bytes": (c_int64, [POINTER(SpectraDesc), c_uint32, c_int, c_int64, c_int64]),
+    "sc_jackknife_phase_f32": (c_int, [c_void_p, POINTER(SpectraDesc), c_void_p, c_uint32, c_uint32, c_int, c_int64, c_int64, c_int64,
+                                       c_void_p, c_void_p, c_int64, c_void_p]),
+    "sc_jackknife_phase_f64": (c_int, [c_void_p, POINTER(SpectraDesc), c_void_p, c_uint32, c_uint32, c_int, c_int64, c_int64, c_int64,
+                                       c_void_p, c_void_p, c_int64, c_void_p]),
+    "sc_jackknife_phase_totals_workspace_bytes": (c_int64, [POINTER(SpectraDesc), c_uint32, c_int, c_int64, c_int64]),
+    "sc_jackknife_phase_totals_f32": (c_int, [c_void_p, POINTER(SpectraDesc), c_uint32, c_int, c_int64, c_int64, c_void_p, c_void_p,
+                                              c_int64, c_void_p]),
+    "sc_jackknife_phase_totals_f64": (c_int, [c_void_p, POINTER(SpectraDesc), c_uint32, c_int, c_int64, c_int64, c_void_p, c_void_p,
+                                              c_int64, c_void_p]),
     "sc_measure_f32": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_int, c_void_p, c_void_p]),
     # host-pointer side (sc_memory.hip)
     "sc_device_alloc": (c_int, [POINTER(c_void_p), c_size_t, c_void_p]),
@@ -402,13 +413,71 @@ def jackknife_request(measures, over, expectation_type, n_trials, n_observations
     return names, mask, JACKKNIFE_OVER[over], n_units
 
 
+# the phase-lag family (jk_phase_kernel, sc_jackknife_phase_*): a mask of its own, same tuple; all on the identity scale
+JACKKNIFE_PHASE_MEASURES = {
+    "phase_lag_index": (0x1, "identity", 2),
+    "weighted_phase_lag_index": (0x2, "identity", 2),
+    "debiased_squared_phase_lag_index": (0x4, "identity", 2),
+    "debiased_squared_weighted_phase_lag_index": (0x8, "identity", 2),
+}
+# planes of the total record each of them reads (= MEASURE_PLANES of the measure's own method)
+JACKKNIFE_PHASE_PLANES = {
+    "phase_lag_index": PLANE_SIGN_IM, "debiased_squared_phase_lag_index": PLANE_SIGN_IM,
+    "weighted_phase_lag_index": PLANE_CSM | PLANE_ABS_IM,
+    "debiased_squared_weighted_phase_lag_index": PLANE_CSM | PLANE_ABS_IM | PLANE_IM_SQ,
+}
+
+
+def jackknife_split(measures):
+    """(old names, phase-lag names) of a measure list of Connectivity.jackknife, as given; ValueError -- all seven names spelled
+    out -- for an empty list and an unknown name."""
+    if isinstance(measures, str):
+        measures = (measures,)
+    measures = tuple(measures)
+    valid = ", ".join(repr(k) for k in list(JACKKNIFE_MEASURES) + list(JACKKNIFE_PHASE_MEASURES))
+    if not measures:
+        raise ValueError(f"jackknife: measures is empty; choose from {valid}")
+    unknown = [m for m in measures if m not in JACKKNIFE_MEASURES and m not in JACKKNIFE_PHASE_MEASURES]
+    if unknown:
+        raise ValueError(f"jackknife: unknown measure {unknown[0]!r}; choose from {valid}")
+    return (tuple(m for m in measures if m in JACKKNIFE_MEASURES), tuple(m for m in measures if m in JACKKNIFE_PHASE_MEASURES))
+
+
+def jackknife_phase_request(measures, over, expectation_type, n_trials, n_observations):
+    """jackknife_request for the phase-lag family: (names in output order, sc_jackknife_phase_* mask, `over` code, n_units, planes
+    the total record must hold).  The same ValueErrors, and one more: the two debiased measures need at least two observations in
+    a delete-one set, n' = (n_units - 1) g >= 2 -- violated only by two units of one observation each."""
+    if isinstance(measures, str):
+        measures = (measures,)
+    measures = tuple(measures)
+    valid = ", ".join(repr(k) for k in JACKKNIFE_PHASE_MEASURES)
+    if not measures:
+        raise ValueError(f"jackknife: measures is empty; choose from {valid}")
+    unknown = [m for m in measures if m not in JACKKNIFE_PHASE_MEASURES]
+    if unknown:
+        raise ValueError(f"jackknife: unknown measure {unknown[0]!r}; choose from {valid}")
+    _, _, over_id, n_units = jackknife_request(("imaginary_coherence",), over, expectation_type, n_trials, n_observations)
+    names = [k for k in JACKKNIFE_PHASE_MEASURES if k in measures]
+    unit_size = int(n_observations) // n_units if over == "trials" else 1
+    if (n_units - 1) * unit_size < 2 and any(k.startswith("debiased") for k in names):
+        raise ValueError("jackknife: the debiased phase-lag measures need at least two observations in a delete-one set, "
+                         f"(n_units - 1) x observations per unit >= 2 (got {n_units} units of {unit_size})")
+    mask = planes = 0
+    for k in names:
+        mask |= JACKKNIFE_PHASE_MEASURES[k][0]
+        planes |= JACKKNIFE_PHASE_PLANES[k]
+    return names, mask, over_id, n_units, planes
+
+
 def jackknife_blocks(names, n_bins, n_signals):
-    """[(name, first double, doubles per array, array shape)] of the library's output for the measures ``names`` (output order):
-    every block is three arrays -- theta(S), sum d, sum d^2."""
+    """[(name, first double, doubles per array, array shape)] of the library's output for the measures ``names`` (output order;
+    all of JACKKNIFE_MEASURES or all of JACKKNIFE_PHASE_MEASURES: one call's): every block is three arrays -- theta(S), sum d,
+    sum d^2."""
     out, at = [], 0
     for k in names:
-        shape = (n_bins, n_signals) if JACKKNIFE_MEASURES[k][2] == 1 else (n_bins, n_signals, n_signals)
-        size = n_bins * n_signals ** JACKKNIFE_MEASURES[k][2]
+        rank = (JACKKNIFE_MEASURES.get(k) or JACKKNIFE_PHASE_MEASURES[k])[2]
+        shape = (n_bins, n_signals) if rank == 1 else (n_bins, n_signals, n_signals)
+        size = n_bins * n_signals ** rank
         out.append((k, at, size, shape))
         at += 3 * size
     return out, at

@@ -268,3 +268,43 @@ def jackknife(mem, spectra, expectation_type, total, planes, measures, over, n_u
     _lib.check(fn(mem.ptr(spectra.X), byref(d), mem.ptr(total), _planes(mem, total, planes), measures, over, lo, hi, n_units_total,
                   mem.ptr(out), _ptr(mem, ws), ws_bytes, mem.stream()), "sc_jackknife")
     return out, n_bins.value
+
+
+def jackknife_phase(mem, spectra, expectation_type, total, planes, measures, over, n_units_total, n_freq=None, unit_range=None):
+    """Delete-one jackknife sums of the phase-lag family (jk_phase_kernel of sc_jackknife.hip): as ``jackknife``, with the mask
+    ``measures`` of _lib.JACKKNIFE_PHASE_MEASURES and a total accumulator record ``total`` that holds the planes these measures
+    read (_lib.JACKKNIFE_PHASE_PLANES) among its ``planes``.  Returns (float64 device array laid out as _lib.jackknife_blocks
+    says, n_bins)."""
+    lib = _lib._handle()
+    d = spectra.desc(expectation_type, n_freq)
+    n_bins, n_units, unit_size, n_out = c_int64(), c_int64(), c_int64(), c_int64()
+    _lib.check(lib.sc_jackknife_phase_layout(byref(d), measures, over, byref(n_bins), byref(n_units), byref(unit_size), byref(n_out)),
+               "sc_jackknife_phase_layout")
+    lo, hi = (0, n_units.value) if unit_range is None else unit_range
+    ws_bytes = int(lib.sc_jackknife_phase_workspace_bytes(byref(d), measures, over, lo, hi))
+    ws = mem.empty((ws_bytes,), np.uint8) if ws_bytes else None
+    out = mem.empty((n_out.value,), np.float64)
+    fn = lib.sc_jackknife_phase_f64 if spectra.f64 else lib.sc_jackknife_phase_f32
+    _lib.check(fn(mem.ptr(spectra.X), byref(d), mem.ptr(total), _planes(mem, total, planes), measures, over, lo, hi, n_units_total,
+                  mem.ptr(out), _ptr(mem, ws), ws_bytes, mem.stream()), "sc_jackknife_phase")
+    return out, n_bins.value
+
+
+def jackknife_phase_totals(mem, spectra, expectation_type, planes, over, n_freq=None, unit_range=None):
+    """The total record of jackknife_phase from the spectra themselves (jk_phase_totals_kernel): float64 device array [n_bins,
+    elements per bin] in the accumulator layout with the families ``planes``, the sums over the units ``unit_range`` of these
+    spectra (default: all); the records of trial shards add.  Returns (record, n_observations of these spectra)."""
+    from . import _stage_abc
+    lib = _lib._handle()
+    d = spectra.desc(expectation_type, n_freq)
+    n_bins, per_bin, _, n_obs = _stage_abc.accum_layout(spectra, expectation_type, planes, n_freq)
+    n_units = c_int64()
+    _lib.check(lib.sc_jackknife_phase_layout(byref(d), 0x1, over, None, byref(n_units), None, None), "sc_jackknife_phase_layout")
+    lo, hi = (0, n_units.value) if unit_range is None else unit_range
+    ws_bytes = int(lib.sc_jackknife_phase_totals_workspace_bytes(byref(d), planes, over, lo, hi))
+    ws = mem.empty((ws_bytes,), np.uint8) if ws_bytes else None
+    record = mem.empty((n_bins, per_bin), np.float64)
+    fn = lib.sc_jackknife_phase_totals_f64 if spectra.f64 else lib.sc_jackknife_phase_totals_f32
+    _lib.check(fn(mem.ptr(spectra.X), byref(d), planes, over, lo, hi, mem.ptr(record), _ptr(mem, ws), ws_bytes, mem.stream()),
+               "sc_jackknife_phase_totals")
+    return record, n_obs

@@ -785,27 +785,74 @@ class Connectivity:
         arctanh of a number within a few ulp of 1 -- at least 17, inf, or NaN beyond 1 -- and its other two outputs carry no
         promise (the float64 reference rounds differently there); no other entry is affected.  ValueError for an
         unknown or empty measure list, a bad ``over`` and fewer than two units, before any device work.
+
+        The phase-lag family, on the identity scale and signed where the measure is signed: "phase_lag_index",
+        "weighted_phase_lag_index" (both antisymmetric), "debiased_squared_phase_lag_index" and
+        "debiased_squared_weighted_phase_lag_index" (symmetric; NaN where sum |Im s|^2 = sum (Im s)^2 exactly, as at the zero and
+        Nyquist bins of a real series) -- the jackknife of FieldTrip's ft_connectivity_wpli.  They come from a pass of their own
+        (jk_phase_kernel) against totals that one more pass sums from the same spectra in fp64 (kept for the next request);
+        ``estimate`` equals the method's value off the NaN diagonal to the engine's precision.  The two debiased measures need
+        two observations in a delete-one set (ValueError for two units of one observation).  The results are ordered: the three
+        measures above first, then these four.
         """
+        old, new = _lib.jackknife_split(measures)
+        # (every request is checked before any device work)
+        plan = _lib.jackknife_request(old, over, self.expectation_type, self._jackknife_trials(), self.n_observations) if old else None
+        phase_plan = (_lib.jackknife_phase_request(new, over, self.expectation_type, self._jackknife_trials(), self.n_observations)
+                      if new else None)
+        out = {}
+        if plan is not None:
+            out.update(self._jackknife_first_family(plan, over))
+        if phase_plan is not None:
+            out.update(self._jackknife_phase_family(phase_plan, over))
+        return out
+
+    def _jackknife_results(self, flat, n_bins, names, table, n_units, over):
+        """{name: JackknifeResult} from the library's flat output (_lib.jackknife_blocks) for the measures ``names`` of ``table``."""
         from .statistics import JackknifeResult, jackknife_finish
-        names, mask, over_id, n_units = _lib.jackknife_request(measures, over, self.expectation_type, self._jackknife_trials(),
-                                                               self.n_observations)
-        if n_units == 2 and self.n_observations == 2 and "coherence_magnitude" in names:
-            logger.warning("jackknife: with two delete units of one observation each a leave-one-out estimate is a single observation, "
-                           "whose coherence magnitude is identically 1: the coherence_magnitude results are inf, NaN or rounding noise")
-        flat, n_bins = self._jackknife_sums(mask, over_id, n_units)
         blocks, _ = _lib.jackknife_blocks(names, n_bins, self._shape5[4])
         out = {}
         for name, at, size, shape in blocks:
             theta, s1, s2 = (flat[at + k * size:at + (k + 1) * size].reshape(self._kept_shape() + (self._n_freq,) + shape[1:])
                              for k in range(3))
             est, corrected, se = jackknife_finish(theta, s1, s2, n_units)
-            out[name] = JackknifeResult(est, corrected, se, _lib.JACKKNIFE_MEASURES[name][1], n_units, over)
+            out[name] = JackknifeResult(est, corrected, se, table[name][1], n_units, over)
+        return out
+
+    def _jackknife_first_family(self, plan, over):
+        """Power, coherence magnitude and imaginary coherence: jk_kernel against the CSM record."""
+        names, mask, over_id, n_units = plan
+        if n_units == 2 and self.n_observations == 2 and "coherence_magnitude" in names:
+            logger.warning("jackknife: with two delete units of one observation each a leave-one-out estimate is a single observation, "
+                           "whose coherence magnitude is identically 1: the coherence_magnitude results are inf, NaN or rounding noise")
+        flat, n_bins = self._jackknife_sums(mask, over_id, n_units)
+        out = self._jackknife_results(flat, n_bins, names, _lib.JACKKNIFE_MEASURES, n_units, over)
         first = out[names[0]].estimate
         n_nan = int(np.isnan(first).sum())
         if names[0] != "power":
             n_nan -= first.size // first.shape[-1]          # (the diagonal is NaN by definition)
         if n_nan:
             logger.warning(f"jackknife: {n_nan} entries of {names[0]} are NaN (a channel without power in a bin)")
+        return out
+
+    def _jackknife_phase_family(self, plan, over):
+        """The phase-lag family: jk_phase_kernel against a record of totals with the planes its measures read."""
+        names, mask, over_id, n_units, planes = plan
+        flat, n_bins = self._jackknife_phase_sums(mask, planes, over_id, n_units)
+        out = self._jackknife_results(flat, n_bins, names, _lib.JACKKNIFE_PHASE_MEASURES, n_units, over)
+        nan = np.isnan(out[names[0]].estimate)
+        C = nan.shape[-1]
+        nan[..., np.arange(C), np.arange(C)] = False        # (the diagonal is NaN by definition)
+        if names[0] == "debiased_squared_weighted_phase_lag_index" and self._device().real_input:
+            # a real series has Im s = 0 in every observation at the zero bin and at the Nyquist bin of an even length: the
+            # denominator sum |Im s|^2 - sum (Im s)^2 is exactly 0 there and the measure NaN by its definition
+            nan[..., 0, :, :] = False
+            if self._shape5[3] % 2 == 0:
+                nan[..., -1, :, :] = False
+        n_nan = int(nan.sum())
+        if n_nan:
+            logger.warning(f"jackknife: {n_nan} entries of {names[0]} are NaN (coefficients that are not finite, or a pair whose "
+                           "sum |Im s|^2 equals its sum (Im s)^2)")
         return out
 
     def _jackknife_trials(self):
@@ -823,8 +870,30 @@ class Connectivity:
                                          n_freq=self._n_freq)
         return mem.download(self._jackknife_reduce(out, mask, n_bins)), n_bins
 
-    def _jackknife_reduce(self, out, mask, n_bins):
-        """Sum of the partial sums over the processes that hold the trials (nothing to add here)."""
+    def _jackknife_phase_sums(self, mask, planes, over_id, n_units):
+        """_jackknife_sums for the phase-lag family.  The spectra are asked for without a planes hint, as there.  The total is a
+        record of doubles with the families ``planes`` that the jackknife sums from the spectra itself
+        (_stage_d.jackknife_phase_totals: the fp64 sum of exactly the unit sums the kernel subtracts, on both engines), summed
+        over every rank's trials and cached like the measures' own records; a later request over the same units that needs no
+        other plane reads it again."""
+        from . import _stage_d
+        sp = self._device()
+        mem = self._memory(sp)
+        mine = [k for k in self._accum_cache if isinstance(k, tuple) and k[0] == "jackknife_phase" and k[2] == over_id]
+        have = next((k for k in mine if k[1] & planes == planes), None)
+        if have is None:
+            total, n_obs = _stage_d.jackknife_phase_totals(mem, sp, self.expectation_type, planes, over_id, n_freq=self._n_freq)
+            for old in [k for k in mine if k[1] & planes == k[1]]:
+                del self._accum_cache[old]             # a record the new one covers: its memory can go
+            have = ("jackknife_phase", planes, over_id)  # (the unit sums behind a total are those of this `over`)
+            self._accum_cache[have] = (self._reduce_over_ranks(total), n_obs)
+        out, n_bins = _stage_d.jackknife_phase(mem, sp, self.expectation_type, self._accum_cache[have][0], have[1], mask, over_id,
+                                               n_units, n_freq=self._n_freq)
+        return mem.download(self._jackknife_reduce(out, mask, n_bins, _lib.JACKKNIFE_PHASE_MEASURES)), n_bins
+
+    def _jackknife_reduce(self, out, mask, n_bins, table=None):
+        """Sum of the partial sums over the processes that hold the trials (nothing to add here).  ``table``: the measures the
+        mask ``mask`` is of (default _lib.JACKKNIFE_MEASURES)."""
         return out
 
     def conditional_spectral_granger_prediction(self):

@@ -1,4 +1,4 @@
-// sc_jackknife.hip -- delete-one jackknife of power, Fisher-z coherence and imaginary coherence (gfx950).
+// sc_jackknife.hip -- delete-one jackknife of power, Fisher-z coherence, imaginary coherence and the phase-lag family (gfx950).
 //
 // For a kept index and bin, delete units u = 1 .. n of g observations each: G_u = sum over the unit's observations of
 // x_i conj(x_j), S = sum_u G_u (the un-normalised CSM record the package accumulates anyway), S_(-u) = S - G_u.  Leaving a
@@ -14,6 +14,15 @@
 // bin's rows come from HBM once and from cache for the other pairs.  Where bins x tile pairs do not fill the chip the units are
 // split over gridDim.y workgroups that write partial sums to the workspace, added in split order by a second kernel: no
 // floating-point atomics anywhere, results are bit-identical from run to run.
+//
+// The phase-lag family (jk_phase_kernel, same geometry): per observation Im s = Im(x_i conj(x_j)) is formed once and summed per
+// unit as a_u = sum Im s, b_u = sum |Im s|, c_u = sum sign(Im s) (an integer) and q_u = sum (Im s)^2; the totals A, B, N, Q are the
+// planes SC_PLANE_CSM (im), _ABS_IM, _SIGN_IM and _IM_SQ of the accumulator record, and with n = n_units_total g observations
+//     PLI = N / n,  wPLI = (A / n) / w with w = B / n (1 where w < 2^-52),  debiased PLI^2 = (n PLI^2 - 1) / (n - 1),
+//     debiased wPLI^2 = (A^2 - Q) / (B^2 - Q) (NaN where the denominator is exactly 0)
+// on the identity scale; a delete-one value is the same formula on A - a_u, ... and n' = (n_units_total - 1) g.
+// jk_phase_totals_kernel sums such a record from the spectra (the fp64 sum of the very unit sums that are subtracted): what the
+// hosts hand in, because the float32 engine's own records are too coarse in A for the debiased wPLI^2 of a pair near 0.
 #include "sc_common.h"
 
 #include <math.h>
@@ -23,6 +32,9 @@ namespace {
 constexpr int JK_T = 32;        // channel tile edge of a workgroup (2 x 2 entries per thread)
 constexpr int JK_ROWS = 32;     // observation rows staged per barrier pair
 constexpr int JK_MAX_SPLITS = 256;
+constexpr int JK_MAX_BLOCKS = 4;  // measure blocks of one call (three of jk_kernel, four of jk_phase_kernel)
+constexpr uint32_t JK_PHASE_ALL = SC_JACKKNIFE_PHASE_PLI | SC_JACKKNIFE_PHASE_WPLI | SC_JACKKNIFE_PHASE_DEBIASED_PLI2 |
+                                  SC_JACKKNIFE_PHASE_DEBIASED_WPLI2;
 
 struct JkArgs {
     ScAxes a;
@@ -40,7 +52,8 @@ struct JkArgs {
     double* out;                 // split s writes at out + s * out_doubles
 };
 
-__device__ __forceinline__ int64_t jk_row_offset(const JkArgs& p, int64_t u, int q) {
+template <typename Args>
+__device__ __forceinline__ int64_t jk_row_offset(const Args& p, int64_t u, int q) {
     if (p.over == SC_JACKKNIFE_OVER_OBSERVATIONS) return sc_obs_offset(p.a, (int)u);
     const int w = q / p.q_tapers, k = q - w * p.q_tapers;
     return (int64_t)w * p.a.sW + u * p.a.sR + (int64_t)k * p.a.sK;
@@ -235,36 +248,348 @@ __global__ __launch_bounds__(256) void jk_kernel(const T2* __restrict__ X, JkArg
     }
 }
 
-// partial sums of the unit splits -> the output, in split order; theta(S) is the same in every split
-__global__ void jk_fold(const double* __restrict__ ws, int n_splits, JkArgs p, double* __restrict__ out) {
+// ---- the phase-lag family ------------------------------------------------------------------------------------------------------
+struct JkPhaseArgs {
+    ScAxes a;
+    ScRec total;
+    int NB16, n_tiles16;
+    int p_im, p_abs, p_sq, p_sign;   // plane index of sum Im s, sum |Im s|, sum (Im s)^2, sum sign(Im s) in a bin record; -1: absent
+    int64_t rec_stride;              // elements of one bin record
+    int n_freq, NT, n_tp;
+    int over, g, q_tapers;
+    int64_t unit_begin, unit_end, units_per_split;
+    double n_full, n_del;            // observations of the full estimate and of a delete-one estimate
+    uint32_t measures;
+    int64_t n_bins;
+    int64_t off[JK_MAX_BLOCKS];      // first double of each measure's block, -1: not requested
+    int64_t out_doubles;
+    double* out;                     // split s writes at out + s * out_doubles
+};
+
+// the four statistics from the sums (A, B, N, Q) of n observations; sc_measure.hip's formulas on the identity scale
+__device__ __forceinline__ double jk_pli(double N, double n) { return N / n; }
+__device__ __forceinline__ double jk_debiased_pli2(double pli, double n) { return (n * pli * pli - 1.0) / (n - 1.0); }
+__device__ __forceinline__ double jk_wpli(double A, double B, double n) {
+    double w = B / n;
+    if (w < 2.220446049250313e-16) w = 1.0;
+    return (A / n) / w;
+}
+__device__ __forceinline__ double jk_debiased_wpli2(double A, double B, double Q) {
+    const double den = B * B - Q;
+    return den == 0.0 ? __builtin_nan("") : (A * A - Q) / den;
+}
+
+template <typename T, typename T2>
+__global__ __launch_bounds__(256) void jk_phase_kernel(const T2* __restrict__ X, JkPhaseArgs p) {
+    __shared__ T2 rows[JK_ROWS][2 * JK_T];
+    __shared__ int64_t row_off[JK_ROWS];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int64_t wg = blockIdx.x;
+    const int tp = (int)(wg % p.n_tp);
+    const int64_t bin = wg / p.n_tp;
+    int ti = 0, rem = tp;
+    while (rem >= p.NT - ti) { rem -= p.NT - ti; ++ti; }
+    const int tj = ti + rem;
+    const int f = (int)(bin % p.n_freq), grp = (int)(bin / p.n_freq);
+    const T2* Xb = X + (int64_t)f * p.a.sF + sc_group_offset(p.a, grp);
+    const int C = p.a.C;
+    const ScRec rec = p.total + bin * p.rec_stride;
+    const bool want_pli = p.measures & SC_JACKKNIFE_PHASE_PLI, want_wpli = p.measures & SC_JACKKNIFE_PHASE_WPLI,
+               want_dpli = p.measures & SC_JACKKNIFE_PHASE_DEBIASED_PLI2, want_dwpli = p.measures & SC_JACKKNIFE_PHASE_DEBIASED_WPLI2;
+    const bool diag_thread = ti == tj && tx == ty;
+    const double nan = __builtin_nan("");
+    const int64_t plane = (int64_t)p.n_tiles16 * SC_TILE_ELEMS;
+
+    int ci[2], cj[2];
+    bool valid[2][2];
+    double tA[2][2], tB[2][2], tN[2][2], tQ[2][2];          // totals of the record
+    double th[4][2][2];                                     // the full estimates
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        ci[a] = ti * JK_T + ty + 16 * a;
+        cj[a] = tj * JK_T + tx + 16 * a;
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            valid[a][b] = ci[a] < cj[b] && cj[b] < C;
+            tA[a][b] = tB[a][b] = tN[a][b] = tQ[a][b] = 0.0;
+            if (valid[a][b]) {
+                const int i = ci[a], j = cj[b];
+                const int64_t off = (int64_t)sc_tile_index(i >> 4, j >> 4, p.NB16) * SC_TILE_ELEMS + (i & 15) * 16 + (j & 15);
+                if (p.p_im >= 0) tA[a][b] = rec[p.p_im * plane + off];
+                if (p.p_abs >= 0) tB[a][b] = rec[p.p_abs * plane + off];
+                if (p.p_sq >= 0) tQ[a][b] = rec[p.p_sq * plane + off];
+                if (p.p_sign >= 0) tN[a][b] = rec[p.p_sign * plane + off];
+            }
+            const double pli = jk_pli(tN[a][b], p.n_full);
+            th[0][a][b] = pli;
+            th[1][a][b] = jk_wpli(tA[a][b], tB[a][b], p.n_full);
+            th[2][a][b] = jk_debiased_pli2(pli, p.n_full);
+            th[3][a][b] = jk_debiased_wpli2(tA[a][b], tB[a][b], tQ[a][b]);
+        }
+
+    // The two sums are taken about the deviation of the first unit this workgroup walks, r (the shifted-data form), and moved back
+    // to the origin after the last unit: sum d = k r + sum (d - r), sum d^2 = r sum d + sum (d - r)^2 + r sum (d - r).  A pair
+    // whose units all have the same deviation (equal sign counts in every unit of a few) then gets sum d^2 = r sum d bit for
+    // bit, which is what the host's n m^2 is: a standard error of exactly 0, as in exact arithmetic.
+    double s1[4][2][2] = {}, s2[4][2][2] = {}, piv[4][2][2] = {};
+    int n_done = 0;
+    T ua[2][2] = {}, ub[2][2] = {}, uq[2][2] = {};
+    int uc[2][2] = {};
+
+    const int64_t u0 = p.unit_begin + (int64_t)blockIdx.y * p.units_per_split;
+    const int64_t u1 = u0 + p.units_per_split < p.unit_end ? u0 + p.units_per_split : p.unit_end;
+    const int n_rows = (int)((u1 - u0) * p.g);
+    int cnt = 0;
+    for (int r0 = 0; r0 < n_rows; r0 += JK_ROWS) {
+        const int nr = n_rows - r0 < JK_ROWS ? n_rows - r0 : JK_ROWS;
+        __syncthreads();
+        if (tid < nr) {
+            const int q = r0 + tid, du = q / p.g;
+            row_off[tid] = jk_row_offset(p, u0 + du, q - du * p.g);
+        }
+        __syncthreads();
+        for (int e = tid; e < nr * 2 * JK_T; e += 256) {
+            const int r = e >> 6, col = e & 63;
+            const int c = (col < JK_T ? ti : tj) * JK_T + (col & (JK_T - 1));
+            T2 v;
+            v.x = 0; v.y = 0;
+            if (c < C) v = Xb[row_off[r] + c];
+            rows[r][col] = v;
+        }
+        __syncthreads();
+        for (int r = 0; r < nr; ++r) {
+            T2 xi[2], xj[2];
+            xi[0] = rows[r][ty]; xi[1] = rows[r][ty + 16];
+            xj[0] = rows[r][JK_T + tx]; xj[1] = rows[r][JK_T + tx + 16];
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    const T im = xi[a].y * xj[b].x - xi[a].x * xj[b].y;
+                    ua[a][b] += im;
+                    ub[a][b] += im < 0 ? -im : im;
+                    uq[a][b] += im * im;
+                    uc[a][b] += (im > 0) - (im < 0);
+                }
+            if (++cnt == p.g) {
+                // the unit is complete: d_u = theta(sums without the unit, n') - theta(sums, n) of every requested measure, in fp64
+                cnt = 0;
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) {
+                        if (valid[a][b]) {
+                            if (want_pli || want_dpli) {
+                                const double pli = jk_pli(tN[a][b] - (double)uc[a][b], p.n_del);
+                                if (want_pli) {
+                                    const double d = pli - th[0][a][b];
+                                    if (n_done == 0) piv[0][a][b] = d;
+                                    const double e = d - piv[0][a][b];
+                                    s1[0][a][b] += e;
+                                    s2[0][a][b] += e * e;
+                                }
+                                if (want_dpli) {
+                                    const double d = jk_debiased_pli2(pli, p.n_del) - th[2][a][b];
+                                    if (n_done == 0) piv[2][a][b] = d;
+                                    const double e = d - piv[2][a][b];
+                                    s1[2][a][b] += e;
+                                    s2[2][a][b] += e * e;
+                                }
+                            }
+                            if (want_wpli || want_dwpli) {
+                                const double A = tA[a][b] - (double)ua[a][b], B = tB[a][b] - (double)ub[a][b];
+                                if (want_wpli) {
+                                    const double d = jk_wpli(A, B, p.n_del) - th[1][a][b];
+                                    if (n_done == 0) piv[1][a][b] = d;
+                                    const double e = d - piv[1][a][b];
+                                    s1[1][a][b] += e;
+                                    s2[1][a][b] += e * e;
+                                }
+                                if (want_dwpli) {
+                                    const double d = jk_debiased_wpli2(A, B, tQ[a][b] - (double)uq[a][b]) - th[3][a][b];
+                                    if (n_done == 0) piv[3][a][b] = d;
+                                    const double e = d - piv[3][a][b];
+                                    s1[3][a][b] += e;
+                                    s2[3][a][b] += e * e;
+                                }
+                            }
+                        }
+                        ua[a][b] = 0; ub[a][b] = 0; uq[a][b] = 0; uc[a][b] = 0;
+                    }
+                ++n_done;
+            }
+        }
+    }
+
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const double r = piv[m][a][b], t1 = s1[m][a][b], t2 = s2[m][a][b];
+                s1[m][a][b] = (double)n_done * r + t1;
+                s2[m][a][b] = r * s1[m][a][b] + (t2 + r * t1);
+            }
+
+    double* out = p.out + (int64_t)blockIdx.y * p.out_doubles;
+    const int64_t CC = (int64_t)C * C, plane2 = p.n_bins * CC;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        if (!(p.measures & (1u << m))) continue;
+        double* o = out + p.off[m] + bin * CC;
+        const double sgn = m < 2 ? -1.0 : 1.0;                // PLI and wPLI are antisymmetric, the debiased squares symmetric
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+                if (valid[a][b]) {
+                    const int64_t e = (int64_t)ci[a] * C + cj[b], mi = (int64_t)cj[b] * C + ci[a];
+                    o[e] = th[m][a][b]; o[mi] = sgn * th[m][a][b];
+                    o[plane2 + e] = s1[m][a][b]; o[plane2 + mi] = sgn * s1[m][a][b];
+                    o[2 * plane2 + e] = s2[m][a][b]; o[2 * plane2 + mi] = s2[m][a][b];
+                }
+        if (diag_thread) {
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+                if (ci[a] >= C) continue;
+                const int64_t e = (int64_t)ci[a] * C + ci[a];
+                o[e] = nan; o[plane2 + e] = nan; o[2 * plane2 + e] = nan;
+            }
+        }
+    }
+}
+
+// The totals of the phase-lag family from the spectra themselves: the same staging and the same per-unit sums as jk_phase_kernel
+// (a_u, b_u, q_u in T, c_u an integer), added over the units in fp64 and written as a record of doubles in the accumulator layout
+// (upper 16 x 16 tiles; planes CSM (re = 0, im), ABS_IM, IM_SQ, SIGN_IM as requested).  A total is then the sum of exactly the unit
+// sums jk_phase_kernel subtracts from it: sum Im s = +-sum |Im s| bit for bit where every observation has the same sign, and no
+// float32 summation error of thousands of observations in A, which the debiased wPLI^2 of a pair near 0 multiplies by B / A.
+template <typename T, typename T2>
+__global__ __launch_bounds__(256) void jk_phase_totals_kernel(const T2* __restrict__ X, JkPhaseArgs p) {
+    __shared__ T2 rows[JK_ROWS][2 * JK_T];
+    __shared__ int64_t row_off[JK_ROWS];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int64_t wg = blockIdx.x;
+    const int tp = (int)(wg % p.n_tp);
+    const int64_t bin = wg / p.n_tp;
+    int ti = 0, rem = tp;
+    while (rem >= p.NT - ti) { rem -= p.NT - ti; ++ti; }
+    const int tj = ti + rem;
+    const int f = (int)(bin % p.n_freq), grp = (int)(bin / p.n_freq);
+    const T2* Xb = X + (int64_t)f * p.a.sF + sc_group_offset(p.a, grp);
+    const int C = p.a.C;
+
+    double sA[2][2] = {}, sB[2][2] = {}, sQ[2][2] = {}, sN[2][2] = {};
+    T ua[2][2] = {}, ub[2][2] = {}, uq[2][2] = {};
+    int uc[2][2] = {};
+    const int64_t u0 = p.unit_begin + (int64_t)blockIdx.y * p.units_per_split;
+    const int64_t u1 = u0 + p.units_per_split < p.unit_end ? u0 + p.units_per_split : p.unit_end;
+    const int n_rows = (int)((u1 - u0) * p.g);
+    int cnt = 0;
+    for (int r0 = 0; r0 < n_rows; r0 += JK_ROWS) {
+        const int nr = n_rows - r0 < JK_ROWS ? n_rows - r0 : JK_ROWS;
+        __syncthreads();
+        if (tid < nr) {
+            const int q = r0 + tid, du = q / p.g;
+            row_off[tid] = jk_row_offset(p, u0 + du, q - du * p.g);
+        }
+        __syncthreads();
+        for (int e = tid; e < nr * 2 * JK_T; e += 256) {
+            const int r = e >> 6, col = e & 63;
+            const int c = (col < JK_T ? ti : tj) * JK_T + (col & (JK_T - 1));
+            T2 v;
+            v.x = 0; v.y = 0;
+            if (c < C) v = Xb[row_off[r] + c];
+            rows[r][col] = v;
+        }
+        __syncthreads();
+        for (int r = 0; r < nr; ++r) {
+            T2 xi[2], xj[2];
+            xi[0] = rows[r][ty]; xi[1] = rows[r][ty + 16];
+            xj[0] = rows[r][JK_T + tx]; xj[1] = rows[r][JK_T + tx + 16];
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    const T im = xi[a].y * xj[b].x - xi[a].x * xj[b].y;
+                    ua[a][b] += im;
+                    ub[a][b] += im < 0 ? -im : im;
+                    uq[a][b] += im * im;
+                    uc[a][b] += (im > 0) - (im < 0);
+                }
+            if (++cnt == p.g) {
+                cnt = 0;
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) {
+                        sA[a][b] += (double)ua[a][b]; sB[a][b] += (double)ub[a][b];
+                        sQ[a][b] += (double)uq[a][b]; sN[a][b] += (double)uc[a][b];
+                        ua[a][b] = 0; ub[a][b] = 0; uq[a][b] = 0; uc[a][b] = 0;
+                    }
+            }
+        }
+    }
+
+    double* rec = p.out + (int64_t)blockIdx.y * p.out_doubles + bin * p.rec_stride;
+    const int64_t plane = (int64_t)p.n_tiles16 * SC_TILE_ELEMS;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int i = ti * JK_T + ty + 16 * a, j = tj * JK_T + tx + 16 * b;
+            if (!(i < j && j < C)) continue;
+            const int64_t off = (int64_t)sc_tile_index(i >> 4, j >> 4, p.NB16) * SC_TILE_ELEMS + (i & 15) * 16 + (j & 15);
+            if (p.p_im >= 0) rec[p.p_im * plane + off] = sA[a][b];
+            if (p.p_abs >= 0) rec[p.p_abs * plane + off] = sB[a][b];
+            if (p.p_sq >= 0) rec[p.p_sq * plane + off] = sQ[a][b];
+            if (p.p_sign >= 0) rec[p.p_sign * plane + off] = sN[a][b];
+        }
+}
+
+// partial sums of the unit splits -> the output, in split order; theta(S) is the same in every split.  A block is three arrays
+// of `len` doubles from `off` on: theta(S), sum d, sum d^2.
+struct JkFold {
+    int n_blocks;
+    int64_t off[JK_MAX_BLOCKS], len[JK_MAX_BLOCKS];
+    int64_t out_doubles;
+};
+
+__global__ void jk_fold(const double* __restrict__ ws, int n_splits, JkFold f, double* __restrict__ out) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= p.out_doubles) return;
+    if (e >= f.out_doubles) return;
     bool is_theta = false;
 #pragma unroll
-    for (int m = 0; m < 3; ++m) {
-        if (p.off[m] < 0) continue;
-        const int64_t len = p.n_bins * (m == 0 ? (int64_t)p.a.C : (int64_t)p.a.C * p.a.C);
-        if (e >= p.off[m] && e < p.off[m] + len) is_theta = true;
-    }
+    for (int m = 0; m < JK_MAX_BLOCKS; ++m)
+        if (m < f.n_blocks && e >= f.off[m] && e < f.off[m] + f.len[m]) is_theta = true;
     double v = ws[e];
     if (!is_theta)
-        for (int s = 1; s < n_splits; ++s) v += ws[(int64_t)s * p.out_doubles + e];
+        for (int s = 1; s < n_splits; ++s) v += ws[(int64_t)s * f.out_doubles + e];
     out[e] = v;
 }
 
 struct JkPlan {
     ScAxes a;
-    int64_t n_bins, n_units, g, out_doubles, off[3];
+    int64_t n_bins, n_units, g, out_doubles, off[JK_MAX_BLOCKS];
     int NT, n_tp, q_tapers;
 };
 
-int jk_plan(const sc_spectra_desc* desc, uint32_t measures, int over, JkPlan* pl) {
+// phase: the masks and blocks of the phase-lag family (four C x C blocks) instead of power / coherence / imaginary coherence
+int jk_plan(const sc_spectra_desc* desc, uint32_t measures, int over, JkPlan* pl, bool phase = false) {
     SC_REQUIRE(desc, "NULL descriptor");
     if (sc_make_axes(desc, &pl->a) != SC_OK) return SC_EINVAL;
     const ScAxes& a = pl->a;
     SC_REQUIRE(a.F >= 1 && a.W >= 1 && a.R >= 1 && a.K >= 1 && a.C >= 1 && a.C <= 32768, "bad spectra sizes");
-    SC_REQUIRE(measures && !(measures & ~(SC_JACKKNIFE_POWER | SC_JACKKNIFE_COHERENCE_MAGNITUDE | SC_JACKKNIFE_IMAGINARY_COHERENCE)),
-               "measures: a non-empty mask of SC_JACKKNIFE_POWER, _COHERENCE_MAGNITUDE, _IMAGINARY_COHERENCE");
+    if (phase)
+        SC_REQUIRE(measures && !(measures & ~JK_PHASE_ALL),
+                   "measures: a non-empty mask of SC_JACKKNIFE_PHASE_PLI, _WPLI, _DEBIASED_PLI2, _DEBIASED_WPLI2");
+    else
+        SC_REQUIRE(measures && !(measures & ~(SC_JACKKNIFE_POWER | SC_JACKKNIFE_COHERENCE_MAGNITUDE | SC_JACKKNIFE_IMAGINARY_COHERENCE)),
+                   "measures: a non-empty mask of SC_JACKKNIFE_POWER, _COHERENCE_MAGNITUDE, _IMAGINARY_COHERENCE");
     SC_REQUIRE(over == SC_JACKKNIFE_OVER_TRIALS || over == SC_JACKKNIFE_OVER_OBSERVATIONS, "over: SC_JACKKNIFE_OVER_TRIALS or _OBSERVATIONS");
     if (over == SC_JACKKNIFE_OVER_TRIALS) {
         SC_REQUIRE(desc->reduce_trial, "a jackknife over trials needs an expectation that averages over trials");
@@ -281,15 +606,28 @@ int jk_plan(const sc_spectra_desc* desc, uint32_t measures, int over, JkPlan* pl
     pl->n_tp = pl->NT * (pl->NT + 1) / 2;
     SC_REQUIRE(pl->n_bins * pl->n_tp < (int64_t)1 << 31, "too many (bin, channel tile pair) workgroups for one launch");
     int64_t at = 0;
-    for (int m = 0; m < 3; ++m) {
+    for (int m = 0; m < JK_MAX_BLOCKS; ++m) {
         pl->off[m] = -1;
         if (measures & (1u << m)) {
             pl->off[m] = at;
-            at += 3 * pl->n_bins * (m == 0 ? (int64_t)a.C : (int64_t)a.C * a.C);
+            at += 3 * pl->n_bins * (m == 0 && !phase ? (int64_t)a.C : (int64_t)a.C * a.C);
         }
     }
     pl->out_doubles = at;
     return SC_OK;
+}
+
+// the blocks of a plan as jk_fold wants them
+JkFold jk_fold_blocks(const JkPlan& pl, bool phase) {
+    JkFold f = {};
+    for (int m = 0; m < JK_MAX_BLOCKS; ++m)
+        if (pl.off[m] >= 0) {
+            f.off[f.n_blocks] = pl.off[m];
+            f.len[f.n_blocks] = pl.n_bins * (m == 0 && !phase ? (int64_t)pl.a.C : (int64_t)pl.a.C * pl.a.C);
+            ++f.n_blocks;
+        }
+    f.out_doubles = pl.out_doubles;
+    return f;
 }
 
 // units per split and number of splits: only when bins x tile pairs leave compute units idle, and never fewer than 16 units each
@@ -343,7 +681,128 @@ int jk_run(const void* d_X, const sc_spectra_desc* desc, const void* d_total, ui
     SC_CHECK_HIP(hipGetLastError());
     if (n_splits > 1) {
         hipLaunchKernelGGL(jk_fold, dim3((unsigned)((pl.out_doubles + 255) / 256)), dim3(256), 0, st, (const double*)d_workspace,
-                           (int)n_splits, p, d_out);
+                           (int)n_splits, jk_fold_blocks(pl, false), d_out);
+        SC_CHECK_HIP(hipGetLastError());
+    }
+    return SC_OK;
+}
+
+// planes of the total record a mask of phase-lag measures reads
+uint32_t jk_phase_planes(uint32_t measures) {
+    uint32_t need = 0;
+    if (measures & (SC_JACKKNIFE_PHASE_PLI | SC_JACKKNIFE_PHASE_DEBIASED_PLI2)) need |= SC_PLANE_SIGN_IM;
+    if (measures & SC_JACKKNIFE_PHASE_WPLI) need |= SC_PLANE_CSM | SC_PLANE_ABS_IM;
+    if (measures & SC_JACKKNIFE_PHASE_DEBIASED_WPLI2) need |= SC_PLANE_CSM | SC_PLANE_ABS_IM | SC_PLANE_IM_SQ;
+    return need;
+}
+
+template <typename T, typename T2>
+int jk_phase_run(const void* d_X, const sc_spectra_desc* desc, const void* d_total, uint32_t planes, uint32_t measures, int over,
+                 int64_t unit_begin, int64_t unit_end, int64_t n_units_total, double* d_out, void* d_workspace,
+                 int64_t workspace_bytes, void* stream) {
+    ScTimed timed_("jackknife_phase", stream);
+    JkPlan pl;
+    int rc = jk_plan(desc, measures, over, &pl, true);
+    if (rc != SC_OK) return rc;
+    SC_REQUIRE(d_X && d_total && d_out, "NULL argument");
+    const uint32_t need = jk_phase_planes(measures);
+    SC_REQUIRE((planes & need) == need,
+               "the total record lacks a plane of a requested measure (PLI, debiased PLI^2: SC_PLANE_SIGN_IM; wPLI: SC_PLANE_CSM | "
+               "_ABS_IM; debiased wPLI^2: SC_PLANE_CSM | _ABS_IM | _IM_SQ)");
+    SC_REQUIRE(0 <= unit_begin && unit_begin < unit_end && unit_end <= pl.n_units, "unit range outside the spectra's units");
+    SC_REQUIRE(n_units_total >= 2 && n_units_total >= unit_end - unit_begin, "a jackknife needs at least two units");
+    if (measures & (SC_JACKKNIFE_PHASE_DEBIASED_PLI2 | SC_JACKKNIFE_PHASE_DEBIASED_WPLI2))
+        SC_REQUIRE((n_units_total - 1) * pl.g >= 2, "a debiased estimate needs at least two observations in a delete-one set");
+    int64_t per, n_splits;
+    jk_splits(pl, unit_end - unit_begin, &per, &n_splits);
+    SC_REQUIRE(per * pl.g < (int64_t)1 << 31, "too many observation rows per workgroup");
+    if (n_splits > 1)
+        SC_REQUIRE(d_workspace && workspace_bytes >= n_splits * pl.out_doubles * (int64_t)sizeof(double), "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    JkPhaseArgs p = {};
+    p.a = pl.a;
+    p.total = sc_rec(d_total, planes);
+    p.NB16 = sc_n_blocks(pl.a.C);
+    p.n_tiles16 = sc_n_tiles(p.NB16);
+    p.p_im = (need & SC_PLANE_CSM) ? sc_plane_offset(planes, SC_PLANE_CSM) + 1 : -1;
+    p.p_abs = (need & SC_PLANE_ABS_IM) ? sc_plane_offset(planes, SC_PLANE_ABS_IM) : -1;
+    p.p_sq = (need & SC_PLANE_IM_SQ) ? sc_plane_offset(planes, SC_PLANE_IM_SQ) : -1;
+    p.p_sign = (need & SC_PLANE_SIGN_IM) ? sc_plane_offset(planes, SC_PLANE_SIGN_IM) : -1;
+    p.rec_stride = (int64_t)sc_plane_count(planes) * p.n_tiles16 * SC_TILE_ELEMS;
+    p.n_freq = pl.a.F; p.NT = pl.NT; p.n_tp = pl.n_tp;
+    p.over = over; p.g = (int)pl.g; p.q_tapers = pl.q_tapers;
+    p.unit_begin = unit_begin; p.unit_end = unit_end; p.units_per_split = per;
+    p.n_full = (double)n_units_total * (double)pl.g;
+    p.n_del = (double)(n_units_total - 1) * (double)pl.g;
+    p.measures = measures;
+    p.n_bins = pl.n_bins;
+    for (int m = 0; m < JK_MAX_BLOCKS; ++m) p.off[m] = pl.off[m];
+    p.out_doubles = pl.out_doubles;
+    p.out = n_splits > 1 ? (double*)d_workspace : d_out;
+    const dim3 grid((unsigned)(pl.n_bins * pl.n_tp), (unsigned)n_splits);
+    hipLaunchKernelGGL((jk_phase_kernel<T, T2>), grid, dim3(256), 0, st, (const T2*)d_X, p);
+    SC_CHECK_HIP(hipGetLastError());
+    if (n_splits > 1) {
+        hipLaunchKernelGGL(jk_fold, dim3((unsigned)((pl.out_doubles + 255) / 256)), dim3(256), 0, st, (const double*)d_workspace,
+                           (int)n_splits, jk_fold_blocks(pl, true), d_out);
+        SC_CHECK_HIP(hipGetLastError());
+    }
+    return SC_OK;
+}
+
+constexpr uint32_t JK_PHASE_PLANES_ALL = SC_PLANE_CSM | SC_PLANE_ABS_IM | SC_PLANE_IM_SQ | SC_PLANE_SIGN_IM;
+
+// plan of a totals pass: the units and splits of jk_plan / jk_splits, no measure blocks
+int jk_totals_plan(const sc_spectra_desc* desc, uint32_t planes, int over, JkPlan* pl) {
+    const int rc = jk_plan(desc, SC_JACKKNIFE_PHASE_PLI, over, pl, true);
+    if (rc != SC_OK) return rc;
+    planes &= ~SC_RECORD_F64;
+    SC_REQUIRE(planes && !(planes & ~JK_PHASE_PLANES_ALL), "planes: a non-empty set of SC_PLANE_CSM, _ABS_IM, _IM_SQ, _SIGN_IM");
+    pl->out_doubles = pl->n_bins * (int64_t)sc_plane_count(planes) * sc_n_tiles(sc_n_blocks(pl->a.C)) * SC_TILE_ELEMS;
+    return SC_OK;
+}
+
+template <typename T, typename T2>
+int jk_phase_totals_run(const void* d_X, const sc_spectra_desc* desc, uint32_t planes, int over, int64_t unit_begin,
+                        int64_t unit_end, double* d_record, void* d_workspace, int64_t workspace_bytes, void* stream) {
+    ScTimed timed_("jackknife_phase_totals", stream);
+    JkPlan pl;
+    int rc = jk_totals_plan(desc, planes, over, &pl);
+    if (rc != SC_OK) return rc;
+    planes &= ~SC_RECORD_F64;
+    SC_REQUIRE(d_X && d_record, "NULL argument");
+    SC_REQUIRE(0 <= unit_begin && unit_begin < unit_end && unit_end <= pl.n_units, "unit range outside the spectra's units");
+    int64_t per, n_splits;
+    jk_splits(pl, unit_end - unit_begin, &per, &n_splits);
+    SC_REQUIRE(per * pl.g < (int64_t)1 << 31, "too many observation rows per workgroup");
+    const int64_t rec_bytes = pl.out_doubles * (int64_t)sizeof(double);
+    if (n_splits > 1) SC_REQUIRE(d_workspace && workspace_bytes >= n_splits * rec_bytes, "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    JkPhaseArgs p = {};
+    p.a = pl.a;
+    p.NB16 = sc_n_blocks(pl.a.C);
+    p.n_tiles16 = sc_n_tiles(p.NB16);
+    p.p_im = (planes & SC_PLANE_CSM) ? sc_plane_offset(planes, SC_PLANE_CSM) + 1 : -1;
+    p.p_abs = (planes & SC_PLANE_ABS_IM) ? sc_plane_offset(planes, SC_PLANE_ABS_IM) : -1;
+    p.p_sq = (planes & SC_PLANE_IM_SQ) ? sc_plane_offset(planes, SC_PLANE_IM_SQ) : -1;
+    p.p_sign = (planes & SC_PLANE_SIGN_IM) ? sc_plane_offset(planes, SC_PLANE_SIGN_IM) : -1;
+    p.rec_stride = (int64_t)sc_plane_count(planes) * p.n_tiles16 * SC_TILE_ELEMS;
+    p.n_freq = pl.a.F; p.NT = pl.NT; p.n_tp = pl.n_tp;
+    p.over = over; p.g = (int)pl.g; p.q_tapers = pl.q_tapers;
+    p.unit_begin = unit_begin; p.unit_end = unit_end; p.units_per_split = per;
+    p.n_bins = pl.n_bins;
+    p.out_doubles = pl.out_doubles;
+    p.out = n_splits > 1 ? (double*)d_workspace : d_record;
+    // the entries no thread owns (the real plane, the diagonal and what lies below it in a diagonal tile, tile padding) are 0
+    SC_CHECK_HIP(hipMemsetAsync(p.out, 0, (size_t)(n_splits * rec_bytes), st));
+    const dim3 grid((unsigned)(pl.n_bins * pl.n_tp), (unsigned)n_splits);
+    hipLaunchKernelGGL((jk_phase_totals_kernel<T, T2>), grid, dim3(256), 0, st, (const T2*)d_X, p);
+    SC_CHECK_HIP(hipGetLastError());
+    if (n_splits > 1) {
+        JkFold fold = {};
+        fold.out_doubles = pl.out_doubles;              // (no theta blocks: every double is a sum over the splits)
+        hipLaunchKernelGGL(jk_fold, dim3((unsigned)((pl.out_doubles + 255) / 256)), dim3(256), 0, st, (const double*)d_workspace,
+                           (int)n_splits, fold, d_record);
         SC_CHECK_HIP(hipGetLastError());
     }
     return SC_OK;
@@ -384,4 +843,62 @@ extern "C" int sc_jackknife_f64(const void* d_X, const sc_spectra_desc* desc, co
                                 double* d_out, void* d_workspace, int64_t workspace_bytes, void* stream) {
     return jk_run<double, double2>(d_X, desc, d_total, planes, measures, over, unit_begin, unit_end, n_units_total, d_out,
                                    d_workspace, workspace_bytes, stream);
+}
+
+extern "C" int sc_jackknife_phase_layout(const sc_spectra_desc* desc, uint32_t measures, int over, int64_t* n_bins,
+                                         int64_t* n_units, int64_t* unit_size, int64_t* out_doubles) {
+    JkPlan pl;
+    const int rc = jk_plan(desc, measures, over, &pl, true);
+    if (rc != SC_OK) return rc;
+    if (n_bins) *n_bins = pl.n_bins;
+    if (n_units) *n_units = pl.n_units;
+    if (unit_size) *unit_size = pl.g;
+    if (out_doubles) *out_doubles = pl.out_doubles;
+    return SC_OK;
+}
+
+extern "C" int64_t sc_jackknife_phase_workspace_bytes(const sc_spectra_desc* desc, uint32_t measures, int over,
+                                                      int64_t unit_begin, int64_t unit_end) {
+    JkPlan pl;
+    if (jk_plan(desc, measures, over, &pl, true) != SC_OK || unit_end <= unit_begin) return 0;
+    int64_t per, n_splits;
+    jk_splits(pl, unit_end - unit_begin, &per, &n_splits);
+    return n_splits > 1 ? n_splits * pl.out_doubles * (int64_t)sizeof(double) : 0;
+}
+
+extern "C" int sc_jackknife_phase_f32(const void* d_X, const sc_spectra_desc* desc, const void* d_total, uint32_t planes,
+                                      uint32_t measures, int over, int64_t unit_begin, int64_t unit_end, int64_t n_units_total,
+                                      double* d_out, void* d_workspace, int64_t workspace_bytes, void* stream) {
+    return jk_phase_run<float, float2>(d_X, desc, d_total, planes, measures, over, unit_begin, unit_end, n_units_total, d_out,
+                                       d_workspace, workspace_bytes, stream);
+}
+
+extern "C" int sc_jackknife_phase_f64(const void* d_X, const sc_spectra_desc* desc, const void* d_total, uint32_t planes,
+                                      uint32_t measures, int over, int64_t unit_begin, int64_t unit_end, int64_t n_units_total,
+                                      double* d_out, void* d_workspace, int64_t workspace_bytes, void* stream) {
+    return jk_phase_run<double, double2>(d_X, desc, d_total, planes, measures, over, unit_begin, unit_end, n_units_total, d_out,
+                                         d_workspace, workspace_bytes, stream);
+}
+
+extern "C" int64_t sc_jackknife_phase_totals_workspace_bytes(const sc_spectra_desc* desc, uint32_t planes, int over,
+                                                             int64_t unit_begin, int64_t unit_end) {
+    JkPlan pl;
+    if (jk_totals_plan(desc, planes, over, &pl) != SC_OK || unit_end <= unit_begin) return 0;
+    int64_t per, n_splits;
+    jk_splits(pl, unit_end - unit_begin, &per, &n_splits);
+    return n_splits > 1 ? n_splits * pl.out_doubles * (int64_t)sizeof(double) : 0;
+}
+
+extern "C" int sc_jackknife_phase_totals_f32(const void* d_X, const sc_spectra_desc* desc, uint32_t planes, int over,
+                                             int64_t unit_begin, int64_t unit_end, double* d_record, void* d_workspace,
+                                             int64_t workspace_bytes, void* stream) {
+    return jk_phase_totals_run<float, float2>(d_X, desc, planes, over, unit_begin, unit_end, d_record, d_workspace,
+                                              workspace_bytes, stream);
+}
+
+extern "C" int sc_jackknife_phase_totals_f64(const void* d_X, const sc_spectra_desc* desc, uint32_t planes, int over,
+                                             int64_t unit_begin, int64_t unit_end, double* d_record, void* d_workspace,
+                                             int64_t workspace_bytes, void* stream) {
+    return jk_phase_totals_run<double, double2>(d_X, desc, planes, over, unit_begin, unit_end, d_record, d_workspace,
+                                                workspace_bytes, stream);
 }

@@ -511,6 +511,18 @@ def jackknife(spectra, expectation_type, total, planes, measures, over, n_units_
                               n_units_total, n_freq, unit_range)
 
 
+def jackknife_phase(spectra, expectation_type, total, planes, measures, over, n_units_total, n_freq=None, unit_range=None):
+    """Delete-one jackknife sums of the phase-lag family (jk_phase_kernel of sc_jackknife.hip) against the total accumulator record
+    ``total`` with the families ``planes`` (partial records are folded first): _stage_d.jackknife_phase."""
+    return _stage_d.jackknife_phase(TorchMemory(spectra.device), spectra, expectation_type, fold_parts(total), planes, measures,
+                                    over, n_units_total, n_freq, unit_range)
+
+
+def jackknife_phase_totals(spectra, expectation_type, planes, over, n_freq=None, unit_range=None):
+    """The float64 total record of jackknife_phase from the spectra themselves: _stage_d.jackknife_phase_totals."""
+    return _stage_d.jackknife_phase_totals(TorchMemory(spectra.device), spectra, expectation_type, planes, over, n_freq, unit_range)
+
+
 class GraphedMeasures:
     """Stage A, stage B and the epilogue of ONE fixed request, captured once in a hipGraph and replayed per time series.
 

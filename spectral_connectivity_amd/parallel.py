@@ -552,13 +552,14 @@ class ShardedConnectivity(_connectivity_base()):
     def _jackknife_trials(self):
         return self._n_trials_total
 
-    def _jackknife_reduce(self, out, mask, n_bins):
-        """Every rank walked ITS units against the total record: one sum over ranks of the two partial sums of every measure
-        (theta(S) is the same on every rank and stays as it is)."""
+    def _jackknife_reduce(self, out, mask, n_bins, table=None):
+        """Every rank walked ITS units against the total record: one sum over ranks of the two partial sums of every measure of
+        the call (theta(S) is the same on every rank and stays as it is).  ``table``: _lib.JACKKNIFE_MEASURES (default) or
+        _lib.JACKKNIFE_PHASE_MEASURES, whichever the mask is of."""
         from . import _lib
         if _no_exchange(self._group):
             return out
-        names = [k for k, v in _lib.JACKKNIFE_MEASURES.items() if mask & v[0]]
+        names = [k for k, v in (table or _lib.JACKKNIFE_MEASURES).items() if mask & v[0]]
         blocks, _ = _lib.jackknife_blocks(names, n_bins, self._shape5[4])
         sums = torch.cat([out[at + size:at + 3 * size] for _, at, size, _ in blocks])
         all_reduce_sum_(sums, self._group)

@@ -115,7 +115,7 @@ def power_fisher_z_transform(spectrum1, n_obs1, spectrum2=0, n_obs2=0):
 # ---- delete-one jackknife (Connectivity.jackknife; Thomson & Chave 1991) -----------------------------------------------------
 JackknifeResult = namedtuple("JackknifeResult", ["estimate", "bias_corrected", "standard_error", "transform", "n_units", "over"])
 JackknifeResult.__doc__ = """One measure of Connectivity.jackknife, on its variance-stabilising scale (``transform``: "log" for
-power, "fisher_z" = arctanh for the coherence magnitude, "identity" for the signed imaginary coherence): ``estimate`` = theta(S),
+power, "fisher_z" = arctanh for the coherence magnitude, "identity" for the signed imaginary coherence and the phase-lag family): ``estimate`` = theta(S),
 ``bias_corrected`` = theta(S) - (n - 1) mean_u d_u and ``standard_error`` = sqrt((n - 1) / n sum_u (d_u - mean d)^2) with
 d_u = theta(S without unit u) - theta(S); float64 arrays shaped like the measure's own output.  ``n_units`` = n delete units,
 ``over`` = "trials" or "observations"."""
@@ -145,3 +145,21 @@ def jackknife_confidence_intervals(result, ci=0.95):
     half = t * np.asarray(result.standard_error)
     centre = np.asarray(result.bias_corrected)
     return back(centre - half), back(centre + half)
+
+
+def jackknife_difference(result_a, result_b):
+    """(z, p) of the difference of two JackknifeResults of the same measure -- two conditions, each with its own jackknife -- on
+    their shared transform scale: z = (a.bias_corrected - b.bias_corrected) / sqrt(a.standard_error^2 + b.standard_error^2), p the
+    two-sided Student-t probability of |z| at a.n_units + b.n_units - 2 degrees of freedom.  ValueError for different transforms
+    or shapes; NaN in gives NaN out."""
+    if result_a.transform != result_b.transform:
+        raise ValueError(f"jackknife_difference: the results are on different scales ({result_a.transform!r} and "
+                         f"{result_b.transform!r})")
+    a, b = np.asarray(result_a.bias_corrected, dtype=float), np.asarray(result_b.bias_corrected, dtype=float)
+    if a.shape != b.shape:
+        raise ValueError(f"jackknife_difference: the results have different shapes ({a.shape} and {b.shape})")
+    se = np.sqrt(np.asarray(result_a.standard_error, dtype=float) ** 2 + np.asarray(result_b.standard_error, dtype=float) ** 2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        z = (a - b) / se
+    p = 2.0 * scipy.stats.t.sf(np.abs(z), result_a.n_units + result_b.n_units - 2)
+    return z, p
