@@ -378,19 +378,24 @@ JACKKNIFE_MEASURES = {
 JACKKNIFE_OVER = {"trials": 0, "observations": 1}
 
 
+def _jackknife_names(measures, *tables):
+    """The measure list ``measures`` (a name or an iterable of names) as a tuple; ValueError -- with the names of ``tables``
+    spelled out -- for an empty list and a name none of the tables has."""
+    measures = (measures,) if isinstance(measures, str) else tuple(measures)
+    valid = ", ".join(repr(k) for table in tables for k in table)
+    if not measures:
+        raise ValueError(f"jackknife: measures is empty; choose from {valid}")
+    unknown = [m for m in measures if not any(m in table for table in tables)]
+    if unknown:
+        raise ValueError(f"jackknife: unknown measure {unknown[0]!r}; choose from {valid}")
+    return measures
+
+
 def jackknife_request(measures, over, expectation_type, n_trials, n_observations):
     """(names in output order, measures mask, `over` code, n_units) of Connectivity.jackknife; ValueError -- with the valid choices
     spelled out -- for an empty or unknown measure list, a bad ``over``, an expectation that keeps the trial axis with
     over="trials", and fewer than two delete units.  ``n_trials`` / ``n_observations``: of the whole job."""
-    if isinstance(measures, str):
-        measures = (measures,)
-    measures = tuple(measures)
-    valid = ", ".join(repr(k) for k in JACKKNIFE_MEASURES)
-    if not measures:
-        raise ValueError(f"jackknife: measures is empty; choose from {valid}")
-    unknown = [m for m in measures if m not in JACKKNIFE_MEASURES]
-    if unknown:
-        raise ValueError(f"jackknife: unknown measure {unknown[0]!r}; choose from {valid}")
+    measures = _jackknife_names(measures, JACKKNIFE_MEASURES)
     if over not in JACKKNIFE_OVER:
         raise ValueError(f"jackknife: over must be 'trials' or 'observations' (got {over!r})")
     if over == "trials":
@@ -431,15 +436,7 @@ JACKKNIFE_PHASE_PLANES = {
 def jackknife_split(measures):
     """(old names, phase-lag names) of a measure list of Connectivity.jackknife, as given; ValueError -- all seven names spelled
     out -- for an empty list and an unknown name."""
-    if isinstance(measures, str):
-        measures = (measures,)
-    measures = tuple(measures)
-    valid = ", ".join(repr(k) for k in list(JACKKNIFE_MEASURES) + list(JACKKNIFE_PHASE_MEASURES))
-    if not measures:
-        raise ValueError(f"jackknife: measures is empty; choose from {valid}")
-    unknown = [m for m in measures if m not in JACKKNIFE_MEASURES and m not in JACKKNIFE_PHASE_MEASURES]
-    if unknown:
-        raise ValueError(f"jackknife: unknown measure {unknown[0]!r}; choose from {valid}")
+    measures = _jackknife_names(measures, JACKKNIFE_MEASURES, JACKKNIFE_PHASE_MEASURES)
     return (tuple(m for m in measures if m in JACKKNIFE_MEASURES), tuple(m for m in measures if m in JACKKNIFE_PHASE_MEASURES))
 
 
@@ -447,15 +444,7 @@ def jackknife_phase_request(measures, over, expectation_type, n_trials, n_observ
     """jackknife_request for the phase-lag family: (names in output order, sc_jackknife_phase_* mask, `over` code, n_units, planes
     the total record must hold).  The same ValueErrors, and one more: the two debiased measures need at least two observations in
     a delete-one set, n' = (n_units - 1) g >= 2 -- violated only by two units of one observation each."""
-    if isinstance(measures, str):
-        measures = (measures,)
-    measures = tuple(measures)
-    valid = ", ".join(repr(k) for k in JACKKNIFE_PHASE_MEASURES)
-    if not measures:
-        raise ValueError(f"jackknife: measures is empty; choose from {valid}")
-    unknown = [m for m in measures if m not in JACKKNIFE_PHASE_MEASURES]
-    if unknown:
-        raise ValueError(f"jackknife: unknown measure {unknown[0]!r}; choose from {valid}")
+    measures = _jackknife_names(measures, JACKKNIFE_PHASE_MEASURES)
     _, _, over_id, n_units = jackknife_request(("imaginary_coherence",), over, expectation_type, n_trials, n_observations)
     names = [k for k in JACKKNIFE_PHASE_MEASURES if k in measures]
     unit_size = int(n_observations) // n_units if over == "trials" else 1

@@ -249,25 +249,37 @@ def partial_coherence(mem, accum, n_signals, planes, n_obs, want):
     return out, mem.read_int(fail)
 
 
+def _jackknife_workspace(mem, workspace_bytes, d, mask, over, n_units, unit_range):
+    """(first unit, end unit, workspace or None, its bytes) of a jackknife call over ``unit_range`` (None: all ``n_units`` units of
+    the spectra); ``workspace_bytes``: the entry-point family's sc_*_workspace_bytes, ``mask``: what it takes after the descriptor."""
+    lo, hi = (0, n_units) if unit_range is None else unit_range
+    ws_bytes = int(workspace_bytes(byref(d), mask, over, lo, hi))
+    return lo, hi, (mem.empty((ws_bytes,), np.uint8) if ws_bytes else None), ws_bytes
+
+
+def _jackknife(mem, prefix, spectra, expectation_type, total, planes, measures, over, n_units_total, n_freq, unit_range):
+    """jackknife / jackknife_phase: layout, unit range, workspace, output and the call of ``prefix`` + _f32 / _f64."""
+    lib = _lib._handle()
+    d = spectra.desc(expectation_type, n_freq)
+    n_bins, n_units, unit_size, n_out = c_int64(), c_int64(), c_int64(), c_int64()
+    _lib.check(getattr(lib, prefix + "_layout")(byref(d), measures, over, byref(n_bins), byref(n_units), byref(unit_size),
+                                                byref(n_out)), prefix + "_layout")
+    lo, hi, ws, ws_bytes = _jackknife_workspace(mem, getattr(lib, prefix + "_workspace_bytes"), d, measures, over, n_units.value,
+                                                unit_range)
+    out = mem.empty((n_out.value,), np.float64)
+    fn = getattr(lib, prefix + ("_f64" if spectra.f64 else "_f32"))
+    _lib.check(fn(mem.ptr(spectra.X), byref(d), mem.ptr(total), _planes(mem, total, planes), measures, over, lo, hi, n_units_total,
+                  mem.ptr(out), _ptr(mem, ws), ws_bytes, mem.stream()), prefix)
+    return out, n_bins.value
+
+
 def jackknife(mem, spectra, expectation_type, total, planes, measures, over, n_units_total, n_freq=None, unit_range=None):
     """Delete-one jackknife sums (sc_jackknife.hip): ONE pass over the complex64 / complex128 spectra (``spectra.X``, described by
     ``spectra.desc``) for every measure of the mask ``measures`` (_lib.JACKKNIFE_MEASURES) against the total CSM record ``total``
     (any rank's sum).  ``over``: _lib.JACKKNIFE_OVER; ``n_units_total``: delete units of the whole job; ``unit_range``: the units
     of these spectra to walk (default: all of them).  Returns (float64 device array laid out as _lib.jackknife_blocks says,
     n_bins)."""
-    lib = _lib._handle()
-    d = spectra.desc(expectation_type, n_freq)
-    n_bins, n_units, unit_size, n_out = c_int64(), c_int64(), c_int64(), c_int64()
-    _lib.check(lib.sc_jackknife_layout(byref(d), measures, over, byref(n_bins), byref(n_units), byref(unit_size), byref(n_out)),
-               "sc_jackknife_layout")
-    lo, hi = (0, n_units.value) if unit_range is None else unit_range
-    ws_bytes = int(lib.sc_jackknife_workspace_bytes(byref(d), measures, over, lo, hi))
-    ws = mem.empty((ws_bytes,), np.uint8) if ws_bytes else None
-    out = mem.empty((n_out.value,), np.float64)
-    fn = lib.sc_jackknife_f64 if spectra.f64 else lib.sc_jackknife_f32
-    _lib.check(fn(mem.ptr(spectra.X), byref(d), mem.ptr(total), _planes(mem, total, planes), measures, over, lo, hi, n_units_total,
-                  mem.ptr(out), _ptr(mem, ws), ws_bytes, mem.stream()), "sc_jackknife")
-    return out, n_bins.value
+    return _jackknife(mem, "sc_jackknife", spectra, expectation_type, total, planes, measures, over, n_units_total, n_freq, unit_range)
 
 
 def jackknife_phase(mem, spectra, expectation_type, total, planes, measures, over, n_units_total, n_freq=None, unit_range=None):
@@ -275,19 +287,8 @@ def jackknife_phase(mem, spectra, expectation_type, total, planes, measures, ove
     ``measures`` of _lib.JACKKNIFE_PHASE_MEASURES and a total accumulator record ``total`` that holds the planes these measures
     read (_lib.JACKKNIFE_PHASE_PLANES) among its ``planes``.  Returns (float64 device array laid out as _lib.jackknife_blocks
     says, n_bins)."""
-    lib = _lib._handle()
-    d = spectra.desc(expectation_type, n_freq)
-    n_bins, n_units, unit_size, n_out = c_int64(), c_int64(), c_int64(), c_int64()
-    _lib.check(lib.sc_jackknife_phase_layout(byref(d), measures, over, byref(n_bins), byref(n_units), byref(unit_size), byref(n_out)),
-               "sc_jackknife_phase_layout")
-    lo, hi = (0, n_units.value) if unit_range is None else unit_range
-    ws_bytes = int(lib.sc_jackknife_phase_workspace_bytes(byref(d), measures, over, lo, hi))
-    ws = mem.empty((ws_bytes,), np.uint8) if ws_bytes else None
-    out = mem.empty((n_out.value,), np.float64)
-    fn = lib.sc_jackknife_phase_f64 if spectra.f64 else lib.sc_jackknife_phase_f32
-    _lib.check(fn(mem.ptr(spectra.X), byref(d), mem.ptr(total), _planes(mem, total, planes), measures, over, lo, hi, n_units_total,
-                  mem.ptr(out), _ptr(mem, ws), ws_bytes, mem.stream()), "sc_jackknife_phase")
-    return out, n_bins.value
+    return _jackknife(mem, "sc_jackknife_phase", spectra, expectation_type, total, planes, measures, over, n_units_total, n_freq,
+                      unit_range)
 
 
 def jackknife_phase_totals(mem, spectra, expectation_type, planes, over, n_freq=None, unit_range=None):
@@ -300,9 +301,8 @@ def jackknife_phase_totals(mem, spectra, expectation_type, planes, over, n_freq=
     n_bins, per_bin, _, n_obs = _stage_abc.accum_layout(spectra, expectation_type, planes, n_freq)
     n_units = c_int64()
     _lib.check(lib.sc_jackknife_phase_layout(byref(d), 0x1, over, None, byref(n_units), None, None), "sc_jackknife_phase_layout")
-    lo, hi = (0, n_units.value) if unit_range is None else unit_range
-    ws_bytes = int(lib.sc_jackknife_phase_totals_workspace_bytes(byref(d), planes, over, lo, hi))
-    ws = mem.empty((ws_bytes,), np.uint8) if ws_bytes else None
+    lo, hi, ws, ws_bytes = _jackknife_workspace(mem, lib.sc_jackknife_phase_totals_workspace_bytes, d, planes, over, n_units.value,
+                                                unit_range)
     record = mem.empty((n_bins, per_bin), np.float64)
     fn = lib.sc_jackknife_phase_totals_f64 if spectra.f64 else lib.sc_jackknife_phase_totals_f32
     _lib.check(fn(mem.ptr(spectra.X), byref(d), planes, over, lo, hi, mem.ptr(record), _ptr(mem, ws), ws_bytes, mem.stream()),

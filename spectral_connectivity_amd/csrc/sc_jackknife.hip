@@ -6,23 +6,29 @@
 // epilogue d_u = theta(S - G_u) - theta(S).  The kernel returns theta(S), sum_u d_u and sum_u d_u^2; the host finishes
 // (m = sum d / n, sum (d - m)^2 = sum d^2 - n m^2: d is already centred on the full estimate, so m is of the order of d).
 //
-// One workgroup of 256 threads owns (bin, pair of 32-channel tiles, share of the units); a thread owns 2 x 2 entries (i, j) of
-// the tile pair and keeps their totals, the running G_u and the two sums of every measure in registers.  The unit's rows of the
-// two channel tiles are staged in LDS 32 rows at a time; G_u is summed in the engine's precision (f32 products for complex64
-// spectra, f64 for complex128), the subtraction, the statistic and the sums are fp64 on both engines.  Only i < j is evaluated;
-// the mirror entry is written with it (imaginary coherence: negated).  The tile pairs of a bin are consecutive workgroups, so a
-// bin's rows come from HBM once and from cache for the other pairs.  Where bins x tile pairs do not fill the chip the units are
-// split over gridDim.y workgroups that write partial sums to the workspace, added in split order by a second kernel: no
-// floating-point atomics anywhere, results are bit-identical from run to run.
+// The walk (jk_place, jk_walk), the same for every kernel here: one workgroup of 256 threads owns (bin, pair of 32-channel tiles,
+// share of the units); a thread owns 2 x 2 entries (i, j) of the tile pair.  The rows of the two channel tiles are staged in LDS 32
+// observations at a time, and the walk hands every observation to the kernel's per-row callable as (x_i[2], x_j[2]) and calls its
+// per-unit callable after the g-th row of a unit.  The tile pairs of a bin are consecutive workgroups, so a bin's rows come from
+// HBM once and from cache for the other pairs.  Where bins x tile pairs do not fill the chip the units are split over gridDim.y
+// workgroups that write partial sums to the workspace, added in split order by a second kernel: no floating-point atomics
+// anywhere, results are bit-identical from run to run.  A kernel is what it keeps in registers and its two callables:
 //
-// The phase-lag family (jk_phase_kernel, same geometry): per observation Im s = Im(x_i conj(x_j)) is formed once and summed per
-// unit as a_u = sum Im s, b_u = sum |Im s|, c_u = sum sign(Im s) (an integer) and q_u = sum (Im s)^2; the totals A, B, N, Q are the
-// planes SC_PLANE_CSM (im), _ABS_IM, _SIGN_IM and _IM_SQ of the accumulator record, and with n = n_units_total g observations
+// jk_kernel: the totals S_ii, S_jj, S_ij of the record.  Per row: G_u and the two powers, summed in the engine's precision (f32
+// products for complex64 spectra, f64 for complex128).  Per unit: the subtraction, d_u of every measure and its two sums, in
+// fp64 on both engines.  Only i < j is evaluated; the mirror entry is written with it (imaginary coherence: negated).
+//
+// jk_phase_kernel, the phase-lag family.  Per row: JkPhaseUnit::add -- Im s = Im(x_i conj(x_j)) is formed once and summed per unit
+// as a_u = sum Im s, b_u = sum |Im s|, c_u = sum sign(Im s) (an integer) and q_u = sum (Im s)^2.  Per unit: the totals A, B, N, Q
+// are the planes SC_PLANE_CSM (im), _ABS_IM, _SIGN_IM and _IM_SQ of the accumulator record, and with n = n_units_total g observations
 //     PLI = N / n,  wPLI = (A / n) / w with w = B / n (1 where w < 2^-52),  debiased PLI^2 = (n PLI^2 - 1) / (n - 1),
 //     debiased wPLI^2 = (A^2 - Q) / (B^2 - Q) (NaN where the denominator is exactly 0)
 // on the identity scale; a delete-one value is the same formula on A - a_u, ... and n' = (n_units_total - 1) g.
-// jk_phase_totals_kernel sums such a record from the spectra (the fp64 sum of the very unit sums that are subtracted): what the
-// hosts hand in, because the float32 engine's own records are too coarse in A for the debiased wPLI^2 of a pair near 0.
+//
+// jk_phase_totals_kernel sums such a record from the spectra.  Per row: the same JkPhaseUnit::add; per unit: the unit sums added
+// in fp64.  Both kernels run the one walk and the one JkPhaseUnit, so a total is by construction the fp64 sum of the very unit
+// sums that are subtracted from it.  It is what the hosts hand in, because the float32 engine's own records are too coarse in A
+// for the debiased wPLI^2 of a pair near 0.
 #include "sc_common.h"
 
 #include <math.h>
@@ -36,84 +42,62 @@ constexpr int JK_MAX_BLOCKS = 4;  // measure blocks of one call (three of jk_ker
 constexpr uint32_t JK_PHASE_ALL = SC_JACKKNIFE_PHASE_PLI | SC_JACKKNIFE_PHASE_WPLI | SC_JACKKNIFE_PHASE_DEBIASED_PLI2 |
                                   SC_JACKKNIFE_PHASE_DEBIASED_WPLI2;
 
-struct JkArgs {
+// what the walk and the write-out of every kernel need (jk_geometry fills it)
+struct JkGeom {
     ScAxes a;
-    ScRec total;
-    int NB16, n_tiles16, p_csm;
+    int NB16, n_tiles16;
     int64_t rec_stride;          // elements of one bin record
     int n_freq, NT, n_tp;
     int over, g, q_tapers;       // rows per unit; tapers per window inside a unit (over = trials)
     int64_t unit_begin, unit_end, units_per_split;
-    double n_total, ln_ratio;    // units of the whole job, ln(n / (n - 1))
-    uint32_t measures;
     int64_t n_bins;
-    int64_t off[3];              // first double of each measure's block, -1: not requested
     int64_t out_doubles;
     double* out;                 // split s writes at out + s * out_doubles
 };
 
-template <typename Args>
-__device__ __forceinline__ int64_t jk_row_offset(const Args& p, int64_t u, int q) {
+// a thread's place: the entries (ci[a], cj[b]), a, b = 0, 1, of the tile pair (ti, tj) of bin `bin`, whose rows start x_off
+// elements into the spectra
+struct JkPlace {
+    int tx, ty, ti, tj, ci[2], cj[2];
+    int64_t bin, x_off;
+};
+
+__device__ __forceinline__ JkPlace jk_place(const JkGeom& p) {
+    JkPlace w;
+    w.tx = threadIdx.x & 15;
+    w.ty = threadIdx.x >> 4;
+    const int64_t wg = blockIdx.x;
+    const int tp = (int)(wg % p.n_tp);
+    w.bin = wg / p.n_tp;
+    int ti = 0, rem = tp;
+    while (rem >= p.NT - ti) { rem -= p.NT - ti; ++ti; }
+    w.ti = ti;
+    w.tj = ti + rem;
+    const int f = (int)(w.bin % p.n_freq), grp = (int)(w.bin / p.n_freq);
+    w.x_off = (int64_t)f * p.a.sF + sc_group_offset(p.a, grp);
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        w.ci[a] = w.ti * JK_T + w.ty + 16 * a;
+        w.cj[a] = w.tj * JK_T + w.tx + 16 * a;
+    }
+    return w;
+}
+
+__device__ __forceinline__ int64_t jk_row_offset(const JkGeom& p, int64_t u, int q) {
     if (p.over == SC_JACKKNIFE_OVER_OBSERVATIONS) return sc_obs_offset(p.a, (int)u);
     const int w = q / p.q_tapers, k = q - w * p.q_tapers;
     return (int64_t)w * p.a.sW + u * p.a.sR + (int64_t)k * p.a.sK;
 }
 
-// S_ij (i <= j) of the total record: upper-triangular 16 x 16 tiles, re and im planes
-__device__ __forceinline__ void jk_total(const ScRec& rec, const JkArgs& p, int i, int j, double& re, double& im) {
-    const int64_t off = (int64_t)sc_tile_index(i >> 4, j >> 4, p.NB16) * SC_TILE_ELEMS + (i & 15) * 16 + (j & 15);
-    const int64_t plane = (int64_t)p.n_tiles16 * SC_TILE_ELEMS;
-    re = rec[p.p_csm * plane + off];
-    im = rec[(p.p_csm + 1) * plane + off];
-}
-
-template <typename T, typename T2>
-__global__ __launch_bounds__(256) void jk_kernel(const T2* __restrict__ X, JkArgs p) {
+// The units of this workgroup's split, row by row: row(xi, xj) for every observation (the two entries of either channel tile
+// this thread owns; channels past C read as 0), unit() after the last row of every unit.
+template <typename T2, typename Row, typename Unit>
+__device__ __forceinline__ void jk_walk(const T2* __restrict__ X, const JkGeom& p, const JkPlace& w, Row row, Unit unit) {
     __shared__ T2 rows[JK_ROWS][2 * JK_T];
     __shared__ int64_t row_off[JK_ROWS];      // element offset of every staged row: one decode per row, not per element
-    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    const int64_t wg = blockIdx.x;
-    const int tp = (int)(wg % p.n_tp);
-    const int64_t bin = wg / p.n_tp;
-    int ti = 0, rem = tp;
-    while (rem >= p.NT - ti) { rem -= p.NT - ti; ++ti; }
-    const int tj = ti + rem;
-    const int f = (int)(bin % p.n_freq), grp = (int)(bin / p.n_freq);
-    const T2* Xb = X + (int64_t)f * p.a.sF + sc_group_offset(p.a, grp);
+    const int tid = threadIdx.x, tx = w.tx, ty = w.ty, ti = w.ti, tj = w.tj;
+    const T2* Xb = X + w.x_off;
     const int C = p.a.C;
-    const ScRec rec = p.total + bin * p.rec_stride;
-    const bool want_pow = p.measures & SC_JACKKNIFE_POWER, want_coh = p.measures & SC_JACKKNIFE_COHERENCE_MAGNITUDE,
-               want_im = p.measures & SC_JACKKNIFE_IMAGINARY_COHERENCE;
-    const bool diag_thread = ti == tj && tx == ty;
-    const double nan = __builtin_nan("");
-
-    int ci[2], cj[2];
-    double Sii[2], Sjj[2], Sre[2][2], Sim[2][2], bcoh[2][2], bim[2][2];
-    bool valid[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        double dummy;
-        ci[a] = ti * JK_T + ty + 16 * a;
-        cj[a] = tj * JK_T + tx + 16 * a;
-        Sii[a] = Sjj[a] = 1.0;
-        if (ci[a] < C) jk_total(rec, p, ci[a], ci[a], Sii[a], dummy);
-        if (cj[a] < C) jk_total(rec, p, cj[a], cj[a], Sjj[a], dummy);
-    }
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            valid[a][b] = ci[a] < cj[b] && cj[b] < C;
-            Sre[a][b] = Sim[a][b] = 0.0;
-            if (valid[a][b]) jk_total(rec, p, ci[a], cj[b], Sre[a][b], Sim[a][b]);
-            const double rr = (1.0 / sqrt(Sii[a])) * (1.0 / sqrt(Sjj[b]));
-            bcoh[a][b] = sqrt(Sre[a][b] * Sre[a][b] + Sim[a][b] * Sim[a][b]) * rr;
-            bim[a][b] = Sim[a][b] * rr;
-        }
-
-    double coh1[2][2] = {}, coh2[2][2] = {}, im1[2][2] = {}, im2[2][2] = {}, pw1[2] = {}, pw2[2] = {};
-    T Gre[2][2] = {}, Gim[2][2] = {}, Pi[2] = {}, Pj[2] = {};
-
     const int64_t u0 = p.unit_begin + (int64_t)blockIdx.y * p.units_per_split;
     const int64_t u1 = u0 + p.units_per_split < p.unit_end ? u0 + p.units_per_split : p.unit_end;
     const int n_rows = (int)((u1 - u0) * p.g);
@@ -139,6 +123,76 @@ __global__ __launch_bounds__(256) void jk_kernel(const T2* __restrict__ X, JkArg
             T2 xi[2], xj[2];
             xi[0] = rows[r][ty]; xi[1] = rows[r][ty + 16];
             xj[0] = rows[r][JK_T + tx]; xj[1] = rows[r][JK_T + tx + 16];
+            row(xi, xj);
+            if (++cnt == p.g) {
+                cnt = 0;
+                unit();
+            }
+        }
+    }
+}
+
+// element (i, j), i <= j, of a plane of a bin record: upper-triangular 16 x 16 tiles
+__device__ __forceinline__ int64_t jk_tile_offset(int i, int j, int NB16) {
+    return (int64_t)sc_tile_index(i >> 4, j >> 4, NB16) * SC_TILE_ELEMS + (i & 15) * 16 + (j & 15);
+}
+
+struct JkArgs {
+    JkGeom geo;
+    ScRec total;
+    int p_csm;
+    double n_total, ln_ratio;    // units of the whole job, ln(n / (n - 1))
+    uint32_t measures;
+    int64_t off[3];              // first double of each measure's block, -1: not requested
+};
+
+// S_ij (i <= j) of the total record: re and im planes
+__device__ __forceinline__ void jk_total(const ScRec& rec, const JkArgs& p, int i, int j, double& re, double& im) {
+    const int64_t off = jk_tile_offset(i, j, p.geo.NB16);
+    const int64_t plane = (int64_t)p.geo.n_tiles16 * SC_TILE_ELEMS;
+    re = rec[p.p_csm * plane + off];
+    im = rec[(p.p_csm + 1) * plane + off];
+}
+
+template <typename T, typename T2>
+__global__ __launch_bounds__(256) void jk_kernel(const T2* __restrict__ X, JkArgs p) {
+    const JkPlace w = jk_place(p.geo);
+    const int (&ci)[2] = w.ci, (&cj)[2] = w.cj;
+    const int64_t bin = w.bin;
+    const int C = p.geo.a.C;
+    const ScRec rec = p.total + bin * p.geo.rec_stride;
+    const bool want_pow = p.measures & SC_JACKKNIFE_POWER, want_coh = p.measures & SC_JACKKNIFE_COHERENCE_MAGNITUDE,
+               want_im = p.measures & SC_JACKKNIFE_IMAGINARY_COHERENCE;
+    const bool diag_thread = w.ti == w.tj && w.tx == w.ty;
+    const double nan = __builtin_nan(""), ln_ratio = p.ln_ratio;
+
+    double Sii[2], Sjj[2], Sre[2][2], Sim[2][2], bcoh[2][2], bim[2][2];
+    bool valid[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        double dummy;
+        Sii[a] = Sjj[a] = 1.0;
+        if (ci[a] < C) jk_total(rec, p, ci[a], ci[a], Sii[a], dummy);
+        if (cj[a] < C) jk_total(rec, p, cj[a], cj[a], Sjj[a], dummy);
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            valid[a][b] = ci[a] < cj[b] && cj[b] < C;
+            Sre[a][b] = Sim[a][b] = 0.0;
+            if (valid[a][b]) jk_total(rec, p, ci[a], cj[b], Sre[a][b], Sim[a][b]);
+            const double rr = (1.0 / sqrt(Sii[a])) * (1.0 / sqrt(Sjj[b]));
+            bcoh[a][b] = sqrt(Sre[a][b] * Sre[a][b] + Sim[a][b] * Sim[a][b]) * rr;
+            bim[a][b] = Sim[a][b] * rr;
+        }
+
+    double coh1[2][2] = {}, coh2[2][2] = {}, im1[2][2] = {}, im2[2][2] = {}, pw1[2] = {}, pw2[2] = {};
+    T Gre[2][2] = {}, Gim[2][2] = {}, Pi[2] = {}, Pj[2] = {};
+
+    jk_walk(
+        X, p.geo, w,
+        [&](const T2 (&xi)[2], const T2 (&xj)[2]) {
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
                 Pi[a] += xi[a].x * xi[a].x + xi[a].y * xi[a].y;
@@ -149,54 +203,52 @@ __global__ __launch_bounds__(256) void jk_kernel(const T2* __restrict__ X, JkArg
                     Gim[a][b] += xi[a].y * xj[b].x - xi[a].x * xj[b].y;
                 }
             }
-            if (++cnt == p.g) {
-                // the unit is complete: d_u = theta(S - G_u) - theta(S) of every measure, in fp64
-                cnt = 0;
-                double ri[2], rj[2];
+        },
+        [&, want_pow, want_coh, want_im, diag_thread, ln_ratio]() {   // (the flags by value: the loop then compiles as written in place)
+            // the unit is complete: d_u = theta(S - G_u) - theta(S) of every measure, in fp64
+            double ri[2], rj[2];
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+                ri[a] = 1.0 / sqrt(Sii[a] - (double)Pi[a]);
+                rj[a] = 1.0 / sqrt(Sjj[a] - (double)Pj[a]);
+            }
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    if (valid[a][b]) {
+                        const double re = Sre[a][b] - (double)Gre[a][b], im = Sim[a][b] - (double)Gim[a][b];
+                        const double rr = ri[a] * rj[b];
+                        if (want_coh) {
+                            // atanh(x) - atanh(y) = atanh((x - y) / (1 - x y)): no difference of two nearly equal transcendentals
+                            const double mag = sqrt(re * re + im * im) * rr;
+                            const double d = atanh((mag - bcoh[a][b]) / (1.0 - mag * bcoh[a][b]));
+                            coh1[a][b] += d;
+                            coh2[a][b] += d * d;
+                        }
+                        if (want_im) {
+                            const double d = im * rr - bim[a][b];
+                            im1[a][b] += d;
+                            im2[a][b] += d * d;
+                        }
+                    }
+                    Gre[a][b] = 0; Gim[a][b] = 0;
+                }
+            if (want_pow && diag_thread) {
 #pragma unroll
                 for (int a = 0; a < 2; ++a) {
-                    ri[a] = 1.0 / sqrt(Sii[a] - (double)Pi[a]);
-                    rj[a] = 1.0 / sqrt(Sjj[a] - (double)Pj[a]);
+                    // ln((S - G) / ((n - 1) g)) - ln(S / (n g)) = log1p(-G / S) + ln(n / (n - 1))
+                    const double d = log1p(-(double)Pi[a] / Sii[a]) + ln_ratio;
+                    pw1[a] += d;
+                    pw2[a] += d * d;
                 }
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) {
-                        if (valid[a][b]) {
-                            const double re = Sre[a][b] - (double)Gre[a][b], im = Sim[a][b] - (double)Gim[a][b];
-                            const double rr = ri[a] * rj[b];
-                            if (want_coh) {
-                                // atanh(x) - atanh(y) = atanh((x - y) / (1 - x y)): no difference of two nearly equal transcendentals
-                                const double mag = sqrt(re * re + im * im) * rr;
-                                const double d = atanh((mag - bcoh[a][b]) / (1.0 - mag * bcoh[a][b]));
-                                coh1[a][b] += d;
-                                coh2[a][b] += d * d;
-                            }
-                            if (want_im) {
-                                const double d = im * rr - bim[a][b];
-                                im1[a][b] += d;
-                                im2[a][b] += d * d;
-                            }
-                        }
-                        Gre[a][b] = 0; Gim[a][b] = 0;
-                    }
-                if (want_pow && diag_thread) {
-#pragma unroll
-                    for (int a = 0; a < 2; ++a) {
-                        // ln((S - G) / ((n - 1) g)) - ln(S / (n g)) = log1p(-G / S) + ln(n / (n - 1))
-                        const double d = log1p(-(double)Pi[a] / Sii[a]) + p.ln_ratio;
-                        pw1[a] += d;
-                        pw2[a] += d * d;
-                    }
-                }
-#pragma unroll
-                for (int a = 0; a < 2; ++a) { Pi[a] = 0; Pj[a] = 0; }
             }
-        }
-    }
+#pragma unroll
+            for (int a = 0; a < 2; ++a) { Pi[a] = 0; Pj[a] = 0; }
+        });
 
-    double* out = p.out + (int64_t)blockIdx.y * p.out_doubles;
-    const int64_t CC = (int64_t)C * C, plane2 = p.n_bins * CC;
+    double* out = p.geo.out + (int64_t)blockIdx.y * p.geo.out_doubles;
+    const int64_t CC = (int64_t)C * C, plane2 = p.geo.n_bins * CC;
     if (want_coh) {
         double* th = out + p.off[1] + bin * CC;
 #pragma unroll
@@ -239,8 +291,8 @@ __global__ __launch_bounds__(256) void jk_kernel(const T2* __restrict__ X, JkArg
             }
             if (want_pow) {
                 double* th = out + p.off[0] + bin * C;
-                const int64_t plane1 = p.n_bins * C;
-                th[ci[a]] = Sii[a] > 0.0 ? log(Sii[a] / (p.n_total * (double)p.g)) : nan;
+                const int64_t plane1 = p.geo.n_bins * C;
+                th[ci[a]] = Sii[a] > 0.0 ? log(Sii[a] / (p.n_total * (double)p.geo.g)) : nan;
                 th[plane1 + ci[a]] = Sii[a] > 0.0 ? pw1[a] : nan;
                 th[2 * plane1 + ci[a]] = Sii[a] > 0.0 ? pw2[a] : nan;
             }
@@ -250,20 +302,40 @@ __global__ __launch_bounds__(256) void jk_kernel(const T2* __restrict__ X, JkArg
 
 // ---- the phase-lag family ------------------------------------------------------------------------------------------------------
 struct JkPhaseArgs {
-    ScAxes a;
+    JkGeom geo;
     ScRec total;
-    int NB16, n_tiles16;
     int p_im, p_abs, p_sq, p_sign;   // plane index of sum Im s, sum |Im s|, sum (Im s)^2, sum sign(Im s) in a bin record; -1: absent
-    int64_t rec_stride;              // elements of one bin record
-    int n_freq, NT, n_tp;
-    int over, g, q_tapers;
-    int64_t unit_begin, unit_end, units_per_split;
     double n_full, n_del;            // observations of the full estimate and of a delete-one estimate
     uint32_t measures;
-    int64_t n_bins;
     int64_t off[JK_MAX_BLOCKS];      // first double of each measure's block, -1: not requested
-    int64_t out_doubles;
-    double* out;                     // split s writes at out + s * out_doubles
+};
+
+// the sums of one unit over a thread's 2 x 2 entries, in the engine's precision: what jk_phase_kernel subtracts from the totals
+// and what jk_phase_totals_kernel adds up to them
+template <typename T>
+struct JkPhaseUnit {
+    T a[2][2], b[2][2], q[2][2];     // sum Im s, sum |Im s|, sum (Im s)^2
+    int c[2][2];                     // sum sign(Im s)
+
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) { a[i][j] = 0; b[i][j] = 0; q[i][j] = 0; c[i][j] = 0; }
+    }
+    template <typename T2>
+    __device__ __forceinline__ void add(const T2 (&xi)[2], const T2 (&xj)[2]) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const T im = xi[i].y * xj[j].x - xi[i].x * xj[j].y;
+                a[i][j] += im;
+                b[i][j] += im < 0 ? -im : im;
+                q[i][j] += im * im;
+                c[i][j] += (im > 0) - (im < 0);
+            }
+    }
 };
 
 // the four statistics from the sums (A, B, N, Q) of n observations; sc_measure.hip's formulas on the identity scale
@@ -279,36 +351,30 @@ __device__ __forceinline__ double jk_debiased_wpli2(double A, double B, double Q
     return den == 0.0 ? __builtin_nan("") : (A * A - Q) / den;
 }
 
+// one deviation into the two sums about the pivot (the first unit's deviation; see jk_phase_kernel)
+__device__ __forceinline__ void jk_shifted_add(double d, bool first, double& piv, double& s1, double& s2) {
+    if (first) piv = d;
+    const double e = d - piv;
+    s1 += e;
+    s2 += e * e;
+}
+
 template <typename T, typename T2>
 __global__ __launch_bounds__(256) void jk_phase_kernel(const T2* __restrict__ X, JkPhaseArgs p) {
-    __shared__ T2 rows[JK_ROWS][2 * JK_T];
-    __shared__ int64_t row_off[JK_ROWS];
-    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    const int64_t wg = blockIdx.x;
-    const int tp = (int)(wg % p.n_tp);
-    const int64_t bin = wg / p.n_tp;
-    int ti = 0, rem = tp;
-    while (rem >= p.NT - ti) { rem -= p.NT - ti; ++ti; }
-    const int tj = ti + rem;
-    const int f = (int)(bin % p.n_freq), grp = (int)(bin / p.n_freq);
-    const T2* Xb = X + (int64_t)f * p.a.sF + sc_group_offset(p.a, grp);
-    const int C = p.a.C;
-    const ScRec rec = p.total + bin * p.rec_stride;
+    const JkPlace w = jk_place(p.geo);
+    const int (&ci)[2] = w.ci, (&cj)[2] = w.cj;
+    const int64_t bin = w.bin;
+    const int C = p.geo.a.C;
+    const ScRec rec = p.total + bin * p.geo.rec_stride;
     const bool want_pli = p.measures & SC_JACKKNIFE_PHASE_PLI, want_wpli = p.measures & SC_JACKKNIFE_PHASE_WPLI,
                want_dpli = p.measures & SC_JACKKNIFE_PHASE_DEBIASED_PLI2, want_dwpli = p.measures & SC_JACKKNIFE_PHASE_DEBIASED_WPLI2;
-    const bool diag_thread = ti == tj && tx == ty;
+    const bool diag_thread = w.ti == w.tj && w.tx == w.ty;
     const double nan = __builtin_nan("");
-    const int64_t plane = (int64_t)p.n_tiles16 * SC_TILE_ELEMS;
+    const int64_t plane = (int64_t)p.geo.n_tiles16 * SC_TILE_ELEMS;
 
-    int ci[2], cj[2];
     bool valid[2][2];
     double tA[2][2], tB[2][2], tN[2][2], tQ[2][2];          // totals of the record
     double th[4][2][2];                                     // the full estimates
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        ci[a] = ti * JK_T + ty + 16 * a;
-        cj[a] = tj * JK_T + tx + 16 * a;
-    }
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -316,8 +382,7 @@ __global__ __launch_bounds__(256) void jk_phase_kernel(const T2* __restrict__ X,
             valid[a][b] = ci[a] < cj[b] && cj[b] < C;
             tA[a][b] = tB[a][b] = tN[a][b] = tQ[a][b] = 0.0;
             if (valid[a][b]) {
-                const int i = ci[a], j = cj[b];
-                const int64_t off = (int64_t)sc_tile_index(i >> 4, j >> 4, p.NB16) * SC_TILE_ELEMS + (i & 15) * 16 + (j & 15);
+                const int64_t off = jk_tile_offset(ci[a], cj[b], p.geo.NB16);
                 if (p.p_im >= 0) tA[a][b] = rec[p.p_im * plane + off];
                 if (p.p_abs >= 0) tB[a][b] = rec[p.p_abs * plane + off];
                 if (p.p_sq >= 0) tQ[a][b] = rec[p.p_sq * plane + off];
@@ -336,93 +401,36 @@ __global__ __launch_bounds__(256) void jk_phase_kernel(const T2* __restrict__ X,
     // bit, which is what the host's n m^2 is: a standard error of exactly 0, as in exact arithmetic.
     double s1[4][2][2] = {}, s2[4][2][2] = {}, piv[4][2][2] = {};
     int n_done = 0;
-    T ua[2][2] = {}, ub[2][2] = {}, uq[2][2] = {};
-    int uc[2][2] = {};
+    JkPhaseUnit<T> u;
+    u.clear();
 
-    const int64_t u0 = p.unit_begin + (int64_t)blockIdx.y * p.units_per_split;
-    const int64_t u1 = u0 + p.units_per_split < p.unit_end ? u0 + p.units_per_split : p.unit_end;
-    const int n_rows = (int)((u1 - u0) * p.g);
-    int cnt = 0;
-    for (int r0 = 0; r0 < n_rows; r0 += JK_ROWS) {
-        const int nr = n_rows - r0 < JK_ROWS ? n_rows - r0 : JK_ROWS;
-        __syncthreads();
-        if (tid < nr) {
-            const int q = r0 + tid, du = q / p.g;
-            row_off[tid] = jk_row_offset(p, u0 + du, q - du * p.g);
-        }
-        __syncthreads();
-        for (int e = tid; e < nr * 2 * JK_T; e += 256) {
-            const int r = e >> 6, col = e & 63;
-            const int c = (col < JK_T ? ti : tj) * JK_T + (col & (JK_T - 1));
-            T2 v;
-            v.x = 0; v.y = 0;
-            if (c < C) v = Xb[row_off[r] + c];
-            rows[r][col] = v;
-        }
-        __syncthreads();
-        for (int r = 0; r < nr; ++r) {
-            T2 xi[2], xj[2];
-            xi[0] = rows[r][ty]; xi[1] = rows[r][ty + 16];
-            xj[0] = rows[r][JK_T + tx]; xj[1] = rows[r][JK_T + tx + 16];
+    jk_walk(
+        X, p.geo, w, [&](const T2 (&xi)[2], const T2 (&xj)[2]) { u.add(xi, xj); },
+        [&]() {
+            // the unit is complete: d_u = theta(sums without the unit, n') - theta(sums, n) of every requested measure, in fp64
+            const bool first = n_done == 0;
 #pragma unroll
             for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
-                    const T im = xi[a].y * xj[b].x - xi[a].x * xj[b].y;
-                    ua[a][b] += im;
-                    ub[a][b] += im < 0 ? -im : im;
-                    uq[a][b] += im * im;
-                    uc[a][b] += (im > 0) - (im < 0);
-                }
-            if (++cnt == p.g) {
-                // the unit is complete: d_u = theta(sums without the unit, n') - theta(sums, n) of every requested measure, in fp64
-                cnt = 0;
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) {
-                        if (valid[a][b]) {
-                            if (want_pli || want_dpli) {
-                                const double pli = jk_pli(tN[a][b] - (double)uc[a][b], p.n_del);
-                                if (want_pli) {
-                                    const double d = pli - th[0][a][b];
-                                    if (n_done == 0) piv[0][a][b] = d;
-                                    const double e = d - piv[0][a][b];
-                                    s1[0][a][b] += e;
-                                    s2[0][a][b] += e * e;
-                                }
-                                if (want_dpli) {
-                                    const double d = jk_debiased_pli2(pli, p.n_del) - th[2][a][b];
-                                    if (n_done == 0) piv[2][a][b] = d;
-                                    const double e = d - piv[2][a][b];
-                                    s1[2][a][b] += e;
-                                    s2[2][a][b] += e * e;
-                                }
-                            }
-                            if (want_wpli || want_dwpli) {
-                                const double A = tA[a][b] - (double)ua[a][b], B = tB[a][b] - (double)ub[a][b];
-                                if (want_wpli) {
-                                    const double d = jk_wpli(A, B, p.n_del) - th[1][a][b];
-                                    if (n_done == 0) piv[1][a][b] = d;
-                                    const double e = d - piv[1][a][b];
-                                    s1[1][a][b] += e;
-                                    s2[1][a][b] += e * e;
-                                }
-                                if (want_dwpli) {
-                                    const double d = jk_debiased_wpli2(A, B, tQ[a][b] - (double)uq[a][b]) - th[3][a][b];
-                                    if (n_done == 0) piv[3][a][b] = d;
-                                    const double e = d - piv[3][a][b];
-                                    s1[3][a][b] += e;
-                                    s2[3][a][b] += e * e;
-                                }
-                            }
-                        }
-                        ua[a][b] = 0; ub[a][b] = 0; uq[a][b] = 0; uc[a][b] = 0;
+                    if (!valid[a][b]) continue;
+                    if (want_pli || want_dpli) {
+                        const double pli = jk_pli(tN[a][b] - (double)u.c[a][b], p.n_del);
+                        if (want_pli) jk_shifted_add(pli - th[0][a][b], first, piv[0][a][b], s1[0][a][b], s2[0][a][b]);
+                        if (want_dpli)
+                            jk_shifted_add(jk_debiased_pli2(pli, p.n_del) - th[2][a][b], first, piv[2][a][b], s1[2][a][b], s2[2][a][b]);
                     }
-                ++n_done;
-            }
-        }
-    }
+                    if (want_wpli || want_dwpli) {
+                        const double A = tA[a][b] - (double)u.a[a][b], B = tB[a][b] - (double)u.b[a][b];
+                        if (want_wpli) jk_shifted_add(jk_wpli(A, B, p.n_del) - th[1][a][b], first, piv[1][a][b], s1[1][a][b], s2[1][a][b]);
+                        if (want_dwpli)
+                            jk_shifted_add(jk_debiased_wpli2(A, B, tQ[a][b] - (double)u.q[a][b]) - th[3][a][b], first, piv[3][a][b],
+                                           s1[3][a][b], s2[3][a][b]);
+                    }
+                }
+            u.clear();
+            ++n_done;
+        });
 
 #pragma unroll
     for (int m = 0; m < 4; ++m)
@@ -435,8 +443,8 @@ __global__ __launch_bounds__(256) void jk_phase_kernel(const T2* __restrict__ X,
                 s2[m][a][b] = r * s1[m][a][b] + (t2 + r * t1);
             }
 
-    double* out = p.out + (int64_t)blockIdx.y * p.out_doubles;
-    const int64_t CC = (int64_t)C * C, plane2 = p.n_bins * CC;
+    double* out = p.geo.out + (int64_t)blockIdx.y * p.geo.out_doubles;
+    const int64_t CC = (int64_t)C * C, plane2 = p.geo.n_bins * CC;
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
         if (!(p.measures & (1u << m))) continue;
@@ -463,87 +471,39 @@ __global__ __launch_bounds__(256) void jk_phase_kernel(const T2* __restrict__ X,
     }
 }
 
-// The totals of the phase-lag family from the spectra themselves: the same staging and the same per-unit sums as jk_phase_kernel
-// (a_u, b_u, q_u in T, c_u an integer), added over the units in fp64 and written as a record of doubles in the accumulator layout
-// (upper 16 x 16 tiles; planes CSM (re = 0, im), ABS_IM, IM_SQ, SIGN_IM as requested).  A total is then the sum of exactly the unit
-// sums jk_phase_kernel subtracts from it: sum Im s = +-sum |Im s| bit for bit where every observation has the same sign, and no
+// The totals of the phase-lag family from the spectra themselves: the unit sums of jk_phase_kernel, added over the units in fp64
+// and written as a record of doubles in the accumulator layout (upper 16 x 16 tiles; planes CSM (re = 0, im), ABS_IM, IM_SQ,
+// SIGN_IM as requested).  So sum Im s = +-sum |Im s| bit for bit where every observation has the same sign, and there is no
 // float32 summation error of thousands of observations in A, which the debiased wPLI^2 of a pair near 0 multiplies by B / A.
 template <typename T, typename T2>
 __global__ __launch_bounds__(256) void jk_phase_totals_kernel(const T2* __restrict__ X, JkPhaseArgs p) {
-    __shared__ T2 rows[JK_ROWS][2 * JK_T];
-    __shared__ int64_t row_off[JK_ROWS];
-    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    const int64_t wg = blockIdx.x;
-    const int tp = (int)(wg % p.n_tp);
-    const int64_t bin = wg / p.n_tp;
-    int ti = 0, rem = tp;
-    while (rem >= p.NT - ti) { rem -= p.NT - ti; ++ti; }
-    const int tj = ti + rem;
-    const int f = (int)(bin % p.n_freq), grp = (int)(bin / p.n_freq);
-    const T2* Xb = X + (int64_t)f * p.a.sF + sc_group_offset(p.a, grp);
-    const int C = p.a.C;
-
+    const JkPlace w = jk_place(p.geo);
     double sA[2][2] = {}, sB[2][2] = {}, sQ[2][2] = {}, sN[2][2] = {};
-    T ua[2][2] = {}, ub[2][2] = {}, uq[2][2] = {};
-    int uc[2][2] = {};
-    const int64_t u0 = p.unit_begin + (int64_t)blockIdx.y * p.units_per_split;
-    const int64_t u1 = u0 + p.units_per_split < p.unit_end ? u0 + p.units_per_split : p.unit_end;
-    const int n_rows = (int)((u1 - u0) * p.g);
-    int cnt = 0;
-    for (int r0 = 0; r0 < n_rows; r0 += JK_ROWS) {
-        const int nr = n_rows - r0 < JK_ROWS ? n_rows - r0 : JK_ROWS;
-        __syncthreads();
-        if (tid < nr) {
-            const int q = r0 + tid, du = q / p.g;
-            row_off[tid] = jk_row_offset(p, u0 + du, q - du * p.g);
-        }
-        __syncthreads();
-        for (int e = tid; e < nr * 2 * JK_T; e += 256) {
-            const int r = e >> 6, col = e & 63;
-            const int c = (col < JK_T ? ti : tj) * JK_T + (col & (JK_T - 1));
-            T2 v;
-            v.x = 0; v.y = 0;
-            if (c < C) v = Xb[row_off[r] + c];
-            rows[r][col] = v;
-        }
-        __syncthreads();
-        for (int r = 0; r < nr; ++r) {
-            T2 xi[2], xj[2];
-            xi[0] = rows[r][ty]; xi[1] = rows[r][ty + 16];
-            xj[0] = rows[r][JK_T + tx]; xj[1] = rows[r][JK_T + tx + 16];
+    JkPhaseUnit<T> u;
+    u.clear();
+
+    jk_walk(
+        X, p.geo, w, [&](const T2 (&xi)[2], const T2 (&xj)[2]) { u.add(xi, xj); },
+        [&]() {
 #pragma unroll
             for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
-                    const T im = xi[a].y * xj[b].x - xi[a].x * xj[b].y;
-                    ua[a][b] += im;
-                    ub[a][b] += im < 0 ? -im : im;
-                    uq[a][b] += im * im;
-                    uc[a][b] += (im > 0) - (im < 0);
+                    sA[a][b] += (double)u.a[a][b]; sB[a][b] += (double)u.b[a][b];
+                    sQ[a][b] += (double)u.q[a][b]; sN[a][b] += (double)u.c[a][b];
                 }
-            if (++cnt == p.g) {
-                cnt = 0;
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) {
-                        sA[a][b] += (double)ua[a][b]; sB[a][b] += (double)ub[a][b];
-                        sQ[a][b] += (double)uq[a][b]; sN[a][b] += (double)uc[a][b];
-                        ua[a][b] = 0; ub[a][b] = 0; uq[a][b] = 0; uc[a][b] = 0;
-                    }
-            }
-        }
-    }
+            u.clear();
+        });
 
-    double* rec = p.out + (int64_t)blockIdx.y * p.out_doubles + bin * p.rec_stride;
-    const int64_t plane = (int64_t)p.n_tiles16 * SC_TILE_ELEMS;
+    double* rec = p.geo.out + (int64_t)blockIdx.y * p.geo.out_doubles + w.bin * p.geo.rec_stride;
+    const int64_t plane = (int64_t)p.geo.n_tiles16 * SC_TILE_ELEMS;
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-            const int i = ti * JK_T + ty + 16 * a, j = tj * JK_T + tx + 16 * b;
-            if (!(i < j && j < C)) continue;
-            const int64_t off = (int64_t)sc_tile_index(i >> 4, j >> 4, p.NB16) * SC_TILE_ELEMS + (i & 15) * 16 + (j & 15);
+            const int i = w.ci[a], j = w.cj[b];
+            if (!(i < j && j < p.geo.a.C)) continue;
+            const int64_t off = jk_tile_offset(i, j, p.geo.NB16);
             if (p.p_im >= 0) rec[p.p_im * plane + off] = sA[a][b];
             if (p.p_abs >= 0) rec[p.p_abs * plane + off] = sB[a][b];
             if (p.p_sq >= 0) rec[p.p_sq * plane + off] = sQ[a][b];
@@ -575,7 +535,7 @@ __global__ void jk_fold(const double* __restrict__ ws, int n_splits, JkFold f, d
 struct JkPlan {
     ScAxes a;
     int64_t n_bins, n_units, g, out_doubles, off[JK_MAX_BLOCKS];
-    int NT, n_tp, q_tapers;
+    int NT, n_tp, q_tapers, over;
 };
 
 // phase: the masks and blocks of the phase-lag family (four C x C blocks) instead of power / coherence / imaginary coherence
@@ -591,6 +551,7 @@ int jk_plan(const sc_spectra_desc* desc, uint32_t measures, int over, JkPlan* pl
         SC_REQUIRE(measures && !(measures & ~(SC_JACKKNIFE_POWER | SC_JACKKNIFE_COHERENCE_MAGNITUDE | SC_JACKKNIFE_IMAGINARY_COHERENCE)),
                    "measures: a non-empty mask of SC_JACKKNIFE_POWER, _COHERENCE_MAGNITUDE, _IMAGINARY_COHERENCE");
     SC_REQUIRE(over == SC_JACKKNIFE_OVER_TRIALS || over == SC_JACKKNIFE_OVER_OBSERVATIONS, "over: SC_JACKKNIFE_OVER_TRIALS or _OBSERVATIONS");
+    pl->over = over;
     if (over == SC_JACKKNIFE_OVER_TRIALS) {
         SC_REQUIRE(desc->reduce_trial, "a jackknife over trials needs an expectation that averages over trials");
         pl->n_units = a.R;
@@ -641,6 +602,62 @@ void jk_splits(const JkPlan& pl, int64_t n_local, int64_t* per, int64_t* n_split
     *n_splits = (n_local + *per - 1) / *per;
 }
 
+// bytes the splits of a unit range need for their partial sums (0: one split, no workspace; 0 too where the plan failed)
+int64_t jk_workspace_bytes(int plan_rc, const JkPlan& pl, int64_t unit_begin, int64_t unit_end) {
+    if (plan_rc != SC_OK || unit_end <= unit_begin) return 0;
+    int64_t per, n_splits;
+    jk_splits(pl, unit_end - unit_begin, &per, &n_splits);
+    return n_splits > 1 ? n_splits * pl.out_doubles * (int64_t)sizeof(double) : 0;
+}
+
+// planes: of the record whose bins are rec_stride apart (the total a kernel reads, the record the totals kernel writes)
+JkGeom jk_geometry(const JkPlan& pl, uint32_t planes, int64_t unit_begin, int64_t unit_end, int64_t per, double* out) {
+    JkGeom p = {};
+    p.a = pl.a;
+    p.NB16 = sc_n_blocks(pl.a.C);
+    p.n_tiles16 = sc_n_tiles(p.NB16);
+    p.rec_stride = (int64_t)sc_plane_count(planes) * p.n_tiles16 * SC_TILE_ELEMS;
+    p.n_freq = pl.a.F; p.NT = pl.NT; p.n_tp = pl.n_tp;
+    p.over = pl.over; p.g = (int)pl.g; p.q_tapers = pl.q_tapers;
+    p.unit_begin = unit_begin; p.unit_end = unit_end; p.units_per_split = per;
+    p.n_bins = pl.n_bins;
+    p.out_doubles = pl.out_doubles;
+    p.out = out;
+    return p;
+}
+
+// the unit range of a call against the plan's units
+int jk_check_range(const JkPlan& pl, int64_t unit_begin, int64_t unit_end) {
+    SC_REQUIRE(0 <= unit_begin && unit_begin < unit_end && unit_end <= pl.n_units, "unit range outside the spectra's units");
+    return SC_OK;
+}
+
+// What the three entry points share once their own checks have passed and their own fields of *p are filled: the splits and their
+// workspace, the geometry, the launch and the fold of the splits.  planes: see jk_geometry; zero: clear what the kernel writes into
+// first (a record of totals).
+template <typename T2, typename Args>
+int jk_launch(void (*kernel)(const T2*, Args), const JkPlan& pl, Args* p, const void* d_X, uint32_t planes, int64_t unit_begin,
+              int64_t unit_end, const JkFold& fold, bool zero, double* d_out, void* d_workspace, int64_t workspace_bytes,
+              void* stream) {
+    int64_t per, n_splits;
+    jk_splits(pl, unit_end - unit_begin, &per, &n_splits);
+    SC_REQUIRE(per * pl.g < (int64_t)1 << 31, "too many observation rows per workgroup");
+    const int64_t out_bytes = pl.out_doubles * (int64_t)sizeof(double);
+    if (n_splits > 1) SC_REQUIRE(d_workspace && workspace_bytes >= n_splits * out_bytes, "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    p->geo = jk_geometry(pl, planes, unit_begin, unit_end, per, n_splits > 1 ? (double*)d_workspace : d_out);
+    if (zero) SC_CHECK_HIP(hipMemsetAsync(p->geo.out, 0, (size_t)(n_splits * out_bytes), st));
+    const dim3 grid((unsigned)(pl.n_bins * pl.n_tp), (unsigned)n_splits);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, (const T2*)d_X, *p);
+    SC_CHECK_HIP(hipGetLastError());
+    if (n_splits > 1) {
+        hipLaunchKernelGGL(jk_fold, dim3((unsigned)((pl.out_doubles + 255) / 256)), dim3(256), 0, st, (const double*)d_workspace,
+                           (int)n_splits, fold, d_out);
+        SC_CHECK_HIP(hipGetLastError());
+    }
+    return SC_OK;
+}
+
 template <typename T, typename T2>
 int jk_run(const void* d_X, const sc_spectra_desc* desc, const void* d_total, uint32_t planes, uint32_t measures, int over,
            int64_t unit_begin, int64_t unit_end, int64_t n_units_total, double* d_out, void* d_workspace, int64_t workspace_bytes,
@@ -651,40 +668,17 @@ int jk_run(const void* d_X, const sc_spectra_desc* desc, const void* d_total, ui
     if (rc != SC_OK) return rc;
     SC_REQUIRE(d_X && d_total && d_out, "NULL argument");
     SC_REQUIRE(planes & SC_PLANE_CSM, "the total record must contain SC_PLANE_CSM");
-    SC_REQUIRE(0 <= unit_begin && unit_begin < unit_end && unit_end <= pl.n_units, "unit range outside the spectra's units");
+    if ((rc = jk_check_range(pl, unit_begin, unit_end)) != SC_OK) return rc;
     SC_REQUIRE(n_units_total >= 2 && n_units_total >= unit_end - unit_begin, "a jackknife needs at least two units");
-    int64_t per, n_splits;
-    jk_splits(pl, unit_end - unit_begin, &per, &n_splits);
-    SC_REQUIRE(per * pl.g < (int64_t)1 << 31, "too many observation rows per workgroup");
-    if (n_splits > 1)
-        SC_REQUIRE(d_workspace && workspace_bytes >= n_splits * pl.out_doubles * (int64_t)sizeof(double), "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
     JkArgs p = {};
-    p.a = pl.a;
     p.total = sc_rec(d_total, planes);
-    p.NB16 = sc_n_blocks(pl.a.C);
-    p.n_tiles16 = sc_n_tiles(p.NB16);
     p.p_csm = sc_plane_offset(planes, SC_PLANE_CSM);
-    p.rec_stride = (int64_t)sc_plane_count(planes) * p.n_tiles16 * SC_TILE_ELEMS;
-    p.n_freq = pl.a.F; p.NT = pl.NT; p.n_tp = pl.n_tp;
-    p.over = over; p.g = (int)pl.g; p.q_tapers = pl.q_tapers;
-    p.unit_begin = unit_begin; p.unit_end = unit_end; p.units_per_split = per;
     p.n_total = (double)n_units_total;
     p.ln_ratio = log((double)n_units_total / (double)(n_units_total - 1));
     p.measures = measures;
-    p.n_bins = pl.n_bins;
     for (int m = 0; m < 3; ++m) p.off[m] = pl.off[m];
-    p.out_doubles = pl.out_doubles;
-    p.out = n_splits > 1 ? (double*)d_workspace : d_out;
-    const dim3 grid((unsigned)(pl.n_bins * pl.n_tp), (unsigned)n_splits);
-    hipLaunchKernelGGL((jk_kernel<T, T2>), grid, dim3(256), 0, st, (const T2*)d_X, p);
-    SC_CHECK_HIP(hipGetLastError());
-    if (n_splits > 1) {
-        hipLaunchKernelGGL(jk_fold, dim3((unsigned)((pl.out_doubles + 255) / 256)), dim3(256), 0, st, (const double*)d_workspace,
-                           (int)n_splits, jk_fold_blocks(pl, false), d_out);
-        SC_CHECK_HIP(hipGetLastError());
-    }
-    return SC_OK;
+    return jk_launch(jk_kernel<T, T2>, pl, &p, d_X, planes, unit_begin, unit_end, jk_fold_blocks(pl, false), false, d_out,
+                     d_workspace, workspace_bytes, stream);
 }
 
 // planes of the total record a mask of phase-lag measures reads
@@ -694,6 +688,14 @@ uint32_t jk_phase_planes(uint32_t measures) {
     if (measures & SC_JACKKNIFE_PHASE_WPLI) need |= SC_PLANE_CSM | SC_PLANE_ABS_IM;
     if (measures & SC_JACKKNIFE_PHASE_DEBIASED_WPLI2) need |= SC_PLANE_CSM | SC_PLANE_ABS_IM | SC_PLANE_IM_SQ;
     return need;
+}
+
+// the planes `use` of a record with the planes `planes`, where the phase-lag kernels find them
+void jk_phase_plane_indices(JkPhaseArgs* p, uint32_t planes, uint32_t use) {
+    p->p_im = (use & SC_PLANE_CSM) ? sc_plane_offset(planes, SC_PLANE_CSM) + 1 : -1;
+    p->p_abs = (use & SC_PLANE_ABS_IM) ? sc_plane_offset(planes, SC_PLANE_ABS_IM) : -1;
+    p->p_sq = (use & SC_PLANE_IM_SQ) ? sc_plane_offset(planes, SC_PLANE_IM_SQ) : -1;
+    p->p_sign = (use & SC_PLANE_SIGN_IM) ? sc_plane_offset(planes, SC_PLANE_SIGN_IM) : -1;
 }
 
 template <typename T, typename T2>
@@ -709,45 +711,19 @@ int jk_phase_run(const void* d_X, const sc_spectra_desc* desc, const void* d_tot
     SC_REQUIRE((planes & need) == need,
                "the total record lacks a plane of a requested measure (PLI, debiased PLI^2: SC_PLANE_SIGN_IM; wPLI: SC_PLANE_CSM | "
                "_ABS_IM; debiased wPLI^2: SC_PLANE_CSM | _ABS_IM | _IM_SQ)");
-    SC_REQUIRE(0 <= unit_begin && unit_begin < unit_end && unit_end <= pl.n_units, "unit range outside the spectra's units");
+    if ((rc = jk_check_range(pl, unit_begin, unit_end)) != SC_OK) return rc;
     SC_REQUIRE(n_units_total >= 2 && n_units_total >= unit_end - unit_begin, "a jackknife needs at least two units");
     if (measures & (SC_JACKKNIFE_PHASE_DEBIASED_PLI2 | SC_JACKKNIFE_PHASE_DEBIASED_WPLI2))
         SC_REQUIRE((n_units_total - 1) * pl.g >= 2, "a debiased estimate needs at least two observations in a delete-one set");
-    int64_t per, n_splits;
-    jk_splits(pl, unit_end - unit_begin, &per, &n_splits);
-    SC_REQUIRE(per * pl.g < (int64_t)1 << 31, "too many observation rows per workgroup");
-    if (n_splits > 1)
-        SC_REQUIRE(d_workspace && workspace_bytes >= n_splits * pl.out_doubles * (int64_t)sizeof(double), "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
     JkPhaseArgs p = {};
-    p.a = pl.a;
     p.total = sc_rec(d_total, planes);
-    p.NB16 = sc_n_blocks(pl.a.C);
-    p.n_tiles16 = sc_n_tiles(p.NB16);
-    p.p_im = (need & SC_PLANE_CSM) ? sc_plane_offset(planes, SC_PLANE_CSM) + 1 : -1;
-    p.p_abs = (need & SC_PLANE_ABS_IM) ? sc_plane_offset(planes, SC_PLANE_ABS_IM) : -1;
-    p.p_sq = (need & SC_PLANE_IM_SQ) ? sc_plane_offset(planes, SC_PLANE_IM_SQ) : -1;
-    p.p_sign = (need & SC_PLANE_SIGN_IM) ? sc_plane_offset(planes, SC_PLANE_SIGN_IM) : -1;
-    p.rec_stride = (int64_t)sc_plane_count(planes) * p.n_tiles16 * SC_TILE_ELEMS;
-    p.n_freq = pl.a.F; p.NT = pl.NT; p.n_tp = pl.n_tp;
-    p.over = over; p.g = (int)pl.g; p.q_tapers = pl.q_tapers;
-    p.unit_begin = unit_begin; p.unit_end = unit_end; p.units_per_split = per;
+    jk_phase_plane_indices(&p, planes, need);
     p.n_full = (double)n_units_total * (double)pl.g;
     p.n_del = (double)(n_units_total - 1) * (double)pl.g;
     p.measures = measures;
-    p.n_bins = pl.n_bins;
     for (int m = 0; m < JK_MAX_BLOCKS; ++m) p.off[m] = pl.off[m];
-    p.out_doubles = pl.out_doubles;
-    p.out = n_splits > 1 ? (double*)d_workspace : d_out;
-    const dim3 grid((unsigned)(pl.n_bins * pl.n_tp), (unsigned)n_splits);
-    hipLaunchKernelGGL((jk_phase_kernel<T, T2>), grid, dim3(256), 0, st, (const T2*)d_X, p);
-    SC_CHECK_HIP(hipGetLastError());
-    if (n_splits > 1) {
-        hipLaunchKernelGGL(jk_fold, dim3((unsigned)((pl.out_doubles + 255) / 256)), dim3(256), 0, st, (const double*)d_workspace,
-                           (int)n_splits, jk_fold_blocks(pl, true), d_out);
-        SC_CHECK_HIP(hipGetLastError());
-    }
-    return SC_OK;
+    return jk_launch(jk_phase_kernel<T, T2>, pl, &p, d_X, planes, unit_begin, unit_end, jk_fold_blocks(pl, true), false, d_out,
+                     d_workspace, workspace_bytes, stream);
 }
 
 constexpr uint32_t JK_PHASE_PLANES_ALL = SC_PLANE_CSM | SC_PLANE_ABS_IM | SC_PLANE_IM_SQ | SC_PLANE_SIGN_IM;
@@ -771,40 +747,22 @@ int jk_phase_totals_run(const void* d_X, const sc_spectra_desc* desc, uint32_t p
     if (rc != SC_OK) return rc;
     planes &= ~SC_RECORD_F64;
     SC_REQUIRE(d_X && d_record, "NULL argument");
-    SC_REQUIRE(0 <= unit_begin && unit_begin < unit_end && unit_end <= pl.n_units, "unit range outside the spectra's units");
-    int64_t per, n_splits;
-    jk_splits(pl, unit_end - unit_begin, &per, &n_splits);
-    SC_REQUIRE(per * pl.g < (int64_t)1 << 31, "too many observation rows per workgroup");
-    const int64_t rec_bytes = pl.out_doubles * (int64_t)sizeof(double);
-    if (n_splits > 1) SC_REQUIRE(d_workspace && workspace_bytes >= n_splits * rec_bytes, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
+    if ((rc = jk_check_range(pl, unit_begin, unit_end)) != SC_OK) return rc;
     JkPhaseArgs p = {};
-    p.a = pl.a;
-    p.NB16 = sc_n_blocks(pl.a.C);
-    p.n_tiles16 = sc_n_tiles(p.NB16);
-    p.p_im = (planes & SC_PLANE_CSM) ? sc_plane_offset(planes, SC_PLANE_CSM) + 1 : -1;
-    p.p_abs = (planes & SC_PLANE_ABS_IM) ? sc_plane_offset(planes, SC_PLANE_ABS_IM) : -1;
-    p.p_sq = (planes & SC_PLANE_IM_SQ) ? sc_plane_offset(planes, SC_PLANE_IM_SQ) : -1;
-    p.p_sign = (planes & SC_PLANE_SIGN_IM) ? sc_plane_offset(planes, SC_PLANE_SIGN_IM) : -1;
-    p.rec_stride = (int64_t)sc_plane_count(planes) * p.n_tiles16 * SC_TILE_ELEMS;
-    p.n_freq = pl.a.F; p.NT = pl.NT; p.n_tp = pl.n_tp;
-    p.over = over; p.g = (int)pl.g; p.q_tapers = pl.q_tapers;
-    p.unit_begin = unit_begin; p.unit_end = unit_end; p.units_per_split = per;
-    p.n_bins = pl.n_bins;
-    p.out_doubles = pl.out_doubles;
-    p.out = n_splits > 1 ? (double*)d_workspace : d_record;
-    // the entries no thread owns (the real plane, the diagonal and what lies below it in a diagonal tile, tile padding) are 0
-    SC_CHECK_HIP(hipMemsetAsync(p.out, 0, (size_t)(n_splits * rec_bytes), st));
-    const dim3 grid((unsigned)(pl.n_bins * pl.n_tp), (unsigned)n_splits);
-    hipLaunchKernelGGL((jk_phase_totals_kernel<T, T2>), grid, dim3(256), 0, st, (const T2*)d_X, p);
-    SC_CHECK_HIP(hipGetLastError());
-    if (n_splits > 1) {
-        JkFold fold = {};
-        fold.out_doubles = pl.out_doubles;              // (no theta blocks: every double is a sum over the splits)
-        hipLaunchKernelGGL(jk_fold, dim3((unsigned)((pl.out_doubles + 255) / 256)), dim3(256), 0, st, (const double*)d_workspace,
-                           (int)n_splits, fold, d_record);
-        SC_CHECK_HIP(hipGetLastError());
-    }
+    jk_phase_plane_indices(&p, planes, planes);
+    JkFold fold = {};
+    fold.out_doubles = pl.out_doubles;                  // (no theta blocks: every double is a sum over the splits)
+    // zero: the entries no thread owns (the real plane, the diagonal and what lies below it in a diagonal tile, tile padding) are 0
+    return jk_launch(jk_phase_totals_kernel<T, T2>, pl, &p, d_X, planes, unit_begin, unit_end, fold, true, d_record, d_workspace,
+                     workspace_bytes, stream);
+}
+
+int jk_layout(int plan_rc, const JkPlan& pl, int64_t* n_bins, int64_t* n_units, int64_t* unit_size, int64_t* out_doubles) {
+    if (plan_rc != SC_OK) return plan_rc;
+    if (n_bins) *n_bins = pl.n_bins;
+    if (n_units) *n_units = pl.n_units;
+    if (unit_size) *unit_size = pl.g;
+    if (out_doubles) *out_doubles = pl.out_doubles;
     return SC_OK;
 }
 
@@ -813,22 +771,13 @@ int jk_phase_totals_run(const void* d_X, const sc_spectra_desc* desc, uint32_t p
 extern "C" int sc_jackknife_layout(const sc_spectra_desc* desc, uint32_t measures, int over, int64_t* n_bins, int64_t* n_units,
                                    int64_t* unit_size, int64_t* out_doubles) {
     JkPlan pl;
-    const int rc = jk_plan(desc, measures, over, &pl);
-    if (rc != SC_OK) return rc;
-    if (n_bins) *n_bins = pl.n_bins;
-    if (n_units) *n_units = pl.n_units;
-    if (unit_size) *unit_size = pl.g;
-    if (out_doubles) *out_doubles = pl.out_doubles;
-    return SC_OK;
+    return jk_layout(jk_plan(desc, measures, over, &pl), pl, n_bins, n_units, unit_size, out_doubles);
 }
 
 extern "C" int64_t sc_jackknife_workspace_bytes(const sc_spectra_desc* desc, uint32_t measures, int over, int64_t unit_begin,
                                                 int64_t unit_end) {
     JkPlan pl;
-    if (jk_plan(desc, measures, over, &pl) != SC_OK || unit_end <= unit_begin) return 0;
-    int64_t per, n_splits;
-    jk_splits(pl, unit_end - unit_begin, &per, &n_splits);
-    return n_splits > 1 ? n_splits * pl.out_doubles * (int64_t)sizeof(double) : 0;
+    return jk_workspace_bytes(jk_plan(desc, measures, over, &pl), pl, unit_begin, unit_end);
 }
 
 extern "C" int sc_jackknife_f32(const void* d_X, const sc_spectra_desc* desc, const void* d_total, uint32_t planes,
@@ -848,22 +797,13 @@ extern "C" int sc_jackknife_f64(const void* d_X, const sc_spectra_desc* desc, co
 extern "C" int sc_jackknife_phase_layout(const sc_spectra_desc* desc, uint32_t measures, int over, int64_t* n_bins,
                                          int64_t* n_units, int64_t* unit_size, int64_t* out_doubles) {
     JkPlan pl;
-    const int rc = jk_plan(desc, measures, over, &pl, true);
-    if (rc != SC_OK) return rc;
-    if (n_bins) *n_bins = pl.n_bins;
-    if (n_units) *n_units = pl.n_units;
-    if (unit_size) *unit_size = pl.g;
-    if (out_doubles) *out_doubles = pl.out_doubles;
-    return SC_OK;
+    return jk_layout(jk_plan(desc, measures, over, &pl, true), pl, n_bins, n_units, unit_size, out_doubles);
 }
 
 extern "C" int64_t sc_jackknife_phase_workspace_bytes(const sc_spectra_desc* desc, uint32_t measures, int over,
                                                       int64_t unit_begin, int64_t unit_end) {
     JkPlan pl;
-    if (jk_plan(desc, measures, over, &pl, true) != SC_OK || unit_end <= unit_begin) return 0;
-    int64_t per, n_splits;
-    jk_splits(pl, unit_end - unit_begin, &per, &n_splits);
-    return n_splits > 1 ? n_splits * pl.out_doubles * (int64_t)sizeof(double) : 0;
+    return jk_workspace_bytes(jk_plan(desc, measures, over, &pl, true), pl, unit_begin, unit_end);
 }
 
 extern "C" int sc_jackknife_phase_f32(const void* d_X, const sc_spectra_desc* desc, const void* d_total, uint32_t planes,
@@ -883,10 +823,7 @@ extern "C" int sc_jackknife_phase_f64(const void* d_X, const sc_spectra_desc* de
 extern "C" int64_t sc_jackknife_phase_totals_workspace_bytes(const sc_spectra_desc* desc, uint32_t planes, int over,
                                                              int64_t unit_begin, int64_t unit_end) {
     JkPlan pl;
-    if (jk_totals_plan(desc, planes, over, &pl) != SC_OK || unit_end <= unit_begin) return 0;
-    int64_t per, n_splits;
-    jk_splits(pl, unit_end - unit_begin, &per, &n_splits);
-    return n_splits > 1 ? n_splits * pl.out_doubles * (int64_t)sizeof(double) : 0;
+    return jk_workspace_bytes(jk_totals_plan(desc, planes, over, &pl), pl, unit_begin, unit_end);
 }
 
 extern "C" int sc_jackknife_phase_totals_f32(const void* d_X, const sc_spectra_desc* desc, uint32_t planes, int over,
