@@ -21,7 +21,7 @@
 #include <math.h>
 #include <vector>
 #include "sc_common.h"
-
+#include "sc_workspace.h"
 
 #define BW_LDS_BLOCK 64          // blocks of up to this many signals are factored in LDS by the epilogue, larger ones in place
 #define BW_LDS_NULLSPACE 64      // problems of up to this many signals keep Psi0 in LDS in bw_nullspace
@@ -176,30 +176,25 @@ __global__ void __launch_bounds__(256) bw_epilogue(cd* __restrict__ S2, const cd
     }
 }
 
-
-// Workspace of one call with P = n_pairs G problems of m signals:
-//   S2 and Psi [P][N][m][m] (complex128); then either the factorisation's own workspace or, once it has returned,
-//   R [P][m][m], Y [P][F][m][m] (complex128) and bw_nullspace's Psi0 beyond BW_LDS_NULLSPACE signals (double [P][m][m])
-static size_t bw_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-static int bw_check_m(int64_t m) {
+// The workspace of one call with P = n_pairs G problems of m signals (ws_blockwise of sc_workspace.h) on d_work, or counted only
+static int bw_layout(void* d_work, int64_t P, int64_t m, int64_t N, WsBlockwise<cd>* k, size_t* need) {
     if (m < 2 || m > sc_mvar_max_signals()) {
         sc_set_error("blockwise Granger: 2 <= signals of a block pair <= %d (got %lld)", sc_mvar_max_signals(), (long long)m);
         return SC_EUNSUPPORTED;
     }
+    size_t mvar = 0;
+    const int rc = sc_mvar_workspace_bytes(P, m, N, &mvar);
+    if (rc != SC_OK) return rc;
+    ScCarver w(d_work);
+    *k = ws_blockwise<cd>(w, P, m, N, mvar);
+    *need = w.used;
     return SC_OK;
 }
 
 extern "C" int sc_blockwise_granger_workspace_bytes(int64_t n_groups, int64_t m, int64_t N, int64_t n_pairs, size_t* bytes) {
     SC_REQUIRE(bytes && n_groups >= 1 && n_pairs >= 1 && N >= 2, "bad workspace query");
-    int rc = bw_check_m(m);
-    if (rc != SC_OK) return rc;
-    const size_t P = (size_t)n_groups * (size_t)n_pairs, E = (size_t)m * m, F = (size_t)N / 2 + 1;
-    size_t mvar = 0;
-    if ((rc = sc_mvar_workspace_bytes((int64_t)P, m, N, &mvar)) != SC_OK) return rc;
-    const size_t epi = bw_align(P * E * sizeof(cd)) + bw_align(P * F * E * sizeof(cd)) + bw_align(P * E * sizeof(double));
-    *bytes = 2 * bw_align(P * (size_t)N * E * sizeof(cd)) + bw_align(mvar > epi ? mvar : epi);
-    return SC_OK;
+    WsBlockwise<cd> k;
+    return bw_layout(nullptr, n_groups * n_pairs, m, N, &k, bytes);
 }
 
 extern "C" int sc_blockwise_granger_f64(const void* d_accum, const void* d_S, int64_t n_groups, int64_t n_freq_accum, int64_t N,
@@ -212,10 +207,10 @@ extern "C" int sc_blockwise_granger_f64(const void* d_accum, const void* d_S, in
     SC_REQUIRE(d_members && d_split && d_cell && d_work && d_out && d_n_iter && d_status, "NULL argument");
     SC_REQUIRE(n_groups >= 1 && n_pairs >= 1 && n_groups * n_pairs <= 65535 && N >= 2 && N <= 1 << 24 && C >= 1 && n_blocks >= 2,
                "bad problem size");
-    int rc = bw_check_m(m);
-    if (rc != SC_OK) return rc;
+    WsBlockwise<cd> k;
     size_t need = 0;
-    if ((rc = sc_blockwise_granger_workspace_bytes(n_groups, m, N, n_pairs, &need)) != SC_OK) return rc;
+    int rc = bw_layout(d_work, n_groups * n_pairs, m, N, &k, &need);
+    if (rc != SC_OK) return rc;
     SC_REQUIRE(work_bytes >= need, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     // the index lists address the records and the output: read back and checked before any launch reads them
@@ -235,12 +230,7 @@ extern "C" int sc_blockwise_granger_f64(const void* d_accum, const void* d_S, in
     }
     for (int32_t s : members) SC_REQUIRE(s >= 0 && s < C, "member signal outside [0, n_signals)");
     const int64_t G = n_groups, P = G * n_pairs, F = N / 2 + 1, E = m * m;
-    char* w = (char*)d_work;
-    cd* S2 = (cd*)w; w += bw_align((size_t)P * N * E * sizeof(cd));
-    cd* Psi = (cd*)w; w += bw_align((size_t)P * N * E * sizeof(cd));
-    char* tail = w;
-    size_t mvar = 0;
-    sc_mvar_workspace_bytes(P, m, N, &mvar);
+    cd *S2 = k.S2, *Psi = k.Psi, *R = k.R, *Y = k.Y;
     if (!(flags & SC_BLOCKWISE_KEEP_OUTPUT)) sc_internal_fill_nan(d_out, G * F * n_blocks * n_blocks, st);
     BwDims d = {};
     d.G = G; d.N = N; d.C = (int)C; d.m = (int)m;
@@ -249,16 +239,13 @@ extern "C" int sc_blockwise_granger_f64(const void* d_accum, const void* d_S, in
     hipLaunchKernelGGL(bw_gather, gridG, dim3(256), 0, st, sc_rec(d_accum, planes), (const cd*)d_S, d, d_members, S2);
     SC_CHECK_HIP(hipGetLastError());
     // factors of the pair spectra: the full factorisation's own path over the P problems
-    if ((rc = sc_mvar_factor_f64(nullptr, S2, P, 0, N, m, 0, 1, tol, max_iter, tail, mvar, Psi, d_n_iter, d_status, h_summary,
+    if ((rc = sc_mvar_factor_f64(nullptr, S2, P, 0, N, m, 0, 1, tol, max_iter, k.mvar, k.mvar_bytes, Psi, d_n_iter, d_status, h_summary,
                                  stream)) != SC_OK)
         return rc;
-    // (the factorisation has synchronised the stream: its workspace is free again)
-    cd* R = (cd*)tail;
-    cd* Y = (cd*)(tail + bw_align((size_t)P * E * sizeof(cd)));
-    double* psi0 = (double*)((char*)Y + bw_align((size_t)P * F * E * sizeof(cd)));
+    // (the factorisation has synchronised the stream: its workspace is free again and holds R, Y and psi0 from here on)
     const int ns_lds = m <= BW_LDS_NULLSPACE;
     hipLaunchKernelGGL(bw_nullspace, dim3((unsigned)P), dim3(256), ns_lds ? (size_t)E * sizeof(double) : 0, st, (const cd*)Psi, d_split,
-                       G, N, (int)m, ns_lds, psi0, R);
+                       G, N, (int)m, ns_lds, k.psi0, R);
     SC_CHECK_HIP(hipGetLastError());
     // Y = Psi(f) R on the non-negative bins
     if ((rc = sc_internal_mvar_gemm(m, P, F, Psi, N * E, E, R, E, 0, Y, F * E, E, st)) != SC_OK) return rc;
@@ -267,9 +254,5 @@ extern "C" int sc_blockwise_granger_f64(const void* d_accum, const void* d_S, in
     SC_CHECK_HIP(hipFuncSetAttribute((const void*)bw_epilogue, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(bw_epilogue, dim3((unsigned)F, (unsigned)P, 2), dim3(256), lds, st, S2, (const cd*)Y, d_split, d_cell, G, N, F,
                        (int)m, n_blocks, lds_max, d_out);
-    if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
-        sc_set_error("blockwise Granger epilogue failed: %s", hipGetErrorString(hipGetLastError()));
-        return SC_EHIP;
-    }
-    return SC_OK;
+    return sc_sync_or_report(st, "blockwise Granger epilogue");
 }

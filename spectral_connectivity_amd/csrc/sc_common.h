@@ -104,6 +104,13 @@ struct ScTimed {
         }                                                                         \
     } while (0)
 
+// The tail of an entry point: waits for the stream; a failed wait or launch before it is reported as "<what> failed: <error>".
+inline int sc_sync_or_report(hipStream_t st, const char* what) {
+    if (hipStreamSynchronize(st) == hipSuccess && hipGetLastError() == hipSuccess) return SC_OK;
+    sc_set_error("%s failed: %s", what, hipGetErrorString(hipGetLastError()));
+    return SC_EHIP;
+}
+
 // Accumulator records as their consumers see them: float elements (f32 engine) or double elements (f64 engine,
 // SC_RECORD_F64 set in `planes`).  Pointer arithmetic in elements, loads widened to double.
 struct ScRec {

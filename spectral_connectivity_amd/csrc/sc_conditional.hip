@@ -20,7 +20,7 @@
 // (SC_CONDITIONAL_KEEP_OUTPUT), like the pair lists of sc_granger_pairwise_f64.
 #include <math.h>
 #include "sc_common.h"
-
+#include "sc_workspace.h"
 
 struct CgDims {
     int64_t G, N;        // groups, two-sided length
@@ -111,28 +111,25 @@ __global__ void __launch_bounds__(256) cg_epilogue(const cd* __restrict__ K, con
     }
 }
 
-
-// Workspace of one call with D dropped signals:
-//   fixed  Psi0^T [G][C][C] and M [G][F][C][C] (complex128), one double 0 (the Tikhonov term of the small inverse)
-//   chunk  S_red and Phi [D G][N][C-1][C-1] (complex128); then either the factorisation's own workspace or, once it has returned,
-//          Phi0 [D G][C-1][C-1], K and the blocked inverse's scratch [D G][N][C-1][C-1] at the first F bins (Phi^-1 reuses S_red)
-static size_t cg_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-extern "C" int sc_conditional_granger_workspace_bytes(int64_t n_groups, int64_t C, int64_t N, int64_t n_dropped, size_t* bytes) {
-    SC_REQUIRE(bytes && n_groups >= 1 && n_dropped >= 1 && N >= 2, "bad workspace query");
+// The workspace of one call with D dropped signals (ws_conditional of sc_workspace.h) on d_work, or counted only (d_work NULL)
+static int cg_layout(void* d_work, int64_t G, int64_t C, int64_t N, int64_t D, WsConditional<cd>* k, size_t* need) {
     if (C < 2 || C > sc_mvar_max_signals()) {
         sc_set_error("conditional Granger: 2 <= n_signals <= %d (got %lld)", sc_mvar_max_signals(), (long long)C);
         return SC_EUNSUPPORTED;
     }
-    const size_t G = (size_t)n_groups, P = G * (size_t)n_dropped, E = (size_t)C * C, Er = (size_t)(C - 1) * (C - 1);
-    const size_t F = (size_t)N / 2 + 1;
     size_t mvar = 0;
-    int rc = sc_mvar_workspace_bytes((int64_t)P, C - 1, N, &mvar);
+    const int rc = sc_mvar_workspace_bytes(G * D, C - 1, N, &mvar);
     if (rc != SC_OK) return rc;
-    const size_t epi = cg_align(P * Er * sizeof(cd)) + 2 * cg_align(P * (size_t)N * Er * sizeof(cd));
-    *bytes = cg_align(G * E * sizeof(cd)) + cg_align(G * F * E * sizeof(cd)) + 256 + 2 * cg_align(P * (size_t)N * Er * sizeof(cd)) +
-             cg_align(mvar > epi ? mvar : epi);
+    ScCarver w(d_work);
+    *k = ws_conditional<cd>(w, G, C, N, D, mvar);
+    *need = w.used;
     return SC_OK;
+}
+
+extern "C" int sc_conditional_granger_workspace_bytes(int64_t n_groups, int64_t C, int64_t N, int64_t n_dropped, size_t* bytes) {
+    SC_REQUIRE(bytes && n_groups >= 1 && n_dropped >= 1 && N >= 2, "bad workspace query");
+    WsConditional<cd> k;
+    return cg_layout(nullptr, n_groups, C, N, n_dropped, &k, bytes);
 }
 
 extern "C" int sc_conditional_granger_f64(const void* d_accum, const void* d_S, int64_t n_groups, int64_t n_freq_accum, int64_t N,
@@ -143,28 +140,17 @@ extern "C" int sc_conditional_granger_f64(const void* d_accum, const void* d_S, 
     SC_REQUIRE((d_accum != nullptr) != (d_S != nullptr), "pass exactly one of d_accum and d_S");
     SC_REQUIRE(d_G && d_dropped && d_work && d_out && d_n_iter && d_status, "NULL argument");
     SC_REQUIRE(n_groups >= 1 && n_dropped >= 1 && n_groups * n_dropped <= 65535 && N >= 2 && N <= 1 << 24, "bad problem size");
-    if (C < 2 || C > sc_mvar_max_signals()) {
-        sc_set_error("conditional Granger: 2 <= n_signals <= %d (got %lld)", sc_mvar_max_signals(), (long long)C);
-        return SC_EUNSUPPORTED;
-    }
+    WsConditional<cd> k;
     size_t need = 0;
-    int rc = sc_conditional_granger_workspace_bytes(n_groups, C, N, n_dropped, &need);
+    int rc = cg_layout(d_work, n_groups, C, N, n_dropped, &k, &need);
     if (rc != SC_OK) return rc;
     SC_REQUIRE(work_bytes >= need, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const int64_t G = n_groups, P = G * n_dropped, F = N / 2 + 1, Cr = C - 1;
     const int64_t E = C * C, Er = Cr * Cr;
-    char* w = (char*)d_work;
-    cd* Psi0T = (cd*)w; w += cg_align((size_t)G * E * sizeof(cd));
-    cd* M = (cd*)w; w += cg_align((size_t)G * F * E * sizeof(cd));
-    double* zero = (double*)w; w += 256;
-    cd* Sred = (cd*)w; w += cg_align((size_t)P * N * Er * sizeof(cd));
-    cd* Phi = (cd*)w; w += cg_align((size_t)P * N * Er * sizeof(cd));
-    char* tail = w;
-    size_t mvar = 0;
-    sc_mvar_workspace_bytes(P, Cr, N, &mvar);
+    cd *Psi0T = k.Psi0T, *M = k.M, *Sred = k.Sred, *Phi = k.Phi, *Phi0 = k.Phi0, *K = k.K;
     if (!(flags & SC_CONDITIONAL_KEEP_OUTPUT)) sc_internal_fill_nan(d_out, G * F * E, st);
-    SC_CHECK_HIP(hipMemsetAsync(zero, 0, 256, st));
+    SC_CHECK_HIP(hipMemsetAsync(k.zero, 0, 256, st));
     // reduced spectra
     CgDims d = {};
     d.G = G; d.N = N; d.C = (int)C;
@@ -173,13 +159,10 @@ extern "C" int sc_conditional_granger_f64(const void* d_accum, const void* d_S, 
     hipLaunchKernelGGL(cg_gather, gridG, dim3(256), 0, st, sc_rec(d_accum, planes), (const cd*)d_S, d, d_dropped, Sred);
     SC_CHECK_HIP(hipGetLastError());
     // reduced factors: the full factorisation's own path over the D G problems
-    if ((rc = sc_mvar_factor_f64(nullptr, Sred, P, 0, N, Cr, 0, 1, tol, max_iter, tail, mvar, Phi, d_n_iter, d_status, h_summary,
+    if ((rc = sc_mvar_factor_f64(nullptr, Sred, P, 0, N, Cr, 0, 1, tol, max_iter, k.mvar, k.mvar_bytes, Phi, d_n_iter, d_status, h_summary,
                                  stream)) != SC_OK)
         return rc;
-    // (the factorisation has synchronised the stream: its workspace is free again)
-    cd* Phi0 = (cd*)tail;
-    cd* K = (cd*)(tail + cg_align((size_t)P * Er * sizeof(cd)));
-    cd* scratch = K + (size_t)P * N * Er;
+    // (the factorisation has synchronised the stream: its workspace is free again and holds Phi0, K and the scratch from here on)
     cd* Phinv = Sred;
     hipLaunchKernelGGL(cg_lag0, dim3((unsigned)((E + 255) / 256), (unsigned)G), dim3(256), 0, st, (const cd*)d_G, Psi0T, N, (int)C, 1);
     hipLaunchKernelGGL(cg_lag0, dim3((unsigned)((Er + 255) / 256), (unsigned)P), dim3(256), 0, st, (const cd*)Phi, Phi0, N, (int)Cr, 0);
@@ -187,13 +170,9 @@ extern "C" int sc_conditional_granger_f64(const void* d_accum, const void* d_S, 
     // M = Psi(f) Psi0^T on the non-negative bins
     if ((rc = sc_internal_mvar_gemm(C, G, F, d_G, N * E, E, Psi0T, E, 0, M, F * E, E, st)) != SC_OK) return rc;
     // Phi(f)^-1, then K = Phi0 Phi(f)^-1 (both at the bin slots of the factor's layout)
-    if ((rc = sc_internal_mvar_inverse(Cr, P, N, F, Phi, Phinv, scratch, zero, st)) != SC_OK) return rc;
+    if ((rc = sc_internal_mvar_inverse(Cr, P, N, F, Phi, Phinv, k.scratch, k.zero, st)) != SC_OK) return rc;
     if ((rc = sc_internal_mvar_gemm(Cr, P, F, Phi0, Er, 0, Phinv, N * Er, Er, K, N * Er, Er, st)) != SC_OK) return rc;
     hipLaunchKernelGGL(cg_epilogue, dim3((unsigned)F, (unsigned)G, (unsigned)n_dropped), dim3(256), 0, st, (const cd*)K, (const cd*)M,
                        (const cd*)Phi0, (const cd*)Psi0T, d_dropped, G, F, N, (int)C, d_out);
-    if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
-        sc_set_error("conditional Granger epilogue failed: %s", hipGetErrorString(hipGetLastError()));
-        return SC_EHIP;
-    }
-    return SC_OK;
+    return sc_sync_or_report(st, "conditional Granger epilogue");
 }

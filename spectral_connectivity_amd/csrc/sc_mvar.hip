@@ -25,6 +25,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "sc_wilson_loop.h"
+#include "sc_workspace.h"
 
 #define MV_CMAX 512          // <= 64: register-resident [G | S] elimination; 65 ... 128: explicit in-register inverse + matrix-
 #define MV_CSMALL 64         // core products; 129 ... 512: panel-blocked inverse in global memory + blocked products
@@ -1324,30 +1325,32 @@ static size_t mv_gj_lds(int Q) {
     const size_t CP = 16 * (size_t)Q;
     return (CP * CP + 2 * CP + 2 * CP + CP) * sizeof(cd) + 2 * CP * sizeof(unsigned) + 2 * CP * sizeof(int) + 64;
 }
+// (the four instantiations of a kernel over Q = 1 ... 4 blocks of 16 signals share a signature: picked by pointer)
 static int mv_launch_predict(int Q, dim3 grid, hipStream_t st, const cd* S, const cd* G, const int32_t* status, cd* A,
                              int64_t N, int C) {
     const size_t lds = mv_gj_lds(Q);
-#define MV_PRED(QQ)                                                                                          \
-    case QQ:                                                                                                 \
-        (void)hipFuncSetAttribute((const void*)m_predict_gj<QQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(m_predict_gj<QQ>, grid, dim3(256), lds, st, S, G, status, A, N, C);              \
-        break;
-    switch (Q) { MV_PRED(1) MV_PRED(2) MV_PRED(3) default: MV_PRED(4) }
-#undef MV_PRED
+    auto k = Q == 1 ? m_predict_gj<1> : Q == 2 ? m_predict_gj<2> : Q == 3 ? m_predict_gj<3> : m_predict_gj<4>;
+    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(k, grid, dim3(256), lds, st, S, G, status, A, N, C);
+    SC_CHECK_HIP(hipGetLastError());
+    return SC_OK;
+}
+// Out = (M + lam I)^-1 for n_mat contiguous C x C matrices of up to 64 signals
+static int mv_launch_inverse_gj(int C, unsigned n_mat, hipStream_t st, const cd* M, const double* lam, cd* Out) {
+    const int Q = (C + 15) / 16;
+    const size_t lds = mv_gj_lds(Q);
+    auto k = Q == 1 ? m_inverse_gj<1> : Q == 2 ? m_inverse_gj<2> : Q == 3 ? m_inverse_gj<3> : m_inverse_gj<4>;
+    SC_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k, dim3(n_mat), dim3(256), lds, st, M, lam, Out, C);
     SC_CHECK_HIP(hipGetLastError());
     return SC_OK;
 }
 static int mv_launch_update(int Q, dim3 grid, hipStream_t st, cd* G, const cd* Aplus, const int32_t* status, double* err,
                             int64_t N, int C) {
-    const size_t CP = 16 * (size_t)Q;
-    const size_t lds = 2 * CP * (CP + 1) * sizeof(cd);
-#define MV_UPD(QQ)                                                                                           \
-    case QQ:                                                                                                 \
-        (void)hipFuncSetAttribute((const void*)m_update_mfma<QQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(m_update_mfma<QQ>, grid, dim3(256), lds, st, G, Aplus, status, err, N, C);       \
-        break;
-    switch (Q) { MV_UPD(1) MV_UPD(2) MV_UPD(3) default: MV_UPD(4) }
-#undef MV_UPD
+    const size_t CP = 16 * (size_t)Q, lds = 2 * CP * (CP + 1) * sizeof(cd);
+    auto k = Q == 1 ? m_update_mfma<1> : Q == 2 ? m_update_mfma<2> : Q == 3 ? m_update_mfma<3> : m_update_mfma<4>;
+    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(k, grid, dim3(256), lds, st, G, Aplus, status, err, N, C);
     SC_CHECK_HIP(hipGetLastError());
     return SC_OK;
 }
@@ -1451,16 +1454,7 @@ extern "C" int sc_mvar_max_signals(void) { return MV_CMAX; }
 
 extern "C" int sc_mvar_workspace_bytes(int64_t n_groups, int64_t C, int64_t N, size_t* bytes) {
     SC_REQUIRE(bytes && n_groups >= 1 && C >= 1 && N >= 2, "bad workspace query");
-    const size_t E = (size_t)C * C, P = (size_t)n_groups, F = (size_t)N / 2 + 1;
-    // factor: S, G, A series (beyond 64 signals also G^-1 and G^-1 S); measures: H, A_mvar natural + small per-window arrays
-    const size_t n_big = C > mv_small_max() ? 5 : 3;
-    const size_t factor = n_big * P * E * (size_t)N * sizeof(cd) + P * 16 + P * E * 8 + 128 + (size_t)WILSON_HIST * 4;
-    // (beyond 128 signals: + the scratch of the blocked inverse, which also parks |H|^2 / |A|^2 for m_measure)
-    // (sq: one partial sum per (window, bin) and, before that, per (window, 256-element chunk of the matrix))
-    const size_t n_sq = (F > 16 ? F : 16) > (E + 255) / 256 ? (F > 16 ? F : 16) : (E + 255) / 256;
-    const size_t meas = (C > MV_CMID ? 3 : 2) * P * F * E * sizeof(cd) + P * E * 8 * 3 + P * n_sq * 8 +
-                        P * (size_t)C * 8 + P * 8 + 256;
-    *bytes = (factor > meas ? factor : meas) + 256;
+    *bytes = ws_mvar_bytes(n_groups, C, N, mv_small_max(), MV_CMID, WILSON_HIST);      // the larger of the two layouts of sc_workspace.h
     return SC_OK;
 }
 
@@ -1478,26 +1472,15 @@ extern "C" int sc_mvar_factor_f64(const void* d_accum, const void* d_S, int64_t 
                      MV_CMAX, (long long)C);
         return SC_EUNSUPPORTED;
     }
-    size_t need = 0;
-    sc_mvar_workspace_bytes(n_groups, C, N, &need);
+    const size_t need = ws_mvar_bytes(n_groups, C, N, mv_small_max(), MV_CMID, WILSON_HIST);
     SC_REQUIRE(work_bytes >= need, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const int64_t P = n_groups;
     const int E = (int)(C * C);
-    char* w = (char*)d_work;
-    cd* S = (cd*)w; w += (size_t)P * E * N * sizeof(cd);
-    cd* G = (cd*)w; w += (size_t)P * E * N * sizeof(cd);
-    cd* A = (cd*)w; w += (size_t)P * E * N * sizeof(cd);
+    ScCarver w(d_work);
+    const WsMvarFactor<cd> k = ws_mvar_factor<cd>(w, P, C, N, mv_small_max(), MV_CMID, WILSON_HIST);
+    cd *const S = k.S, *const A = k.A, *const Ginv = k.Ginv, *G = k.G, *T = k.T;          // (G and T swap beyond 128 signals)
     const bool big = C > mv_small_max();
-    cd* Ginv = nullptr;
-    cd* T = nullptr;
-    if (big) {
-        Ginv = (cd*)w; w += (size_t)P * E * N * sizeof(cd);
-        T = (cd*)w; w += (size_t)P * E * N * sizeof(cd);
-    }
-    double* err = (double*)w; w += (size_t)P * 8;
-    double* g0 = (double*)w; w += (size_t)P * E * 8;
-    int32_t* n_fallback = (int32_t*)w;          // 64 bytes, then the [WILSON_HIST] slots of the still-running counts
     const dim3 gridE((unsigned)((N + 255) / 256), (unsigned)(E < MV_GRID_Y ? E : MV_GRID_Y), (unsigned)P);
     const bool huge = C > MV_CMID;
     if (d_accum) {
@@ -1520,19 +1503,19 @@ extern "C" int sc_mvar_factor_f64(const void* d_accum, const void* d_S, int64_t 
     const MvMat Adesc = natA ? mv_natural(A, N, E) : mv_series(A, N, E);
     const int Q = (int)((C + 15) / 16);
     if (max_iter <= WILSON_HIST && !fused && (rc = fft.init((size_t)N, (size_t)E * P, st)) != SC_OK) return rc;
-    const WilsonCounters c = {err, d_n_iter, d_status, n_fallback, 64};
+    const WilsonCounters c = {k.err, d_n_iter, d_status, k.n_fallback, k.fallback_bytes};
     const WilsonLoopResult r = wilson_loop(c, P, tol, max_iter, st,
         [&]() -> int {
             // G0 = chol(Re ifft_n(S)[lag 0])^H broadcast over the bins (minimum_phase_decomposition.py:48-77)
-            if (big) hipLaunchKernelGGL(m_lag0_nat, dim3((unsigned)((E + 255) / 256), (unsigned)P), dim3(256), 0, st, S, g0, N, E);
-            else hipLaunchKernelGGL(m_lag0, dim3((unsigned)(((int64_t)P * E + 3) / 4)), dim3(256), 0, st, S, g0, N, (int64_t)P * E);
+            if (big) hipLaunchKernelGGL(m_lag0_nat, dim3((unsigned)((E + 255) / 256), (unsigned)P), dim3(256), 0, st, S, k.g0, N, E);
+            else hipLaunchKernelGGL(m_lag0, dim3((unsigned)(((int64_t)P * E + 3) / 4)), dim3(256), 0, st, S, k.g0, N, (int64_t)P * E);
             if (!huge) SC_CHECK_HIP(hipFuncSetAttribute((const void*)m_chol, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)E * 8)));
-            hipLaunchKernelGGL(m_chol, dim3((unsigned)P), dim3(256), huge ? (size_t)0 : (size_t)E * 8, st, g0, d_status, n_fallback, (int)C,
+            hipLaunchKernelGGL(m_chol, dim3((unsigned)P), dim3(256), huge ? (size_t)0 : (size_t)E * 8, st, k.g0, d_status, k.n_fallback, (int)C,
                                huge ? 1 : 0);
-            hipLaunchKernelGGL(m_restart_all, dim3(64), dim3(256), 0, st, g0, n_fallback, (int64_t)P, (int)C);
-            hipLaunchKernelGGL(m_restart_count, dim3(1), dim3(1), 0, st, n_fallback, (int32_t)P);
-            if (big) hipLaunchKernelGGL(m_fill_nat, dim3((unsigned)((E + 255) / 256), (unsigned)N, (unsigned)P), dim3(256), 0, st, g0, G, N, E);
-            else hipLaunchKernelGGL(m_fill, gridE, dim3(256), 0, st, g0, G, N, E);
+            hipLaunchKernelGGL(m_restart_all, dim3(64), dim3(256), 0, st, k.g0, k.n_fallback, (int64_t)P, (int)C);
+            hipLaunchKernelGGL(m_restart_count, dim3(1), dim3(1), 0, st, k.n_fallback, (int32_t)P);
+            if (big) hipLaunchKernelGGL(m_fill_nat, dim3((unsigned)((E + 255) / 256), (unsigned)N, (unsigned)P), dim3(256), 0, st, k.g0, G, N, E);
+            else hipLaunchKernelGGL(m_fill, gridE, dim3(256), 0, st, k.g0, G, N, E);
             return (int)SC_OK;
         },
         [&]() -> int {
@@ -1553,23 +1536,20 @@ extern "C" int sc_mvar_factor_f64(const void* d_accum, const void* d_S, int64_t 
             if (rcs != SC_OK) return rcs;
             if (huge) {         // the blocked product cannot run in place: G A+ into T (frozen windows copied), then swap
                 if ((rcs = mv_launch_gemm(C, MV_GEMM_ERR, gridB, st, mv_natural(G, N, E), Adesc, mv_natural(T, N, E),
-                                          d_status, err)) != SC_OK) return rcs;
+                                          d_status, k.err)) != SC_OK) return rcs;
                 cd* t = G; G = T; T = t;
                 return (int)SC_OK;
             }
-            if (big) return mv_launch_gemm(C, MV_GEMM_ERR, gridB, st, mv_natural(G, N, E), Adesc, mv_natural(G, N, E), d_status, err);
-            return mv_launch_update(Q, gridB, st, G, A, d_status, err, N, (int)C);
+            if (big) return mv_launch_gemm(C, MV_GEMM_ERR, gridB, st, mv_natural(G, N, E), Adesc, mv_natural(G, N, E), d_status, k.err);
+            return mv_launch_update(Q, gridB, st, G, A, d_status, k.err, N, (int)C);
         });
     if (r.rc != SC_OK) return r.rc;
     if (big) (void)hipMemcpyAsync(d_G, G, (size_t)P * E * N * sizeof(cd), hipMemcpyDeviceToDevice, st);
     else hipLaunchKernelGGL(m_to_natural, gridE, dim3(256), 0, st, G, (cd*)d_G, N, E);
-    if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
-        sc_set_error("Wilson factor copy-out failed: %s", hipGetErrorString(hipGetLastError()));
-        return SC_EHIP;
-    }
+    if ((rc = sc_sync_or_report(st, "Wilson factor copy-out")) != SC_OK) return rc;
     if (h_summary) {
         int fb = 0;
-        (void)hipMemcpy(&fb, n_fallback, 4, hipMemcpyDeviceToHost);      // the stream was synchronised just above
+        (void)hipMemcpy(&fb, k.n_fallback, 4, hipMemcpyDeviceToHost);      // the stream was synchronised just above
         h_summary[0] = r.iters; h_summary[1] = r.running; h_summary[2] = fb;
     }
     return SC_OK;
@@ -1588,25 +1568,16 @@ extern "C" int sc_mvar_measure_f64(const void* d_G, int64_t n_groups, int64_t N,
         sc_set_error("MVAR measures: n_signals <= %d (got %lld)", MV_CMAX, (long long)C);
         return SC_EUNSUPPORTED;
     }
-    size_t need = 0;
-    sc_mvar_workspace_bytes(n_groups, C, N, &need);
+    const size_t need = ws_mvar_bytes(n_groups, C, N, mv_small_max(), MV_CMID, WILSON_HIST);
     SC_REQUIRE(work_bytes >= need, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const int64_t P = n_groups, F = N / 2 + 1;
     const int E = (int)(C * C);
-    char* w = (char*)d_work;
-    cd* H = (cd*)w; w += (size_t)P * F * E * sizeof(cd);
-    cd* Amv = (cd*)w; w += (size_t)P * F * E * sizeof(cd);
-    double* h0 = (double*)w; w += (size_t)P * E * 8;
-    double* hinv = (double*)w; w += (size_t)P * E * 8;
-    double* sigma = (double*)w; w += (size_t)P * E * 8;
-    const size_t n_sq = (size_t)(F > 16 ? F : 16) > ((size_t)E + 255) / 256 ? (size_t)(F > 16 ? F : 16) : ((size_t)E + 255) / 256;
-    double* sq = (double*)w; w += (size_t)P * n_sq * 8;      // per (window, bin) or per (window, 256-element chunk)
-    double* tot = (double*)w; w += (size_t)P * C * 8;
-    double* lam = (double*)w; w += 64;                // [0] lam of H0, [1] lam' of H
+    ScCarver w(d_work);
+    const WsMvarMeasure<cd> k = ws_mvar_measure<cd>(w, P, C, N, MV_CMID);
+    cd *H = k.H, *Amv = k.Amv, *h0c = k.h0c, *hinvc = k.hinvc, *scratch = k.scratch;
+    double *h0 = k.h0, *hinv = k.hinv, *sigma = k.sigma, *sq = k.sq, *tot = k.tot, *lam = k.lam;
     const bool huge = C > MV_CMID;
-    w += (16 - ((uintptr_t)w & 15)) & 15;
-    cd* scratch = huge ? (cd*)w : nullptr;            // [P][F][E]: the blocked inverse's matrices, then m_measure's squared moduli
     const int nt = mv_threads((int)C);
     const bool big = C > mv_small_max();
     const size_t lds = big ? 0 : mv_pair_lds((int)C);
@@ -1615,13 +1586,16 @@ extern "C" int sc_mvar_measure_f64(const void* d_G, int64_t n_groups, int64_t N,
         (void)hipFuncSetAttribute((const void*)m_transfer, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
     const cd* G = (const cd*)d_G;
+    auto copy_out = [&](const void* src, size_t bytes) -> int {         // the quantities that are intermediate results of the chain
+        SC_CHECK_HIP(hipMemcpyAsync(d_out, src, bytes, hipMemcpyDeviceToDevice, st));
+        SC_CHECK_HIP(hipStreamSynchronize(st));
+        return SC_OK;
+    };
     const int h0_chunks = (E + 255) / 256;
     hipLaunchKernelGGL(m_h0, dim3((unsigned)P, (unsigned)h0_chunks), dim3(256), 0, st, G, h0, sq, N, E);
     hipLaunchKernelGGL(m_sum, dim3(1), dim3(64), 0, st, sq, P * h0_chunks, 1e-12 / (double)(P * E), lam);
     // beyond 64 signals the LDS-resident LU kernels give way to the in-register inverse and the matrix-core product;
-    // (H0 + lam I)^-1 as a complex matrix with zero imaginary part, parked in the (still unused) A_mvar buffer
-    cd* h0c = Amv;
-    cd* hinvc = Amv + (size_t)P * E;
+    // (H0 + lam I)^-1 as a complex matrix with zero imaginary part, parked in the (still unused) A_mvar buffer: h0c, hinvc
     if (big) {
         const unsigned nb = (unsigned)(((int64_t)P * E + 255) / 256);
         hipLaunchKernelGGL(m_real_to_cd, dim3(nb), dim3(256), 0, st, h0, h0c, (int64_t)P * E);
@@ -1633,11 +1607,7 @@ extern "C" int sc_mvar_measure_f64(const void* d_G, int64_t n_groups, int64_t N,
     } else {
         hipLaunchKernelGGL(m_h0_inverse, dim3((unsigned)P), dim3(nt), lds, st, h0, lam, hinv, sigma, (int)C);
     }
-    if (which == SC_MVAR_NOISE_COVARIANCE) {
-        SC_CHECK_HIP(hipMemcpyAsync(d_out, sigma, (size_t)P * E * 8, hipMemcpyDeviceToDevice, st));
-        SC_CHECK_HIP(hipStreamSynchronize(st));
-        return SC_OK;
-    }
+    if (which == SC_MVAR_NOISE_COVARIANCE) return copy_out(sigma, (size_t)P * E * 8);
     if (big) {          // H = G (H0 + lam I)^-1 on the non-negative bins, then the per-(window, bin) sums of |H|^2
         int rcb = mv_launch_gemm(C, MV_GEMM_PLAIN, dim3((unsigned)F, (unsigned)P), st,
                                  MvMat{const_cast<cd*>(G), N * (int64_t)E, (int64_t)E, 1}, MvMat{hinvc, (int64_t)E, 0, 1},
@@ -1647,42 +1617,23 @@ extern "C" int sc_mvar_measure_f64(const void* d_G, int64_t n_groups, int64_t N,
     } else {
         hipLaunchKernelGGL(m_transfer, dim3((unsigned)F, (unsigned)P), dim3(nt), lds, st, G, hinv, H, sq, N, F, (int)C);
     }
-    if (which == SC_MVAR_TRANSFER) {
-        SC_CHECK_HIP(hipMemcpyAsync(d_out, H, (size_t)P * F * E * sizeof(cd), hipMemcpyDeviceToDevice, st));
-        SC_CHECK_HIP(hipStreamSynchronize(st));
-        return SC_OK;
-    }
+    if (which == SC_MVAR_TRANSFER) return copy_out(H, (size_t)P * F * E * sizeof(cd));
     hipLaunchKernelGGL(m_sum, dim3(1), dim3(64), 0, st, sq, P * F, 1e-12 / (double)(P * F * E), lam + 1);
     if (big) {          // A_mvar = (H + lam' I)^-1 per (window, bin); the launch overwrites the parked H0 matrices last
         int rcb = mv_launch_inverse_big(C, dim3((unsigned)F, (unsigned)P), st, MvMat{H, F * (int64_t)E, (int64_t)E, 1}, lam + 1,
                                         MvMat{Amv, F * (int64_t)E, (int64_t)E, 1}, nullptr, scratch);
         if (rcb != SC_OK) return rcb;
     } else {
-        const int Q = (int)((C + 15) / 16);
-        const size_t glds = mv_gj_lds(Q);
-#define MV_INV(QQ)                                                                                              \
-    case QQ:                                                                                                    \
-        (void)hipFuncSetAttribute((const void*)m_inverse_gj<QQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds); \
-        hipLaunchKernelGGL(m_inverse_gj<QQ>, dim3((unsigned)(P * F)), dim3(256), glds, st, H, lam + 1, Amv, (int)C); \
-        break;
-        switch (Q) { MV_INV(1) MV_INV(2) MV_INV(3) default: MV_INV(4) }
-#undef MV_INV
+        int rcb = mv_launch_inverse_gj((int)C, (unsigned)(P * F), st, H, lam + 1, Amv);
+        if (rcb != SC_OK) return rcb;
     }
-    if (which == SC_MVAR_COEFFICIENTS) {
-        SC_CHECK_HIP(hipMemcpyAsync(d_out, Amv, (size_t)P * F * E * sizeof(cd), hipMemcpyDeviceToDevice, st));
-        SC_CHECK_HIP(hipStreamSynchronize(st));
-        return SC_OK;
-    }
+    if (which == SC_MVAR_COEFFICIENTS) return copy_out(Amv, (size_t)P * F * E * sizeof(cd));
     if (which == SC_MVAR_DDTF) hipLaunchKernelGGL(m_inflow_all, dim3((unsigned)P), dim3(64), 0, st, H, tot, F, (int)C);
     const size_t mlds = huge ? (size_t)C * 8 : (size_t)(E + C) * 8;
     SC_CHECK_HIP(hipFuncSetAttribute((const void*)m_measure, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
     hipLaunchKernelGGL(m_measure, dim3((unsigned)(P * F)), dim3(nt), mlds, st, H, Amv, sigma, tot, which,
                        (double*)d_out, F, (int)C, huge ? 0 : 1, (double*)scratch);
-    if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
-        sc_set_error("MVAR measure failed: %s", hipGetErrorString(hipGetLastError()));
-        return SC_EHIP;
-    }
-    return SC_OK;
+    return sc_sync_or_report(st, "MVAR measure");
 }
 
 // ---- the inverse and product launchers above on caller buffers (sc_conditional.hip: conditional Granger's epilogue) ----
@@ -1696,18 +1647,7 @@ int sc_internal_mvar_inverse(int64_t C, int64_t P, int64_t N, int64_t n_bins, co
     if (C > MV_CSMALL)
         return mv_launch_inverse_big(C, dim3((unsigned)n_bins, (unsigned)P), st, MvMat{(cd*)d_M, N * E, E, 1}, nullptr,
                                      MvMat{(cd*)d_out, N * E, E, 1}, nullptr, (cd*)scratch);
-    const int Q = (int)((C + 15) / 16);
-    const size_t glds = mv_gj_lds(Q);
-#define MV_INV(QQ)                                                                                              \
-    case QQ:                                                                                                    \
-        SC_CHECK_HIP(hipFuncSetAttribute((const void*)m_inverse_gj<QQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds)); \
-        hipLaunchKernelGGL(m_inverse_gj<QQ>, dim3((unsigned)(P * N)), dim3(256), glds, st, (const cd*)d_M, d_zero, (cd*)d_out, \
-                           (int)C);                                                                             \
-        break;
-    switch (Q) { MV_INV(1) MV_INV(2) MV_INV(3) default: MV_INV(4) }
-#undef MV_INV
-    SC_CHECK_HIP(hipGetLastError());
-    return SC_OK;
+    return mv_launch_inverse_gj((int)C, (unsigned)(P * N), st, (const cd*)d_M, d_zero, (cd*)d_out);
 }
 
 // O = X Y per (problem p < n_problems, bin n < n_bins) on the fp64 matrix cores (m_gemm_mfma); every operand is natural-layout

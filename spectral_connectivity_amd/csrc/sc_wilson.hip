@@ -20,6 +20,7 @@
 // Layouts: S [P][4][N] doubles (s00, s11, Re s01, Im s01); G, A [P][4][N] complex128
 // (entry e = 2*row + col), n fastest so the FFTs are unit-stride and pointwise kernels coalesce.
 #include "sc_wilson_loop.h"
+#include "sc_workspace.h"
 
 __device__ __forceinline__ int64_t wilson_problem() { return (int64_t)blockIdx.z * WILSON_PMAX + blockIdx.y; }
 static inline dim3 wilson_grid(unsigned gx, int64_t P) {
@@ -249,34 +250,14 @@ void sc_internal_granger_epilogue(const void* d_G, int64_t g_stride, const doubl
 // ------------------------------------------------------------------------------- host side
 extern "C" int sc_granger_workspace_bytes(int64_t n_groups, int64_t n_pairs, int64_t N, size_t* bytes) {
     SC_REQUIRE(bytes && n_groups >= 1 && n_pairs >= 1 && N >= 2, "bad workspace query");
-    const size_t P = (size_t)n_groups * n_pairs;
-    // S (4 doubles) + G (4 complex) + A (4 complex) per (problem, bin) + per-problem scalars
-    *bytes = P * (size_t)N * (4 * 8 + 4 * 16 + 4 * 16) + P * (8 + 4 + 4 + 4 * 8 * 3) + 256 + WILSON_HIST * 4;
+    ScCarver w(nullptr);
+    ws_wilson<cd>(w, (size_t)n_groups * n_pairs, N, WILSON_HIST);
+    *bytes = w.used;
     return SC_OK;
 }
 
-struct WilsonWork {
-    double* S; cd* G; cd* A; double* err; double* h0; double* hinv; double* rot;
-    int32_t* n_fallback;     // problems started from the identity (lag-0 covariance not positive definite); 256 bytes, then the
-                             // [WILSON_HIST] problems still running after iteration i
-};
-
-static WilsonWork wilson_carve(void* d_work, int64_t P, int64_t N) {
-    WilsonWork k;
-    char* w = (char*)d_work;
-    k.S = (double*)w; w += (size_t)P * N * 4 * 8;
-    k.G = (cd*)w; w += (size_t)P * N * 4 * 16;
-    k.A = (cd*)w; w += (size_t)P * N * 4 * 16;
-    k.err = (double*)w; w += (size_t)P * 8;
-    k.h0 = (double*)w; w += (size_t)P * 32;
-    k.hinv = (double*)w; w += (size_t)P * 32;
-    k.rot = (double*)w; w += (size_t)P * 32;
-    k.n_fallback = (int32_t*)w;
-    return k;
-}
-
 // k_init + the Wilson iteration on work.S -> work.G (the loop: sc_wilson_loop.h).
-static int wilson_iterate(const WilsonWork& k, int64_t P, int64_t n_batch, int64_t N, double tol, int max_iter,
+static int wilson_iterate(const WsWilson<cd>& k, int64_t P, int64_t n_batch, int64_t N, double tol, int max_iter,
                           int32_t* d_n_iter, int32_t* d_status, int* iters_out, int* running_out, int* fallback_out,
                           hipStream_t st) {
     int rc;
@@ -284,7 +265,7 @@ static int wilson_iterate(const WilsonWork& k, int64_t P, int64_t n_batch, int64
     const dim3 gridN = wilson_grid((unsigned)((N + 255) / 256), P);
     const bool fused = sc_internal_causal_fft_supported(N);
     if (max_iter <= WILSON_HIST && !fused && (rc = fft.init((size_t)N, (size_t)(4 * P), st)) != SC_OK) return rc;
-    const WilsonCounters c = {k.err, d_n_iter, d_status, k.n_fallback, 256};
+    const WilsonCounters c = {k.err, d_n_iter, d_status, k.n_fallback, k.fallback_bytes};
     const WilsonLoopResult r = wilson_loop(c, P, tol, max_iter, st,
         [&]() -> int {
             // (the per-batch flags borrow the start of the error array: P doubles >= n_batch ints, cleared again below)
@@ -324,8 +305,9 @@ extern "C" int sc_granger_pairwise_f64(const void* d_accum, int64_t n_groups, in
     int rc = sc_csm_view(planes, n_freq_accum, N, C, n_obs, &d.v);
     if (rc != SC_OK) return rc;
     SC_REQUIRE(n_groups >= 1 && n_pairs >= 1 && n_groups * n_pairs <= (int64_t)WILSON_PMAX * WILSON_PMAX, "bad problem count");
-    size_t need = 0;
-    sc_granger_workspace_bytes(n_groups, n_pairs, N, &need);
+    ScCarver w(d_work);
+    const WsWilson<cd> k = ws_wilson<cd>(w, (size_t)n_groups * n_pairs, N, WILSON_HIST);
+    const size_t need = w.used;
     SC_REQUIRE(work_bytes >= need, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     if (sc_internal_granger_resident_applies(n_freq_accum, N)) {
@@ -336,7 +318,6 @@ extern "C" int sc_granger_pairwise_f64(const void* d_accum, int64_t n_groups, in
     }
     d.P = n_groups * n_pairs; d.n_pairs = n_pairs;
     const int64_t P = d.P, Fout = N / 2 + 1;
-    const WilsonWork k = wilson_carve(d_work, P, N);
     const dim3 gridN = wilson_grid((unsigned)((N + 255) / 256), P);
     if (!(flags & SC_GRANGER_KEEP_OUTPUT)) sc_internal_fill_nan(d_out, n_groups * Fout * C * C, st);
     hipLaunchKernelGGL(k_build, gridN, dim3(256), 0, st, sc_rec(d_accum, planes), d_pairs, d, k.S);
@@ -345,10 +326,7 @@ extern "C" int sc_granger_pairwise_f64(const void* d_accum, int64_t n_groups, in
     if (rc != SC_OK) return rc;
     hipLaunchKernelGGL(k_h0, dim3((unsigned)P), dim3(256), 0, st, k.G, k.h0, N);
     sc_internal_granger_epilogue(k.G, N, k.h0, k.hinv, k.rot, sc_rec(d_accum, planes), d.v, d_pairs, n_groups, n_pairs, C, d_out, st);
-    if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
-        sc_set_error("Granger epilogue failed: %s", hipGetErrorString(hipGetLastError()));
-        return SC_EHIP;
-    }
+    if ((rc = sc_sync_or_report(st, "Granger epilogue")) != SC_OK) return rc;
     if (h_summary) { h_summary[0] = iters; h_summary[1] = running; h_summary[2] = fallback; }
     return SC_OK;
 }
@@ -362,11 +340,11 @@ extern "C" int sc_wilson_factor_f64(const double* d_S, int64_t n_problems, int64
     ScTimed timed_("wilson_factor", stream);
     SC_REQUIRE(d_S && d_work && d_G && d_n_iter && d_status, "NULL argument");
     SC_REQUIRE(n_problems >= 1 && n_problems <= (int64_t)WILSON_PMAX * WILSON_PMAX && N >= 2, "bad problem size");
-    size_t need = 0;
-    sc_granger_workspace_bytes(1, n_problems, N, &need);
+    ScCarver w(d_work);
+    const WsWilson<cd> k = ws_wilson<cd>(w, n_problems, N, WILSON_HIST);
+    const size_t need = w.used;
     SC_REQUIRE(work_bytes >= need, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    const WilsonWork k = wilson_carve(d_work, n_problems, N);
     SC_CHECK_HIP(hipMemcpyAsync(k.S, d_S, (size_t)n_problems * N * 4 * 8, hipMemcpyDeviceToDevice, st));
     int iters = 0, running = 0, fallback = 0;
     const int rc = wilson_iterate(k, n_problems, 1, N, tol, max_iter, d_n_iter, d_status, &iters, &running, &fallback, st);

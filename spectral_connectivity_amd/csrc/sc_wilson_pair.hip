@@ -27,6 +27,7 @@
 // coefficients, other lengths, sc_wilson_factor_f64 -- stays on sc_wilson.hip.  SC_GRANGER_KERNEL=batched forces that path.
 #include <string.h>
 #include "sc_wilson_fft.h"
+#include "sc_workspace.h"
 
 // (the record fields are a copy of the entry point's ScCsmView, and pair_read_S below is this file's own reader, on purpose: the
 //  kernels run at the register limit of one wave per SIMD, and sc_csm_entry in their place -- its diagonal test, the view's layout --
@@ -671,11 +672,6 @@ static int pair_launch(const PairArgs& a, hipStream_t st) {
     return SC_OK;
 }
 
-// bytes of workspace the resident form needs (always within sc_granger_workspace_bytes of the same request)
-static size_t pair_workspace_bytes(int64_t P, int64_t n_pairs, int64_t N) {
-    return (size_t)P * (size_t)(N / 2 + 1) * 4 * 16 + (size_t)P * 4 * 8 * 4 + (size_t)n_pairs * 4 + 256;
-}
-
 bool sc_internal_granger_resident_applies(int64_t n_freq_accum, int64_t N) {
     const char* e = sc_switch(SC_SW_GRANGER_KERNEL);
     if (e && strcmp(e, "batched") == 0) return false;
@@ -688,7 +684,10 @@ int sc_internal_granger_resident(const void* d_accum, int64_t n_groups, const Sc
                                  int keep_output, double* d_out, int32_t* d_n_iter, int32_t* d_status, int32_t* h_summary,
                                  hipStream_t st) {
     const int64_t N = v.N, P = n_groups * n_pairs, F = N / 2 + 1;
-    SC_REQUIRE(work_bytes >= pair_workspace_bytes(P, n_pairs, N), "workspace too small");
+    ScCarver w(d_work);          // (within sc_granger_workspace_bytes of the same request: tests/test_workspace_layouts.py)
+    const WsPair<cd> k = ws_pair<cd>(w, P, n_pairs, N);
+    const size_t need = w.used;
+    SC_REQUIRE(work_bytes >= need, "workspace too small");
     PairArgs a;
     a.accum = sc_rec(d_accum, planes);
     a.pairs = d_pairs;
@@ -696,14 +695,7 @@ int sc_internal_granger_resident(const void* d_accum, int64_t n_groups, const Sc
     a.C = (int)C; a.NB = v.NB; a.n_tiles = v.n_tiles; a.p_csm = v.p_csm;
     a.floats_per_bin = v.floats_per_bin;
     a.n_obs = v.n_obs;
-    char* w = (char*)d_work;
-    a.Ghalf = (cd*)w; w += (size_t)P * F * 4 * 16;
-    a.chol = (double*)w; w += (size_t)P * 32;
-    a.h0 = (double*)w; w += (size_t)P * 32;
-    double* hinv = (double*)w; w += (size_t)P * 32;
-    double* rot = (double*)w; w += (size_t)P * 32;
-    a.batch_bad = (int32_t*)w; w += (size_t)n_pairs * 4;
-    a.summary = (int32_t*)w;
+    a.Ghalf = k.Ghalf; a.chol = k.chol; a.h0 = k.h0; a.batch_bad = k.batch_bad; a.summary = k.summary;
     a.n_iter = d_n_iter; a.status = d_status;
     a.tol = tol; a.max_iter = max_iter;
     SC_CHECK_HIP(hipMemsetAsync(a.batch_bad, 0, (size_t)n_pairs * 4 + 256, st));          // the flags and the summary behind them
@@ -727,7 +719,7 @@ int sc_internal_granger_resident(const void* d_accum, int64_t n_groups, const Sc
     default: rc = pair_launch<12>(a, st); break;
     }
     if (rc != SC_OK) return rc;
-    sc_internal_granger_epilogue(a.Ghalf, F, a.h0, hinv, rot, a.accum, v, d_pairs, n_groups, n_pairs, C, d_out, st);
+    sc_internal_granger_epilogue(a.Ghalf, F, a.h0, k.hinv, k.rot, a.accum, v, d_pairs, n_groups, n_pairs, C, d_out, st);
     int32_t sum[3] = {0, 0, 0};
     if (hipMemcpyAsync(sum, a.summary, sizeof sum, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
         hipGetLastError() != hipSuccess) {

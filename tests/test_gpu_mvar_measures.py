@@ -28,6 +28,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mvar_measures_ref as mref                                              # noqa: E402
+from guarded_buffers import BAND, guarded, intact                             # noqa: E402
 from spectral_connectivity_amd import _lib                                    # noqa: E402
 
 gpu = pytest.mark.gpu
@@ -242,9 +243,6 @@ def test_edges(kind, C, N, P):
 
 
 # ---- (g) stores ----------------------------------------------------------------------------------------------------------------------
-BAND = 4096
-
-
 @gpu
 @pytest.mark.parametrize("C", [5, 64, 100, 130, 260])
 def test_nothing_is_stored_outside_the_buffers(C):
@@ -261,19 +259,7 @@ def test_nothing_is_stored_outside_the_buffers(C):
     nbytes = ctypes.c_size_t()
     _lib.check(lib.sc_mvar_workspace_bytes(P, C, N, ctypes.byref(nbytes)), "sc_mvar_workspace_bytes")
     nbytes = nbytes.value
-    pattern = torch.arange(BAND, dtype=torch.int32, device="cuda:0").mul_(37).add_(11).to(torch.uint8)
     stream = engine.TorchMemory(d_G.device).stream()
-
-    def guarded(n):
-        buf = torch.empty(n + 2 * BAND, dtype=torch.uint8, device="cuda:0")
-        buf[BAND:BAND + n] = 0x5A
-        buf[:BAND] = pattern
-        buf[BAND + n:] = pattern
-        assert (buf.data_ptr() + BAND) % 256 == 0
-        return buf
-
-    def intact(buf, n):
-        return bool(torch.equal(buf[:BAND], pattern)) and bool(torch.equal(buf[BAND + n:], pattern))
 
     for name in mref.QUANTITIES:
         itemsize = 16 if name in ("transfer_function", "mvar_coefficients") else 8
