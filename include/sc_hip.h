@@ -608,6 +608,41 @@ int sc_partial_coherence_f64(const void* d_accum, int64_t n_bins, int64_t n_sign
                              int64_t n_observations, void* d_coherency /*complex128*/, double* d_magnitude,
                              double* d_multiple, int32_t* d_fail, void* stream);
 
+/* ---- partial and multiple coherence given a chosen set of signals (sc_partial.hip; additive, ABI v8) ----
+ * The same measures with a chosen conditioning set (FieldTrip's partchannel): the coherence of the kept signals after the m
+ * given signals Z -- and only those -- are regressed out of each, and the share of a kept signal's power that the given ones
+ * explain.  Per bin record, with A the a kept signals (disjoint from Z) and the residual cross-spectrum
+ *     E = S_AA - S_AZ S_ZZ^-1 S_ZA = S_AA - W^H W,   W = L^-1 S_ZA,   S_ZZ = L L^H:
+ *     partial coherency given Z      gamma_ij = E_ij / sqrt(E_ii E_jj)          Hermitian, i, j in A
+ *     magnitude                      |gamma_ij|                                 in [0, 1], not squared
+ *     multiple coherence given Z     R_i = sqrt(max(0, 1 - E_ii / S_ii))        in [0, 1]
+ * All three are unchanged under S -> D S D; the kernel works on the unit-diagonal S', where r_i = E'_ii = 1 - sum_k |W_ki|^2 and
+ * R_i = sqrt(sum_k |W_ki|^2).  One 256-thread workgroup per record, no workspace; resident in LDS are the packed triangle of Z,
+ * W [m][a] and three rows of doubles:
+ *     sc_partial_given_lds_bytes(a, m) = (m (m + 1) / 2 + m a) * 16 + (2 a + m) * 8 + 16   (-1 outside the two ranges below)
+ * which must not exceed sc_partial_given_lds_limit() = 160 KB: 1024 kept given 8 (145 KB), 512 given 16 (138 KB), 300 given 6
+ * (33 KB), 14 given 128 (158 KB), and every a + m <= 128.  1 <= m <= sc_partial_given_max_given() = 128,
+ * 1 <= a <= sc_partial_given_max_kept() = 1024, a + m <= n_signals.
+ *   d_accum       records as for sc_partial_coherence_f64 (same checks and error codes; SC_EINVAL also for sizes outside the
+ *                 limits and for three NULL outputs; SC_EHIP if the device refuses the dynamic LDS)
+ *   d_kept        int32 [n_kept], d_given int32 [n_given]: device arrays of distinct signal indices in [0, n_signals); the
+ *                 outputs are in the order of d_kept.  An index outside the range fails its problems (its record is not read).
+ *   d_coherency   complex128 [n_bins][a][a] or NULL, NaN diagonal
+ *   d_magnitude   double [n_bins][a][a] or NULL, symmetric, NaN diagonal
+ *   d_multiple    double [n_bins][a] or NULL
+ *   d_fail        int32 [2]: [0] records that failed -- a kept or given signal without (finite) power, or a Cholesky pivot of
+ *                 the scaled Z block that is not finite or <= m 2^-52 (two identical given signals) --, NaN in all of their
+ *                 outputs; [1] (record, kept signal) cases with r_i <= (m + 1) 2^-52 or not finite -- the given signals explain
+ *                 the signal entirely (a copy of one of them): NaN in its row and column, R_i = 1, nothing else affected */
+int     sc_partial_given_max_given(void);
+int     sc_partial_given_max_kept(void);
+int64_t sc_partial_given_lds_bytes(int64_t n_kept, int64_t n_given);
+int64_t sc_partial_given_lds_limit(void);
+int sc_partial_coherence_given_f64(const void* d_accum, int64_t n_bins, int64_t n_signals, uint32_t planes,
+                                   int64_t n_observations, const int32_t* d_kept, int n_kept, const int32_t* d_given,
+                                   int n_given, void* d_coherency /*complex128 [n_bins][a][a]*/, double* d_magnitude,
+                                   double* d_multiple /*[n_bins][a]*/, int32_t* d_fail /*[2]*/, void* stream);
+
 /* ---- delete-one jackknife of power and coherence (sc_jackknife.hip; additive, ABI v8) ------------------------
  * Standard errors that rest on the data (Thomson & Chave 1991; Chronux coherencyc / mtspectrumc with err = [2 p]); the
  * reference has only the closed forms of statistics.py.  Per kept index and bin the delete units u = 1 .. n hold g

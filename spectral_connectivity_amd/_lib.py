@@ -171,6 +171,12 @@ SYMBOLS = {
     "sc_partial_coherence_max_signals": (c_int, []),
     "sc_partial_coherence_f64": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p]),
+    "sc_partial_given_max_given": (c_int, []),
+    "sc_partial_given_max_kept": (c_int, []),
+    "sc_partial_given_lds_bytes": (c_int64, [c_int64, c_int64]),
+    "sc_partial_given_lds_limit": (c_int64, []),
+    "sc_partial_coherence_given_f64": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_void_p, c_int, c_void_p, c_int,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sc_jackknife_layout": (c_int, [POINTER(SpectraDesc), c_uint32, c_int, c_int64_p, c_int64_p, c_int64_p, c_int64_p]),
     "sc_jackknife_workspace_bytes": (c_int64, [POINTER(SpectraDesc), c_uint32, c_int, c_int64, c_int64]),
     "sc_jackknife_f32": (c_int, [c_void_p, POINTER(SpectraDesc), c_void_p, c_uint32, c_uint32, c_int, c_int64, c_int64, c_int64,
@@ -365,6 +371,45 @@ def interaction_kept(sizes, n_obs):
     import numpy as np
     keep = np.flatnonzero(np.asarray(sizes) <= 2 * n_obs)
     return keep, len(sizes) - len(keep)
+
+
+def _index_list(values, what, n_signals):
+    """1-D int64 array of distinct signal indices in [0, n_signals) out of ``values``; ValueError otherwise."""
+    import numpy as np
+    raw = np.asarray(values)
+    if raw.ndim != 1:
+        raise ValueError(f"partial coherence: `{what}` must be a list of signal indices (got shape {raw.shape})")
+    if raw.size and (raw.dtype == bool or not np.issubdtype(raw.dtype, np.integer)):
+        raise ValueError(f"partial coherence: `{what}` must hold integer signal indices (got {raw.dtype})")
+    idx = raw.astype(np.int64)
+    if idx.size and (idx.min() < 0 or idx.max() >= n_signals):
+        raise ValueError(f"partial coherence: `{what}` has an index outside [0, {n_signals})")
+    if len(np.unique(idx)) != len(idx):
+        raise ValueError(f"partial coherence: `{what}` names a signal twice")
+    return idx
+
+
+def partial_given_indices(given, signals, n_signals):
+    """The two index lists of partial and multiple coherence given a chosen set, checked before any device work (both hosts):
+    (kept int32 [a] in the order of ``signals``, given int32 [m] in the caller's order).  ``signals`` None: every signal that is
+    not given, ascending.  ValueError for an empty ``given`` (or ``signals`` without ``given``), an empty kept set, duplicates,
+    overlap between the two lists, an index outside [0, n_signals) and anything but integers."""
+    import numpy as np
+    if given is None:
+        raise ValueError("partial coherence: `signals` needs `given`, the signals to condition on")
+    z = _index_list(given, "given", n_signals)
+    if len(z) == 0:
+        raise ValueError("partial coherence: `given` is empty (without the keyword, every other signal is conditioned on)")
+    if signals is None:
+        kept = np.setdiff1d(np.arange(n_signals), z)
+    else:
+        kept = _index_list(signals, "signals", n_signals)
+        both = np.intersect1d(kept, z)
+        if len(both):
+            raise ValueError(f"partial coherence: signals {both.tolist()} are both kept and given")
+    if len(kept) == 0:
+        raise ValueError("partial coherence: no signal is kept")
+    return kept.astype(np.int32), z.astype(np.int32)
 
 
 # ---- delete-one jackknife (sc_jackknife.hip): the request, checked before any device work (both hosts) ----------------------------

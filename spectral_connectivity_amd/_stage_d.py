@@ -249,6 +249,26 @@ def partial_coherence(mem, accum, n_signals, planes, n_obs, want):
     return out, mem.read_int(fail)
 
 
+def partial_coherence_given(mem, accum, n_signals, planes, n_obs, kept, given, want):
+    """Partial and multiple coherence given a chosen set (sc_partial_coherence_given_f64) of every bin record.  ``kept`` / ``given``:
+    the int32 arrays of _lib.partial_given_indices; ``want`` as partial_coherence.  Returns ({name: device array}, (records that
+    failed, (record, kept signal) cases without a residual)): coherency complex128 and magnitude float64 [n_bins, a, a] in the order
+    of ``kept``, multiple float64 [n_bins, a]."""
+    n_bins, a = accum.shape[0], len(kept)
+    shapes = {"coherency": ((n_bins, a, a), np.complex128), "magnitude": ((n_bins, a, a), np.float64),
+              "multiple": ((n_bins, a), np.float64)}
+    out = {name: mem.empty(*shapes[name]) for name in want}
+    d_kept, d_given = mem.upload(np.ascontiguousarray(kept, dtype=np.int32)), mem.upload(np.ascontiguousarray(given, dtype=np.int32))
+    fail = mem.zeros((2,), np.int32)
+    _lib.check(_lib._handle().sc_partial_coherence_given_f64(mem.ptr(accum), n_bins, n_signals, _planes(mem, accum, planes), n_obs,
+                                                             mem.ptr(d_kept), a, mem.ptr(d_given), len(given),
+                                                             _ptr(mem, out.get("coherency")), _ptr(mem, out.get("magnitude")),
+                                                             _ptr(mem, out.get("multiple")), mem.ptr(fail), mem.stream()),
+               "sc_partial_coherence_given_f64")
+    n_failed, n_explained = (int(n) for n in np.asarray(mem.download(fail)).ravel())
+    return out, (n_failed, n_explained)
+
+
 def _jackknife_workspace(mem, workspace_bytes, d, mask, over, n_units, unit_range):
     """(first unit, end unit, workspace or None, its bytes) of a jackknife call over ``unit_range`` (None: all ``n_units`` units of
     the spectra); ``workspace_bytes``: the entry-point family's sc_*_workspace_bytes, ``mask``: what it takes after the descriptor."""

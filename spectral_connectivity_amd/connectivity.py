@@ -696,30 +696,103 @@ class Connectivity:
         return engine.to_host(mic).reshape(shape), engine.to_host(mim).reshape(shape), labels
 
     # ---- partial and multiple coherence (Bendat & Piersol 1986, ch. 7; Dahlhaus 2000) ----------------------------
-    def partial_coherency(self):
-        """Coherency of each pair of signals after the linear influence of ALL other signals is removed from both:
-        -G_ij / sqrt(G_ii G_jj) with G the inverse of the cross-spectral matrix.  Where two signals are coherent only because both
-        see a third recorded signal, it is 0 while ``coherency()`` is not; with two signals it is ``coherency()``.
+    def partial_coherency(self, given=None, signals=None):
+        """Coherency of each pair of signals after the linear influence of other signals is removed from both.
 
-        Returns complex128 [kept axes..., n_frequencies, n_signals, n_signals], Hermitian with a NaN diagonal; the expectation
-        is the object's ``expectation_type``.  Up to sc_partial_coherence_max_signals() = 128 signals (sc_partial.hip;
-        ValueError beyond).  The cross-spectral matrix of fewer observations than signals is singular: everything is NaN (one
-        warning, no device work); a matrix the device cannot invert -- a channel without power, two identical channels, a
-        condition number beyond 1 / (n_signals 2^-52) after scaling to a unit diagonal -- gives NaN in its bin (one warning
-        counts them).  No bias correction, and no choice of the signals to condition on: always all the others.
+        Without keywords ALL other signals are removed: -G_ij / sqrt(G_ii G_jj) with G the inverse of the cross-spectral matrix.
+        Where two signals are coherent only because both see a third recorded signal, it is 0 while ``coherency()`` is not; with
+        two signals it is ``coherency()``.  Returns complex128 [kept axes..., n_frequencies, n_signals, n_signals], Hermitian with
+        a NaN diagonal; the expectation is the object's ``expectation_type``.  Up to sc_partial_coherence_max_signals() = 128
+        signals (sc_partial.hip; ValueError beyond).  The cross-spectral matrix of fewer observations than signals is singular:
+        everything is NaN (one warning, no device work); a matrix the device cannot invert -- a channel without power, two
+        identical channels, a condition number beyond 1 / (n_signals 2^-52) after scaling to a unit diagonal -- gives NaN in its
+        bin (one warning counts them).  No bias correction.
+
+        ``given``: the indices of the m signals to remove (EOG, ECG, a reference sensor, a stimulus trace; FieldTrip's
+        ``partchannel``), and ``signals`` the indices of the a signals to keep -- by default every signal that is not given,
+        ascending.  The result is E_ij / sqrt(E_ii E_jj) with E = S_AA - S_AZ S_ZZ^-1 S_ZA the cross-spectrum of what is left of
+        the kept signals A after each is regressed on the given signals Z, complex128 [kept axes..., n_frequencies, a, a] in the
+        order of ``signals``.  The record may then have any number of signals: 1 <= m <= 128, 1 <= a <= 1024 and
+        sc_partial_given_lds_bytes(a, m) within 160 KB (1024 kept given 8, 512 given 16, 300 given 6, every a + m <= 128);
+        ValueError with the numbers beyond, and for lists that are empty, overlap, repeat a signal or leave the range.  No more
+        observations than given signals leave no residual: everything is NaN (one warning, no device work).  A bin whose given
+        block cannot be factored (a given signal without power, two identical given signals) is NaN (one warning counts the
+        bins); a kept signal the given ones explain entirely (a copy of one) is NaN in its row and column of its bin, nothing
+        else (one warning counts the cases).
         """
-        return self._partial_coherence("coherency")
+        return self._partial_dispatch("coherency", given, signals)
 
-    def partial_coherence_magnitude(self):
-        """|partial_coherency()|, in [0, 1] and not squared: float64 [kept axes..., n_frequencies, n_signals, n_signals],
-        symmetric with a NaN diagonal.  Computes and limits as partial_coherency."""
-        return self._partial_coherence("magnitude")
+    def partial_coherence_magnitude(self, given=None, signals=None):
+        """|partial_coherency(given, signals)|, in [0, 1] and not squared: float64 shaped like it, symmetric with a NaN diagonal.
+        Computes and limits as partial_coherency."""
+        return self._partial_dispatch("magnitude", given, signals)
 
-    def multiple_coherence_magnitude(self):
-        """The share of each signal's power that all the other signals explain linearly, as a magnitude:
-        sqrt(1 - 1 / (S_ii G_ii)) in [0, 1), float64 [kept axes..., n_frequencies, n_signals].  Computes and limits as
-        partial_coherency."""
-        return self._partial_coherence("multiple")
+    def multiple_coherence_magnitude(self, given=None, signals=None):
+        """The share of each signal's power that other signals explain linearly, as a magnitude.  Without keywords the share that
+        ALL the other signals explain: sqrt(1 - 1 / (S_ii G_ii)) in [0, 1), float64 [kept axes..., n_frequencies, n_signals].
+        With ``given`` it is the share of the power of each kept signal that the GIVEN signals explain -- not all the others --,
+        sqrt(1 - E_ii / S_ii) in [0, 1], float64 [kept axes..., n_frequencies, a] in the order of ``signals``; exactly 1 for a
+        kept signal that the given ones explain entirely.  Computes and limits as partial_coherency."""
+        return self._partial_dispatch("multiple", given, signals)
+
+    def _partial_dispatch(self, name, given, signals):
+        if given is None and signals is None:
+            return self._partial_coherence(name)
+        return self._partial_coherence_given(name, given, signals)
+
+    def _partial_given_request(self, name, given, signals):
+        """(kept, given int32 index arrays, the signal axes, the whole shape, the dtype) of the output ``name`` of
+        sc_partial_coherence_given_f64, after every check that needs no device."""
+        kept, z = _lib.partial_given_indices(given, signals, self._shape5[4])
+        lib = _lib.load()
+        a, m = len(kept), len(z)
+        max_kept, max_given = int(lib.sc_partial_given_max_kept()), int(lib.sc_partial_given_max_given())
+        if m > max_given or a > max_kept:
+            raise ValueError(f"partial coherence given a set takes at most {max_given} given and {max_kept} kept signals "
+                             f"(got {m} given, {a} kept)")
+        need, limit = int(lib.sc_partial_given_lds_bytes(a, m)), int(lib.sc_partial_given_lds_limit())
+        if need > limit:
+            raise ValueError(f"partial coherence of {a} kept signals given {m} needs {need} bytes of LDS, beyond the {limit} of a "
+                             "compute unit: keep or give fewer signals")
+        tail = (a,) if name == "multiple" else (a, a)
+        return kept, z, tail, self._kept_shape() + (self._n_freq,) + tail, np.complex128 if name == "coherency" else np.float64
+
+    def _partial_given_few_observations(self, n_total, m):
+        if n_total <= m:
+            logger.warning(f"partial coherence: {m} given signals from {n_total} observations leave no residual (no more "
+                           "observations than given signals): NaN")
+        return n_total <= m
+
+    def _partial_given_failed(self, counts):
+        n_failed, n_explained = counts
+        if n_failed:
+            logger.warning(f"partial coherence: {n_failed} matrices of the given signals have no inverse (a signal without power, "
+                           "or not positive definite to rounding): NaN output")
+        if n_explained:
+            logger.warning(f"partial coherence: {n_explained} (bin, signal) cases where the given signals explain a kept signal "
+                           "entirely: NaN in its pairs")
+
+    def _partial_coherence_given(self, name, given, signals):
+        from . import engine
+        import torch
+        kept, z, tail, shape, dtype = self._partial_given_request(name, given, signals)
+        accum, n_obs, _ = self._csm_records("interaction", two_sided=False)
+        n_total = self._n_observations_total(n_obs)
+        if self._partial_given_few_observations(n_total, len(z)):
+            return np.full(shape, np.nan, dtype=dtype)
+        lo, hi, per = self._canonical_bins(accum.shape[0])
+        counts = (0, 0)
+        if hi > lo:
+            res, counts = engine.partial_coherence_given(accum[lo:hi], self._shape5[4], _lib.PLANE_CSM, n_total, kept, z, (name,))
+            out = res[name]
+        else:                                  # more processes than bins: this one has nothing to evaluate
+            out = torch.empty((0,) + tail, dtype=engine._TORCH_DTYPES[dtype], device=accum.device)
+        if name == "coherency":                # (gathered as pairs of doubles: not every backend moves complex tensors)
+            out = torch.view_as_complex(self._canonical_gather(torch.view_as_real(out), accum.shape[0], per).contiguous())
+        else:
+            out = self._canonical_gather(out, accum.shape[0], per)
+        self._partial_given_failed(counts)
+        return engine.to_host(out).reshape(shape)
 
     def _partial_shape(self, name):
         """(n_signals after the range check, the signal axes, the whole shape, the dtype) of the output ``name`` of

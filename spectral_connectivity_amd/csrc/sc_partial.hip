@@ -225,6 +225,208 @@ __global__ __launch_bounds__(PC_THREADS) void partial_coherence_kernel(PartialAr
     }
 }
 
+// ---- given a chosen set of signals ----------------------------------------------------------------------------------------
+// With Z the m given signals and A the a kept ones, the residual cross-spectrum of A after regressing on Z is
+//     E = S_AA - S_AZ S_ZZ^-1 S_ZA = S_AA - W^H W,    W = L^-1 S_ZA,    S_ZZ = L L^H,
+// and per (bin, kept pair) gamma_ij = E_ij / sqrt(E_ii E_jj), R_i = sqrt(max(0, 1 - E_ii / S_ii)).  On the unit-diagonal S' as
+// above: r_i = E'_ii = 1 - sum_k |W_ki|^2 and R_i = sqrt(sum_k |W_ki|^2).  Only the triangle of Z and W are resident:
+//     P     [m (m + 1) / 2] complex   packed lower triangle of S'_ZZ, then its Cholesky factor L
+//     W     [m][a]          complex   S'(z_k, a_i), i fastest, then L^-1 of it
+//     dg    [m + a]         double    S_ii of the given, then of the kept signals (the latter 1 / sqrt(S_ii) from step 4 on)
+//     r     [a]             double    r_i as 1 / sqrt(r_i) (NaN: the kept signal is entirely explained by the given ones)
+//     flag  [4]             int       the problem failed
+// Steps: diagonal and index check; load both blocks scaled, Cholesky of the Z block (pivot floor m 2^-52); forward elimination
+// L W = B, right-looking over the rows of W with one barrier a given signal (row k is scaled by 1 / L_kk one iteration late, when
+// nobody reads it any more); r_i and R_i; the pairs, one 8 x 8 tile of (i >= j) pairs a wave and step: the stores at (i, j) and
+// their mirrors at (j, i) are then both eight runs of eight neighbours (128 B of coherency each) per wave instruction.
+constexpr int PG_MAX_GIVEN = 128;
+constexpr int PG_MAX_KEPT = 1024;
+constexpr size_t PG_LDS_LIMIT = 160 * 1024;
+
+struct PartialGivenArgs {
+    ScRec accum;
+    ScCsmView v;
+    int a, m, n_signals;
+    int64_t n_bins;
+    const int32_t* kept;     // [a]
+    const int32_t* given;    // [m]
+    cd* coherency;           // [n_bins][a][a] or NULL
+    double* magnitude;       // [n_bins][a][a] or NULL
+    double* multiple;        // [n_bins][a] or NULL
+    int32_t* fail;           // [2]: failed problems, (problem, kept signal) cases without a residual
+};
+
+__host__ __device__ constexpr size_t pg_lds_bytes(int64_t a, int64_t m) {
+    return ((size_t)m * (m + 1) / 2 + (size_t)m * a) * sizeof(cd) + (size_t)(2 * a + m) * sizeof(double) + 16;
+}
+
+__global__ __launch_bounds__(PC_THREADS) void partial_given_kernel(PartialGivenArgs g) {
+    extern __shared__ __attribute__((aligned(16))) char pc_smem[];
+    const int a = g.a, m = g.m, tid = threadIdx.x;
+    cd* P = reinterpret_cast<cd*>(pc_smem);
+    cd* W = P + m * (m + 1) / 2;
+    double* dz = reinterpret_cast<double*>(W + m * a);
+    double* da = dz + m;
+    double* r = da + a;
+    int* bad = reinterpret_cast<int*>(r + a);
+    const double qnan = nan("");
+    // entry e = tid + 256 s of an [rows][a] array is (k0 + s q + carries, i): no division per entry
+    const int q = PC_THREADS / a, rm = PC_THREADS - q * a;
+    const int k0 = tid / a, i0 = tid - k0 * a;
+
+    for (int64_t bin = blockIdx.x; bin < g.n_bins; bin += gridDim.x) {
+        const ScRec rec = sc_csm_record(g.accum, g.v, 0, bin);
+        if (tid == 0) *bad = 0;
+        __syncthreads();
+        // 1. the diagonal of the given and the kept signals; an index outside the record fails the problem unread
+        for (int t = tid; t < m + a; t += PC_THREADS) {
+            const int c = t < m ? g.given[t] : g.kept[t - m];
+            bool ok = c >= 0 && c < g.n_signals;
+            double s = 1.0;
+            if (ok) {
+                s = sc_csm_entry(rec, g.v, c, c).x;
+                ok = s > 0.0 && isfinite(s);
+            }
+            if (!ok) *bad = 1;
+            dz[t] = ok ? s : 1.0;
+        }
+        __syncthreads();
+        if (!*bad) {
+            // the Z block and B = S'_ZA, scaled to the unit diagonal
+            for (int e = tid; e < m * m; e += PC_THREADS) {
+                const int j = e / m, i = e - j * m;
+                if (i > j) {
+                    const cd s = sc_csm_entry(rec, g.v, g.given[i], g.given[j]);
+                    const double w = sqrt(dz[i] * dz[j]);
+                    P[pc_row(i) + j] = make_double2(s.x / w, s.y / w);
+                } else if (i == j) {
+                    P[pc_row(i) + i] = make_double2(1.0, 0.0);
+                }
+            }
+            for (int k = k0, i = i0; k < m;) {
+                const cd s = sc_csm_entry(rec, g.v, g.given[k], g.kept[i]);
+                const double w = sqrt(dz[k] * da[i]);
+                W[k * a + i] = make_double2(s.x / w, s.y / w);
+                i += rm; k += q;
+                if (i >= a) { i -= a; ++k; }
+            }
+        }
+        __syncthreads();
+        // 2. Cholesky S'_ZZ = L L^H
+        if (PC_STEPS >= 2 && !*bad) pc_cholesky_packed(P, m, (double)m * 0x1p-52, bad);
+        __syncthreads();
+        const bool failed = *bad != 0;
+        if (!failed && PC_STEPS >= 3) {
+            // 3. L W = B.  Iteration k: rows k' > k lose L_k'k W_k with W_k = B_k / L_kk formed on the fly from the unscaled row,
+            // and row k - 1 (read by nobody now) is scaled; two entries a thread and step with their loads ahead of the first store
+            double rprev = 1.0;
+            for (int k = 0; k < m; ++k) {
+                const double rk = 1.0 / P[pc_row(k) + k].x;
+                if (k > 0)
+                    for (int i = tid; i < a; i += PC_THREADS) {
+                        const cd v = W[(k - 1) * a + i];
+                        W[(k - 1) * a + i] = make_double2(v.x * rprev, v.y * rprev);
+                    }
+                const cd* wk = W + k * a;
+                for (int kk = k + 1 + k0, i = i0; kk < m;) {
+                    int kk2 = kk + q, i2 = i + rm;
+                    if (i2 >= a) { i2 -= a; ++kk2; }
+                    const bool two = kk2 < m;
+                    if (!two) { kk2 = kk; i2 = i; }
+                    const cd l = P[pc_row(kk) + k], b = wk[i], v = W[kk * a + i];
+                    const cd l2 = P[pc_row(kk2) + k], b2 = wk[i2], v2 = W[kk2 * a + i2];
+                    const double tx = b.x * rk, ty = b.y * rk, tx2 = b2.x * rk, ty2 = b2.y * rk;
+                    W[kk * a + i] = make_double2(v.x - (l.x * tx - l.y * ty), v.y - (l.x * ty + l.y * tx));
+                    if (two) W[kk2 * a + i2] = make_double2(v2.x - (l2.x * tx2 - l2.y * ty2), v2.y - (l2.x * ty2 + l2.y * tx2));
+                    kk = kk2 + q; i = i2 + rm;
+                    if (i >= a) { i -= a; ++kk; }
+                    if (!two) break;
+                }
+                __syncthreads();
+                rprev = rk;
+            }
+            for (int i = tid; i < a; i += PC_THREADS) {
+                const cd v = W[(m - 1) * a + i];
+                W[(m - 1) * a + i] = make_double2(v.x * rprev, v.y * rprev);
+            }
+            __syncthreads();
+            // 4. r_i = 1 - sum_k |W_ki|^2 and R_i; a kept signal that the given ones explain entirely
+            if (PC_STEPS >= 4)
+                for (int i = tid; i < a; i += PC_THREADS) {
+                    double s = 0.0;
+                    int k = 0;
+                    for (; k + 3 < m; k += 4) {
+                        cd w[4];
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) w[u] = W[(k + u) * a + i];
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) s += w[u].x * w[u].x + w[u].y * w[u].y;
+                    }
+                    for (; k < m; ++k) {
+                        const cd w = W[k * a + i];
+                        s += w.x * w.x + w.y * w.y;
+                    }
+                    const double ri = 1.0 - s;
+                    const bool none = !(ri > (double)(m + 1) * 0x1p-52) || !isfinite(ri);
+                    r[i] = none ? qnan : 1.0 / sqrt(ri);           // (the two square roots per kept signal here, not per pair in step 5)
+                    da[i] = 1.0 / sqrt(da[i]);
+                    if (none) atomicAdd(g.fail + 1, 1);
+                    if (g.multiple) g.multiple[bin * a + i] = none ? 1.0 : sqrt(s);
+                }
+            __syncthreads();
+        }
+        // 5. outputs (6.: NaN everywhere for a failed problem): tile (ti >= tj) of 8 x 8 pairs per wave and step
+        cd* oc = g.coherency ? g.coherency + bin * a * a : nullptr;
+        double* om = g.magnitude ? g.magnitude + bin * a * a : nullptr;
+        const int wave = tid >> 6, li = (tid >> 3) & 7, lj = tid & 7;
+        const int T = (a + 7) >> 3, n_tiles = T * (T + 1) / 2;
+        for (int t = wave; t < (PC_STEPS >= 5 ? n_tiles : 0); t += PC_THREADS / 64) {
+            int ti, tj;
+            pc_unpack(t, ti, tj);
+            const int i = 8 * ti + li, j = 8 * tj + lj;
+            if (i >= a || j > i) continue;
+            double gx = qnan, gy = qnan;
+            if (!failed && i != j) {
+                const cd s = sc_csm_entry(rec, g.v, g.kept[i], g.kept[j]);
+                double sx = 0.0, sy = 0.0;                         // conj(W_ki) W_kj
+                int k = 0;
+                for (; k + 3 < m; k += 4) {
+                    cd p[4], q4[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) { p[u] = W[(k + u) * a + i]; q4[u] = W[(k + u) * a + j]; }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        sx += p[u].x * q4[u].x + p[u].y * q4[u].y;
+                        sy += p[u].x * q4[u].y - p[u].y * q4[u].x;
+                    }
+                }
+                for (; k < m; ++k) {
+                    const cd p = W[k * a + i], q1 = W[k * a + j];
+                    sx += p.x * q1.x + p.y * q1.y;
+                    sy += p.x * q1.y - p.y * q1.x;
+                }
+                const double ws = da[i] * da[j], w = r[i] * r[j];
+                gx = (s.x * ws - sx) * w; gy = (s.y * ws - sy) * w;
+            }
+            if (oc) {
+                oc[(int64_t)i * a + j] = make_double2(gx, gy);
+                if (i != j) oc[(int64_t)j * a + i] = make_double2(gx, -gy);
+            }
+            if (om) {
+                const double mag = i == j ? qnan : sqrt(gx * gx + gy * gy);
+                om[(int64_t)i * a + j] = mag;
+                if (i != j) om[(int64_t)j * a + i] = mag;
+            }
+        }
+        if (failed) {
+            if (g.multiple)
+                for (int i = tid; i < a; i += PC_THREADS) g.multiple[bin * a + i] = qnan;
+            if (tid == 0) atomicAdd(g.fail, 1);
+        }
+        __syncthreads();                                           // (the next problem overwrites everything)
+    }
+}
+
 }  // namespace
 
 extern "C" int sc_partial_coherence_max_signals(void) { return PC_MAX_C; }
@@ -258,6 +460,56 @@ extern "C" int sc_partial_coherence_f64(const void* d_accum, int64_t n_bins, int
     const int64_t want = (int64_t)256 * per_cu;
     const unsigned blocks = (unsigned)(n_bins < want ? n_bins : want);
     hipLaunchKernelGGL(partial_coherence_kernel, dim3(blocks), dim3(PC_THREADS), lds, st, a);
+    SC_CHECK_HIP(hipGetLastError());
+    return SC_OK;
+}
+
+extern "C" int sc_partial_given_max_given(void) { return PG_MAX_GIVEN; }
+extern "C" int sc_partial_given_max_kept(void) { return PG_MAX_KEPT; }
+extern "C" int64_t sc_partial_given_lds_limit(void) { return (int64_t)PG_LDS_LIMIT; }
+extern "C" int64_t sc_partial_given_lds_bytes(int64_t n_kept, int64_t n_given) {
+    if (n_kept < 1 || n_kept > PG_MAX_KEPT || n_given < 1 || n_given > PG_MAX_GIVEN) return -1;
+    return (int64_t)pg_lds_bytes(n_kept, n_given);
+}
+
+extern "C" int sc_partial_coherence_given_f64(const void* d_accum, int64_t n_bins, int64_t n_signals, uint32_t planes,
+                                              int64_t n_observations, const int32_t* d_kept, int n_kept, const int32_t* d_given,
+                                              int n_given, void* d_coherency, double* d_magnitude, double* d_multiple,
+                                              int32_t* d_fail, void* stream) {
+    ScTimed timed_("partial_coherence_given", stream);
+    SC_REQUIRE(d_accum && d_fail && d_kept && d_given, "NULL argument");
+    SC_REQUIRE(d_coherency || d_magnitude || d_multiple, "no output requested");
+    PartialGivenArgs g;
+    const int rcv = sc_csm_view(planes, n_bins, n_bins, n_signals, n_observations, &g.v);
+    if (rcv != SC_OK) return rcv;
+    SC_REQUIRE(n_bins >= 1, "empty problem");
+    if (n_given < 1 || n_given > PG_MAX_GIVEN || n_kept < 1 || n_kept > PG_MAX_KEPT || (int64_t)n_kept + n_given > n_signals) {
+        sc_set_error("invalid argument: partial coherence given a set takes 1 ... %d given and 1 ... %d kept signals out of the "
+                     "%lld of the record (got %d given, %d kept)", PG_MAX_GIVEN, PG_MAX_KEPT, (long long)n_signals, n_given, n_kept);
+        return SC_EINVAL;
+    }
+    // every LDS index of the kernel is a function of (a, m) alone, and pg_lds_bytes(a, m) fits here
+    const size_t lds = pg_lds_bytes(n_kept, n_given);
+    static_assert(pg_lds_bytes(PG_MAX_KEPT, 8) <= PG_LDS_LIMIT && pg_lds_bytes(512, 16) <= PG_LDS_LIMIT &&
+                  pg_lds_bytes(1, PG_MAX_GIVEN) <= PG_LDS_LIMIT, "the advertised sizes must fit LDS");
+    if (lds > PG_LDS_LIMIT) {
+        sc_set_error("invalid argument: %d kept signals given %d need %lld bytes of LDS, beyond the %lld of a compute unit", n_kept,
+                     n_given, (long long)lds, (long long)PG_LDS_LIMIT);
+        return SC_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    g.accum = sc_rec(d_accum, planes); g.a = n_kept; g.m = n_given; g.n_signals = (int)n_signals; g.n_bins = n_bins;
+    g.kept = d_kept; g.given = d_given;
+    g.coherency = static_cast<cd*>(d_coherency); g.magnitude = d_magnitude; g.multiple = d_multiple; g.fail = d_fail;
+    SC_CHECK_HIP(hipMemsetAsync(d_fail, 0, 8, st));
+    if (lds > 64 * 1024)
+        SC_CHECK_HIP(hipFuncSetAttribute((const void*)partial_given_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    // persistent workgroups: as many a compute unit as their LDS allows (at most 8: 2048 threads)
+    int per_cu = (int)(PG_LDS_LIMIT / lds);
+    per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
+    const int64_t want = (int64_t)256 * per_cu;
+    const unsigned blocks = (unsigned)(n_bins < want ? n_bins : want);
+    hipLaunchKernelGGL(partial_given_kernel, dim3(blocks), dim3(PC_THREADS), lds, st, g);
     SC_CHECK_HIP(hipGetLastError());
     return SC_OK;
 }

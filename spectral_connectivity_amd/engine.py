@@ -504,6 +504,12 @@ def partial_coherence(accum, n_signals, planes, n_obs, want):
     return _stage_d.partial_coherence(TorchMemory(accum.device), accum, n_signals, planes, n_obs, want)
 
 
+def partial_coherence_given(accum, n_signals, planes, n_obs, kept, given, want):
+    """Partial and multiple coherence of the signals ``kept`` given the signals ``given`` (sc_partial.hip):
+    _stage_d.partial_coherence_given.  Returns ({name: tensor} for the names in ``want``, (n_failed, n_explained))."""
+    return _stage_d.partial_coherence_given(TorchMemory(accum.device), accum, n_signals, planes, n_obs, kept, given, want)
+
+
 def jackknife(spectra, expectation_type, total, planes, measures, over, n_units_total, n_freq=None, unit_range=None):
     """Delete-one jackknife sums (sc_jackknife.hip) of the spectra against the total CSM record ``total`` (partial records are
     folded first): _stage_d.jackknife.  Returns (float64 device tensor laid out as _lib.jackknife_blocks says, n_bins)."""

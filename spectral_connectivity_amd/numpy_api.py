@@ -303,3 +303,14 @@ class Connectivity(_TorchHostConnectivity):
         res, n_fail = _stage_d.partial_coherence(mem, rec, C, _lib.PLANE_CSM, n_total, (name,))
         self._partial_failed(n_fail)
         return mem.download(res[name]).reshape(shape)
+
+    def _partial_coherence_given(self, name, given, signals):
+        kept, z, _, shape, dtype = self._partial_given_request(name, given, signals)
+        rec, n_obs, _ = self._csm_records("interaction", two_sided=False)
+        n_total = self._n_observations_total(n_obs)
+        if self._partial_given_few_observations(n_total, len(z)):
+            return np.full(shape, np.nan, dtype=dtype)
+        mem = self._memory()
+        res, counts = _stage_d.partial_coherence_given(mem, rec, self._shape5[4], _lib.PLANE_CSM, n_total, kept, z, (name,))
+        self._partial_given_failed(counts)
+        return mem.download(res[name]).reshape(shape)

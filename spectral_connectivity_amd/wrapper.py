@@ -43,6 +43,7 @@ _NOT_IN_DATASET = {
     "maximized_imaginary_coherence", "multivariate_interaction_measure", "jackknife",
     "partial_coherency", "partial_coherence_magnitude", "multiple_coherence_magnitude",
 }
+_PARTIAL = ("partial_coherency", "partial_coherence_magnitude", "multiple_coherence_magnitude")
 _MT_SKIP = {"time_series", "fft", "tapers", "frequencies", "time"}
 
 
@@ -72,6 +73,12 @@ def _to_dataarray(xr, m, connectivity, method, signal_names, squeeze, **kwargs):
     n_signals = m.time_series.shape[-1]
     names = list(np.arange(n_signals).astype(str)) if signal_names is None else signal_names
     values = getattr(connectivity, method)(**kwargs)
+    if method in _PARTIAL and (kwargs.get("given") is not None or kwargs.get("signals") is not None):
+        # a chosen conditioning set: the signal axes hold the kept signals only, in the order of `signals`
+        from . import _lib
+        kept, _ = _lib.partial_given_indices(kwargs.get("given"), kwargs.get("signals"), n_signals)
+        names = [names[k] for k in kept]
+        n_signals = len(names)
     if n_signals > 2 and squeeze:
         logger.warning(f"Squeeze is on, but there are {n_signals} pairs!")
     if method in ("power", "multiple_coherence_magnitude"):
