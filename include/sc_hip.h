@@ -764,6 +764,19 @@ int sc_stream_synchronize(void* stream);
 int sc_nonfinite_f32(const float* d_x, int64_t n, int32_t* d_flag, void* stream);
 int sc_nonfinite_f64(const double* d_x, int64_t n, int32_t* d_flag, void* stream);
 
+/* ---- amplitude range of the float32 engine -----------------------------------------------------------------------------------
+ * The float32 stage-B kernels square products of coefficients: (Im s)^2 is of the order |x|^4, which leaves the float32 range for
+ * coefficients of 1e-13 (MEG in tesla), and no float32 record can hold such a sum.  A host asks for the size of the coefficients
+ * before it sends such a request to the float32 kernels and accumulates a float64 record from a complex128 copy otherwise
+ * (spectral_connectivity_amd/_stage_abc.py: amplitude_guard, with the thresholds).
+ *   sc_amplitude_range_f32   dense complex64 rows [n_rows][C] -> d_out double[2][C]: sum |x_c|^2, max(|Re x_c|, |Im x_c|); partial
+ *                            sums folded in a fixed order (the same bits on every run); d_work: sc_amplitude_range_work_bytes
+ *   sc_spectra_widen_f32     n complex64 numbers -> complex128 (exact) */
+int64_t sc_amplitude_range_work_bytes(int64_t n_rows, int64_t C);
+int sc_amplitude_range_f32(const void* d_X /*float2*/, int64_t n_rows, int64_t C, double* d_out, void* d_work, int64_t work_bytes,
+                           void* stream);
+int sc_spectra_widen_f32(const void* d_X /*float2*/, int64_t n, void* d_out /*double2*/, void* stream);
+
 /* ---- Exchange of trial-sharded records over RCCL / xGMI (SURVEY section 8(b) `sc_allreduce`, 8(e)) ------------------------
  * The reference has no multi-device path (its CuPy backend is one GPU: transforms.py:405-439, connectivity.py:31-65); trials
  * shard over one process per GPU because the expectation is a plain sum of per-observation terms (connectivity.py:67-75,

@@ -210,6 +210,9 @@ SYMBOLS = {
     "sc_stream_synchronize": (c_int, [c_void_p]),
     "sc_nonfinite_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "sc_nonfinite_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "sc_amplitude_range_work_bytes": (c_int64, [c_int64, c_int64]),
+    "sc_amplitude_range_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "sc_spectra_widen_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -13,6 +13,7 @@ drivers here use:
     mem.fft_plan(n_fft, batch, f64)      context manager around ONE execution of a rocFFT plan: the PyTorch host hands out its cached
                                          plan; the torch-free host creates one, synchronises and destroys it
     mem.spectra(X, dims, strides, n_fft, real_input, C_alloc=, P=, scale=)      the host's spectra object (a subclass of Spectra)
+    mem.read_scales(spectra)             the 2 C_alloc floats of planes-format spectra's ``scale`` as a NumPy array (one small read-back)
 
 Nothing is released explicitly: the torch-free host's buffers go back to its pool with their last reference (DeviceBuffer.__del__),
 which for ``work``, ``y`` and the workspace is the driver's return -- no later than the explicit frees that host had.  No driver reads
@@ -23,6 +24,7 @@ in ``accumulate`` (and its bit in ``_lib``): both hosts get it through their one
 """
 import ctypes
 from ctypes import byref, c_int64
+from logging import getLogger
 
 import numpy as np
 
@@ -30,6 +32,7 @@ from . import _lib
 from ._lib import EXPECTATION_AXES, SpectraDesc
 from ._stage_d import _ptr
 
+logger = getLogger(__name__)
 DETREND_ERROR = ("Invalid trend type '{}' is not supported.\n"
                  "Valid options are 'linear'/'l', 'constant'/'c' or None.")
 NONFINITE_WARNING = ("Input time_series contains NaN or infinite values.\n"
@@ -87,6 +90,7 @@ class Spectra:
         self.real_input = bool(real_input)   # negative bins are conj mirrors of positive ones
         self.f64 = bool(f64)
         self.quality = self.taper_l2_min = None
+        self._amplitude = self._amplitude_scales = self._widened = None      # amplitude_guard: measured / widened once per object
 
     @property
     def X(self):
@@ -224,6 +228,123 @@ def decode_planes(mem, sp):
     return X
 
 
+# ---- amplitude range of the float32 engine -----------------------------------------------------------------------------------------
+# Two accumulator families form quantities a float32 number cannot hold for coefficients x far from 1.  (Im s)^2 is of the order
+# |x_i|^2 |x_j|^2: float32's smallest normal number is 2^-126, so a product d = Im s with |d| < 2^-63 has a square that is subnormal or
+# 0 -- and no float32 RECORD can hold the sum either, whatever the kernel does.  Let t_c be the root mean square of channel c's
+# coefficients.  The products of a pair spread around t_i t_j; one 2^8 times smaller contributes 2^-16 of a typical term to the sum
+# of squares, far below the 1e-5 the records are held to, so only products down to 2^-8 t_i t_j need a normal square:
+# t_i t_j >= 2^(-63 + 8) = 2^-55 for every pair, i.e. for the two quietest live channels.  At the other end squares overflow from
+# |d| = 2^64; with 2^10 for the sum over up to a million observations the two largest coefficients must satisfy m_i m_j <= 2^54.
+# s / |s| is formed from the unit phasors x / |x| of the factors (every route), whose |x|^2 must stay normal: coefficients down
+# to 2^-12 of the typical one (one in 2^24 for Gaussian data) need |x| >= 2^-63, so t_c >= 2^-51; and m_c <= 2^60 keeps |x|^2 finite.
+# Volts (1e-6) and 24-bit ADC counts are far inside; tesla (1e-13) is outside for (Im s)^2 and inside for s / |s|.
+IM_SQ_MIN_PAIR_TYPICAL, IM_SQ_MAX_PAIR_LARGEST = 2.0 ** -55, 2.0 ** 54
+UNIT_MIN_TYPICAL, UNIT_MAX_LARGEST = 2.0 ** -51, 2.0 ** 60
+# Planes format: the kernel sums (Im s)^2 of the SCALED coefficients x * scale[c] (typical size >= 2.5 by the format's quality check, at
+# most 2^12: sc_fused2.hip) and multiplies the sum by (inv_i inv_j)^2, inv = 1 / scale, on the way out.  Nothing is estimated: the
+# factor itself must be a normal float32, (inv_i inv_j)^2 >= 2^-124, i.e. inv_i inv_j >= 2^-62 for the two smallest; and the largest
+# entry, at most n_obs 2^50 (inv_i inv_j)^2, must stay finite: inv_i inv_j <= 2^28 covers 2^20 observations per bin.
+PLANES_MIN_PAIR_INVERSE, PLANES_MAX_PAIR_INVERSE = 2.0 ** -62, 2.0 ** 28
+SQUARING_PLANES = _lib.PLANE_IM_SQ | _lib.PLANE_UNIT
+
+
+def _span(sp):
+    """Elements from the first to the last coefficient of the spectra (their rows are dense: every stride a multiple of C_alloc)."""
+    return sum((n - 1) * st for n, st in zip((sp.F, sp.W, sp.R, sp.K), sp.strides)) + sp.C_alloc
+
+
+def amplitude_range(mem, sp):
+    """(typical, largest) coefficient magnitude per channel of complex64 spectra, NumPy float64 [C]: the root mean square and the
+    largest |Re|, |Im| from one reduction over them (sc_amplitude_range_f32).  One small read-back, kept on the spectra object."""
+    if sp._amplitude is None:
+        lib = _lib._handle()
+        X = sp.X
+        assert all(st % sp.C_alloc == 0 for st in sp.strides), "the amplitude scan needs spectra whose rows are dense"
+        n_rows = _span(sp) // sp.C_alloc
+        work_bytes = int(lib.sc_amplitude_range_work_bytes(n_rows, sp.C_alloc))
+        work, out = mem.empty((work_bytes,), np.uint8), mem.empty((2, sp.C_alloc), np.float64)
+        _lib.check(lib.sc_amplitude_range_f32(mem.ptr(X), n_rows, sp.C_alloc, mem.ptr(out), mem.ptr(work), work_bytes,
+                                              mem.stream()), "sc_amplitude_range_f32")
+        both = np.asarray(mem.download(out), dtype=np.float64).reshape(2, sp.C_alloc)[:, :sp.C]
+        sp._amplitude = (np.sqrt(both[0] / n_rows), both[1])
+    return sp._amplitude
+
+
+def amplitude_out_of_range(typical, largest, planes):
+    """Why the float32 kernels cannot take ``planes`` for channels of these magnitudes (a sentence), or None.  Silent channels
+    (all zero: every product is an exact 0) and channels with NaN / infinite coefficients (non-finite on either engine) do not count."""
+    live = np.isfinite(typical) & np.isfinite(largest) & (typical > 0)
+    t, m = np.sort(typical[live]), np.sort(largest[live])
+    if planes & _lib.PLANE_IM_SQ and t.size >= 2:
+        if t[0] * t[1] < IM_SQ_MIN_PAIR_TYPICAL:
+            return (f"(Im s)^2 of the two quietest channels (typical coefficients {t[0]:.3g}, {t[1]:.3g}) is below the float32 range")
+        if m[-1] * m[-2] > IM_SQ_MAX_PAIR_LARGEST:
+            return (f"(Im s)^2 of the two largest channels (coefficients up to {m[-1]:.3g}, {m[-2]:.3g}) is above the float32 range")
+    if planes & _lib.PLANE_UNIT and t.size >= 1:
+        if t[0] < UNIT_MIN_TYPICAL:
+            return f"|x|^2 of the quietest channel (typical coefficient {t[0]:.3g}) is below the float32 range"
+        if m[-1] > UNIT_MAX_LARGEST:
+            return f"|x|^2 of the largest channel (coefficients up to {m[-1]:.3g}) is above the float32 range"
+    return None
+
+
+def planes_scales_out_of_range(inverse, planes):
+    """The same question for spectra only the planes format holds, from the reciprocals of its channel scales (derivation above)."""
+    inv = np.sort(inverse[np.isfinite(inverse) & (inverse > 0)])
+    if planes & _lib.PLANE_IM_SQ and inv.size >= 2:
+        if inv[0] * inv[1] < PLANES_MIN_PAIR_INVERSE:
+            return f"the factor that unscales (Im s)^2 of the two quietest channels (1 / scale {inv[0]:.3g}, {inv[1]:.3g}) is below the float32 range"
+        if inv[-1] * inv[-2] > PLANES_MAX_PAIR_INVERSE:
+            return f"(Im s)^2 of the two largest channels (1 / scale {inv[-1]:.3g}, {inv[-2]:.3g}) is above the float32 range"
+    return None
+
+
+def amplitude_verdict(mem, sp, planes):
+    """Why this float32 request must be accumulated in float64 (a sentence), or None; nothing is measured for a request without
+    (Im s)^2 or s / |s|, or for complex128 spectra.  The measurement is kept on the spectra object, the verdict is per request."""
+    if sp.f64 or not planes & SQUARING_PLANES:
+        return None
+    if sp._X is None and not planes & _lib.PLANE_UNIT:
+        if sp._amplitude_scales is None:
+            sp._amplitude_scales = np.asarray(mem.read_scales(sp), dtype=np.float64).reshape(-1)[sp.C_alloc:sp.C_alloc + sp.C]
+        return planes_scales_out_of_range(sp._amplitude_scales, planes)
+    return amplitude_out_of_range(*amplitude_range(mem, sp), planes)
+
+
+def widen(mem, sp):
+    """complex128 spectra with the values of complex64 (or planes-format) ones: same geometry, the float64 engine's kernels apply."""
+    X = sp._X if sp._X is not None else decode_planes(mem, sp)
+    n = _span(sp)
+    shape = getattr(X, "shape", None)              # (a tensor keeps its five axes: the channel-block tiling gathers along the last)
+    Xw = mem.empty(tuple(shape) if shape is not None and int(np.prod(shape)) == n else (n,), np.complex128)
+    _lib.check(_lib._handle().sc_spectra_widen_f32(mem.ptr(X), n, mem.ptr(Xw), mem.stream()), "sc_spectra_widen_f32")
+    return mem.spectra(Xw, (sp.F, sp.W, sp.R, sp.K, sp.C), sp.strides, sp.n_fft, sp.real_input, C_alloc=sp.C_alloc)
+
+
+def amplitude_guard(mem, sp, planes, decided=None):
+    """The spectra a float32-engine request for ``planes`` is accumulated from: ``sp`` itself while the families that square products
+    ((Im s)^2, s / |s|) stay inside the float32 range for its channels (thresholds above) -- in-range data never leave the float32
+    kernels --, otherwise a complex128 copy (made once, kept on ``sp``), from which stage B writes a float64 record with the float64
+    engine's kernels; one line is logged.  Every consumer of records takes either kind.  The verdict is taken per request: a later
+    request that is in range runs on ``sp`` again.  ``decided``: the verdict of a GROUP of processes (True: widen), taken by the
+    caller so that every rank accumulates the same kind of record; None: this process decides for itself.  The hosts call this
+    before stage B (engine.accumulate, NumpyHost._accumulate_record); ``accumulate`` below takes the spectra as they come."""
+    if sp.f64 or not planes & SQUARING_PLANES:
+        return sp
+    if decided is None:
+        why = amplitude_verdict(mem, sp, planes)
+        decided = why is not None
+    else:
+        why = "(Im s)^2 or |x|^2 is outside the float32 range on a process of the group"
+    if not decided:
+        return sp
+    if sp._widened is None:
+        sp._widened = widen(mem, sp)
+    logger.warning("spectral_connectivity_amd: %s: this request is accumulated by the float64 engine", why)
+    return sp._widened
+
+
 # ---- stage B ---------------------------------------------------------------------------------------------------------------------
 def accum_layout(sp, expectation_type, planes, n_freq=None):
     """(n_bins, floats per bin, n_groups, n_observations) of the record of ``planes``."""
@@ -241,7 +362,7 @@ def accumulate(mem, sp, expectation_type, planes, n_freq=None, which=None, out=N
     ``out`` already.  ``fold=False`` (planes format, no ``out``): where the kernel split every bin over several workgroups their
     partial records are kept -- the result is then 3-D, [n_parts, n_bins, floats_per_bin], parts in the order their sum is taken.
     ``use_fused=False``: every plane through its separate kernel.  At most 256 signals, or planes-format spectra of a family their
-    kernels take: the callers see to that."""
+    kernels take: the callers see to that, and to the amplitude range of the float32 kernels (amplitude_guard)."""
     lib, mark = _lib._handle(), mark or (lambda name: None)
     d = sp.desc(expectation_type, n_freq)
     n_bins, fpb, _, n_obs = accum_layout(sp, expectation_type, planes, n_freq)

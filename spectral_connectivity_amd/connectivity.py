@@ -244,7 +244,8 @@ class Connectivity:
             planes = _lib.PLANE_CSM | _lib.PLANE_ABS_IM
         # single process, float32 engine on the planes format: the split-bin partial records stay unfolded (a 3-D tensor) and
         # the epilogue sums them while it reads -- the path bench.py times
-        accum, n_obs = engine.accumulate(sp, self.expectation_type, planes, n_freq=self._n_freq, have=have, fold=not single)
+        accum, n_obs = engine.accumulate(self._guard_spectra(sp, planes), self.expectation_type, planes, n_freq=self._n_freq, have=have,
+                                         fold=not single, guard=False)
         accum = self._reduce_over_ranks(accum)
         if have is not None:
             del self._accum_cache[have[0]]
@@ -267,6 +268,12 @@ class Connectivity:
             self._accum_cache[key] = (self._reduce_over_ranks(accum), n_obs)
         accum, n_obs = self._accum_cache[key]
         return accum, n_obs, n_freq
+
+    def _guard_spectra(self, sp, planes):
+        """The spectra this request is accumulated from: a complex128 copy when (Im s)^2 or s / |s| would leave the float32 range
+        (engine.guarded_spectra); parallel.ShardedConnectivity takes the decision once for its group."""
+        from . import engine
+        return engine.guarded_spectra(sp, planes)
 
     def _reduce_over_ranks(self, accum):
         """Sum of the records over the processes that hold the trials: nothing to add here; parallel.ShardedConnectivity

@@ -170,3 +170,87 @@ extern "C" int sc_nonfinite_f64(const double* d_x, int64_t n, int32_t* d_flag, v
     SC_CHECK_HIP(hipGetLastError());
     return SC_OK;
 }
+
+// ---- amplitude range of complex64 spectra and their complex128 copy: the float32 engine's guard (_stage_abc.amplitude_guard) ------
+// A float32 record cannot hold sums of (Im s)^2 ~ |x|^4 for coefficients of 1e-13 (MEG in tesla).  Before a request that squares
+// products runs on the float32 kernels, the host asks for the per-channel size of the coefficients: d_out[0][c] = sum |x_c|^2 (in
+// double: the squares themselves leave the float32 range) and d_out[1][c] = max(|Re x_c|, |Im x_c|) over dense rows [n_rows][C].
+// Two launches, partial sums per row slice folded in slice order: the same bits on every run (the statistic picks the engine).
+#define SC_AMP_PARTS_MAX 1024
+
+static int amp_parts(int64_t n_rows) {
+    const int64_t want = (n_rows + 3) / 4;
+    return (int)(want < 1 ? 1 : want > SC_AMP_PARTS_MAX ? SC_AMP_PARTS_MAX : want);
+}
+
+__global__ void __launch_bounds__(256) amplitude_part_kernel(const float2* __restrict__ X, int64_t n_rows, int C,
+                                                             double* __restrict__ part /*[gridDim.y][2][C]*/) {
+    __shared__ double s_sq[4][64];
+    __shared__ float s_mx[4][64];
+    const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + cx;
+    double sq = 0.0;
+    float mx = 0.f;
+    if (c < C)
+        for (int64_t r = (int64_t)blockIdx.y * 4 + ry; r < n_rows; r += (int64_t)gridDim.y * 4) {
+            const float2 v = X[r * C + c];
+            sq += (double)v.x * (double)v.x + (double)v.y * (double)v.y;
+            mx = fmaxf(mx, fmaxf(fabsf(v.x), fabsf(v.y)));
+        }
+    s_sq[ry][cx] = sq;
+    s_mx[ry][cx] = mx;
+    __syncthreads();
+    if (ry == 0 && c < C) {
+        part[((int64_t)blockIdx.y * 2 + 0) * C + c] = (s_sq[0][cx] + s_sq[1][cx]) + (s_sq[2][cx] + s_sq[3][cx]);
+        part[((int64_t)blockIdx.y * 2 + 1) * C + c] = (double)fmaxf(fmaxf(s_mx[0][cx], s_mx[1][cx]), fmaxf(s_mx[2][cx], s_mx[3][cx]));
+    }
+}
+
+__global__ void amplitude_fold_kernel(const double* __restrict__ part, int n_parts, int C, double* __restrict__ out /*[2][C]*/) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    double sq = 0.0, mx = 0.0;
+    for (int k = 0; k < n_parts; ++k) {
+        sq += part[((int64_t)k * 2 + 0) * C + c];
+        mx = fmax(mx, part[((int64_t)k * 2 + 1) * C + c]);
+    }
+    out[c] = sq;
+    out[C + c] = mx;
+}
+
+extern "C" int64_t sc_amplitude_range_work_bytes(int64_t n_rows, int64_t C) {
+    if (n_rows < 1 || C < 1) return 0;
+    return (int64_t)amp_parts(n_rows) * 2 * C * (int64_t)sizeof(double);
+}
+
+extern "C" int sc_amplitude_range_f32(const void* d_X, int64_t n_rows, int64_t C, double* d_out, void* d_work, int64_t work_bytes,
+                                      void* stream) {
+    SC_REQUIRE(d_X && d_out && d_work, "NULL argument");
+    SC_REQUIRE(n_rows >= 1 && C >= 1 && C <= (1 << 20), "empty or oversized dimension");
+    SC_REQUIRE(work_bytes >= sc_amplitude_range_work_bytes(n_rows, C), "workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    const int parts = amp_parts(n_rows);
+    hipLaunchKernelGGL(amplitude_part_kernel, dim3((unsigned)((C + 63) / 64), (unsigned)parts), dim3(256), 0, s, (const float2*)d_X,
+                       n_rows, (int)C, (double*)d_work);
+    hipLaunchKernelGGL(amplitude_fold_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, (const double*)d_work, parts, (int)C,
+                       d_out);
+    SC_CHECK_HIP(hipGetLastError());
+    return SC_OK;
+}
+
+// d_out[i] = (double) d_X[i], i < n complex numbers: the complex128 copy of complex64 spectra (exact)
+__global__ void widen_kernel(const float2* __restrict__ X, int64_t n, double2* __restrict__ out) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        const float2 v = X[i];
+        out[i] = make_double2((double)v.x, (double)v.y);
+    }
+}
+
+extern "C" int sc_spectra_widen_f32(const void* d_X, int64_t n, void* d_out, void* stream) {
+    SC_REQUIRE(d_X && d_out && n >= 1, "NULL argument or empty spectra");
+    const int grid = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
+    hipLaunchKernelGGL(widen_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float2*)d_X, n, (double2*)d_out);
+    SC_CHECK_HIP(hipGetLastError());
+    return SC_OK;
+}

@@ -106,6 +106,17 @@ __device__ __forceinline__ void md_passes_wave(cd* z, const cd* tw, int lane) {
     }
 }
 
+// Pair normalisation (what mt_pair_scale does in the float32 kernels): two real channels ride through ONE complex transform and
+// are separated by conjugate symmetry, so the rounding of the larger one lands on the smaller -- an MEG channel in tesla beside a
+// trigger channel of order one lost ten of its sixteen digits.  Each channel is multiplied by the power of two that brings the largest
+// |sample| of its detrended window to [1, 2) (exact) and its bins by the inverse on the way out (exact).  ``mx``: bit pattern of
+// the largest finite |sample|, 0 for a silent channel.
+__device__ __forceinline__ double md_pair_scale(unsigned long long mx, bool inverse) {
+    long long e = 2046 - (long long)(mx >> 52);                   // biased exponent of the scale
+    e = e < 1 ? 1 : (e > 2045 ? 2045 : e);
+    return __longlong_as_double((inverse ? 2046 - e : e) << 52);
+}
+
 template <int N, int NF>
 __global__ void __launch_bounds__(64 * NF) mtfft_f64_kernel(MdArgs p) {
     constexpr int NT = 64 * NF, CT = 2 * NF, XS = CT + 1, F = N / 2 + 1;
@@ -116,8 +127,9 @@ __global__ void __launch_bounds__(64 * NF) mtfft_f64_kernel(MdArgs p) {
     cd* tw = z + (NF * N > (NT + CT) ? NF * N : (NT + CT));       // [N]
     double* tile = reinterpret_cast<double*>(tw + N);             // [L][XS] (odd stride: the column walks of the trend sums)
     __shared__ int nzf[CT], nbf[CT];                              // channel not identically zero after the detrend / holds a non-finite sample
+    __shared__ unsigned long long mxc[CT];                        // largest finite |detrended sample| of the channel in this window
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid < CT) { nzf[tid] = 0; nbf[tid] = 0; }
+    if (tid < CT) { nzf[tid] = 0; nbf[tid] = 0; mxc[tid] = 0ull; }
     const int L = p.L, C = p.C;
     const int c0 = blockIdx.x * CT, r = blockIdx.y, w = blockIdx.z;
     const int64_t RC = (int64_t)p.R * C;
@@ -182,15 +194,20 @@ __global__ void __launch_bounds__(64 * NF) mtfft_f64_kernel(MdArgs p) {
         const bool nz = orv != 0ull, bad = mxv >= 0x7ff0000000000000ull;
         if (nz) nzf[cc] = 1;                                      // (plain stores of a constant: many threads may set the same flag)
         if (bad) nbf[cc] = 1;
+        if (nz && !bad) atomicMax(&mxc[cc], mxv);
         __syncthreads();
         if (nbf[cc]) {
             for (int l = sl; l < L; l += SL) tile[l * XS + cc] = 0.0;
+        } else {                                                  // pair normalisation (md_pair_scale): exact, undone at the store
+            const double sc = md_pair_scale(mxc[cc], false);
+            for (int l = sl; l < L; l += SL) tile[l * XS + cc] *= sc;
         }
         __syncthreads();
     }
     // flags of the pair this thread stores (the store loop advances by NT, a multiple of NF: the pair never changes)
     const int spr = 2 * (tid & (NF - 1));
     const bool na = nbf[spr] != 0, nb = nbf[spr + 1] != 0, za = !na && nzf[spr] == 0, zb = !nb && nzf[spr + 1] == 0;
+    const double ha = 0.5 * md_pair_scale(mxc[spr], true), hb = 0.5 * md_pair_scale(mxc[spr + 1], true);   // back to the samples' units
     const int64_t sF = (int64_t)p.W * p.R * p.K * C;
     cd* zw = z + wave * N;                                        // this wave's pair
     for (int k = 0; k < p.K; ++k) {
@@ -211,8 +228,8 @@ __global__ void __launch_bounds__(64 * NF) mtfft_f64_kernel(MdArgs p) {
             const int f = idx >> LNF, pr = idx & (NF - 1), c = c0 + 2 * pr;
             if (c >= C) continue;
             const cd u1 = z[pr * N + f], u2 = z[pr * N + (f == 0 ? 0 : N - f)];
-            cd A = make_double2(0.5 * (u1.x + u2.x), 0.5 * (u1.y - u2.y));
-            cd B = make_double2(0.5 * (u1.y + u2.y), 0.5 * (u2.x - u1.x));
+            cd A = make_double2(ha * (u1.x + u2.x), ha * (u1.y - u2.y));
+            cd B = make_double2(hb * (u1.y + u2.y), hb * (u2.x - u1.x));
             if (za) A = make_double2(0.0, 0.0);
             if (zb) B = make_double2(0.0, 0.0);
             if (na) A = make_double2(__longlong_as_double(0x7ff8000000000000LL), __longlong_as_double(0x7ff8000000000000LL));
@@ -247,8 +264,9 @@ __global__ void __launch_bounds__(256, 2) mtfft16_f64_kernel(MdArgs p, int kh) {
     cd* tw = reinterpret_cast<cd*>(smem + UNION_BYTES);                           // [N] twiddles
     double* hk = reinterpret_cast<double*>(tw + N);                               // [kh][L] tapers (kh = K, or 2 buffers)
     __shared__ int nzf[CT], nbf[CT];
+    __shared__ unsigned long long mxc[CT];                        // largest finite |detrended sample| of the channel in this window
     const int tid = threadIdx.x;
-    if (tid < CT) { nzf[tid] = 0; nbf[tid] = 0; }
+    if (tid < CT) { nzf[tid] = 0; nbf[tid] = 0; mxc[tid] = 0ull; }
     const int L = p.L, C = p.C;
     const int c0 = blockIdx.x * CT, r = blockIdx.y, w = blockIdx.z;
     const int64_t RC = (int64_t)p.R * C;
@@ -332,16 +350,20 @@ __global__ void __launch_bounds__(256, 2) mtfft16_f64_kernel(MdArgs p, int kh) {
         if (or0 != 0ull) nzf[2 * pf] = 1;
         if (or1 != 0ull) nzf[2 * pf + 1] = 1;
         if (mx0 >= 0x7ff0000000000000ull) nbf[2 * pf] = 1;
+        else if (or0 != 0ull) atomicMax(&mxc[2 * pf], mx0);
         if (mx1 >= 0x7ff0000000000000ull) nbf[2 * pf + 1] = 1;
+        else if (or1 != 0ull) atomicMax(&mxc[2 * pf + 1], mx1);
     }
     __syncthreads();                                          // tile and detrend scratch consumed: their space is free
-    if (nbf[2 * pf]) {
+    {
+        // a non-finite channel leaves the packed transform; every other one is normalised (md_pair_scale: exact, undone at the store)
+        const double s0 = nbf[2 * pf] ? 0.0 : md_pair_scale(mxc[2 * pf], false);
+        const double s1 = nbf[2 * pf + 1] ? 0.0 : md_pair_scale(mxc[2 * pf + 1], false);
 #pragma unroll
-        for (int t = 0; t < 16; ++t) xs[t].x = 0.0;
-    }
-    if (nbf[2 * pf + 1]) {
-#pragma unroll
-        for (int t = 0; t < 16; ++t) xs[t].y = 0.0;
+        for (int t = 0; t < 16; ++t) {
+            xs[t].x = nbf[2 * pf] ? 0.0 : xs[t].x * s0;
+            xs[t].y = nbf[2 * pf + 1] ? 0.0 : xs[t].y * s1;
+        }
     }
     const int spr = 2 * (tid & (NF - 1));                     // the pair this thread stores
     const bool na = nbf[spr] != 0, nb = nbf[spr + 1] != 0, za = !na && nzf[spr] == 0, zb = !nb && nzf[spr + 1] == 0;
@@ -470,9 +492,11 @@ __global__ void __launch_bounds__(256, 2) mtfft16_f64_kernel(MdArgs p, int kh) {
         const int pr = tid & (NF - 1), fb = tid / NF, c = c0 + 2 * pr;
         if (c < C) {
             const cd* zp = z + pr * ZS;
+            // back to the samples' units (read from LDS here, not kept in registers across the passes)
+            const double ha = 0.5 * md_pair_scale(mxc[2 * pr], true), hb = 0.5 * md_pair_scale(mxc[2 * pr + 1], true);
             auto put = [&](int f, cd u1, cd u2) {
-                cd A = make_double2(0.5 * (u1.x + u2.x), 0.5 * (u1.y - u2.y));
-                cd B = make_double2(0.5 * (u1.y + u2.y), 0.5 * (u2.x - u1.x));
+                cd A = make_double2(ha * (u1.x + u2.x), ha * (u1.y - u2.y));
+                cd B = make_double2(hb * (u1.y + u2.y), hb * (u2.x - u1.x));
                 if (za) A = make_double2(0.0, 0.0);
                 if (zb) B = make_double2(0.0, 0.0);
                 if (na) A = make_double2(qnan, qnan);

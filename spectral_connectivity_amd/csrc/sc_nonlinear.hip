@@ -92,6 +92,18 @@ __global__ void __launch_bounds__(256) nonlinear_kernel(NlArgs p) {
                     xi[2] = make_float2(i1.x, i1.y); xi[3] = make_float2(i1.z, i1.w);
                     xj[0] = make_float2(j0.x, j0.y); xj[1] = make_float2(j0.z, j0.w);
                     xj[2] = make_float2(j1.x, j1.y); xj[3] = make_float2(j1.z, j1.w);
+                    // s / |s| as the product of the unit phasors x / |x| (what sc_fused.hip sums): every FACTOR is normalised, so
+                    // nothing of the order |x|^4 is formed -- rsqrtf(|s|^2) left the float32 range for |x| below 1e-10
+                    float2 ui[4], uj[4];
+                    if constexpr (WHICH & SC_PLANE_UNIT) {
+#pragma unroll
+                        for (int a = 0; a < 4; ++a) {
+                            const float ia = rsqrtf(xi[a].x * xi[a].x + xi[a].y * xi[a].y);   // 0 -> inf -> 0*inf = NaN
+                            const float ib = rsqrtf(xj[a].x * xj[a].x + xj[a].y * xj[a].y);
+                            ui[a] = make_float2(xi[a].x * ia, xi[a].y * ia);
+                            uj[a] = make_float2(xj[a].x * ib, xj[a].y * ib);
+                        }
+                    }
 #pragma unroll
                     for (int a = 0; a < 4; ++a) {
 #pragma unroll
@@ -105,10 +117,8 @@ __global__ void __launch_bounds__(256) nonlinear_kernel(NlArgs p) {
                                 ++q;
                             }
                             if constexpr (WHICH & SC_PLANE_UNIT) {
-                                const float rev = xi[a].x * xj[b].x + xi[a].y * xj[b].y;
-                                const float inv = rsqrtf(rev * rev + imv * imv);  // 0 -> inf -> 0*inf = NaN
-                                acc[s][q][a * 4 + b] += rev * inv;
-                                acc[s][q + 1][a * 4 + b] += imv * inv;
+                                acc[s][q][a * 4 + b] += ui[a].x * uj[b].x + ui[a].y * uj[b].y;
+                                acc[s][q + 1][a * 4 + b] += ui[a].y * uj[b].x - ui[a].x * uj[b].y;
                             }
                         }
                     }

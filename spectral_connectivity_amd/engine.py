@@ -196,6 +196,9 @@ class TorchMemory:
     def is_f64(self, record):
         return record.dtype == torch.float64
 
+    def read_scales(self, spectra):
+        return spectra.scale.cpu().numpy()
+
     def fill_nan(self, t):
         t.fill_(float("nan"))
 
@@ -330,7 +333,9 @@ def _accumulate_blocked(spectra, expectation_type, planes, n_freq, mark, row_mul
     dev = spectra.device
     for _, _, cols, src, dst in _lib.tile_plan(C):
         sub = _channel_subset(spectra, torch.as_tensor(cols, device=dev))
-        rec, _ = accumulate(sub, expectation_type, planes, n_freq=n_freq, mark=mark)
+        rec, _ = accumulate(sub, expectation_type, planes, n_freq=n_freq, mark=mark, guard=False)    # (decided for the whole array)
+        if rec.dtype != full.dtype:
+            raise _lib.HipEngineError(f"a channel-block record came back as {rec.dtype}, the tiled record is {full.dtype}")
         nb_s = -(-sub.C // 16)
         rec_v = rec.view(n_bins, n_planes, nb_s * (nb_s + 1) // 2, 256)
         full_v[:, :, torch.tensor(dst, device=dev)] = rec_v[:, :, torch.tensor(src, device=dev)]
@@ -338,8 +343,19 @@ def _accumulate_blocked(spectra, expectation_type, planes, n_freq, mark, row_mul
     return full, n_obs
 
 
+def out_of_range(spectra, planes):
+    """Does this process find the float32 request ``planes`` outside the amplitude range of the float32 kernels
+    (_stage_abc.amplitude_verdict)?  What a group of processes reduces (MAX) before it calls guarded_spectra with the result."""
+    return _stage_abc.amplitude_verdict(TorchMemory(spectra.device), spectra, planes) is not None
+
+
+def guarded_spectra(spectra, planes, decided=None):
+    """_stage_abc.amplitude_guard on this host: ``spectra``, or their complex128 copy when the request is out of range."""
+    return _stage_abc.amplitude_guard(TorchMemory(spectra.device), spectra, planes, decided)
+
+
 def accumulate(spectra, expectation_type, planes, n_freq=None, mark=None, use_fused=None, row_multiple=1, have=None,
-               fold=True, ws_owner=None):
+               fold=True, ws_owner=None, guard=True):
     """Stage B: un-normalised accumulator record tensor [n_bins, floats_per_bin] (float32; float64 records from
     complex128 spectra) -- one call of _stage_abc.accumulate; what is tensor arithmetic of this host happens around it.
     ``row_multiple``: see _record_tensor (trial-sharded callers pass the world size).
@@ -350,7 +366,14 @@ def accumulate(spectra, expectation_type, planes, n_freq=None, mark=None, use_fu
     ``have`` = (planes_old, record_old), float64 engine only: families already accumulated for the same spectra and
     expectation are copied over (a strided device copy) and only the missing ones are computed -- its CSM and
     per-observation planes are separate kernels, so a wPLI after a coherence costs the |Im s| plane alone.
-    ``ws_owner``: see _workspace (a dict that owns the split-bin scratch of this call instead of the per-device cache)."""
+    ``ws_owner``: see _workspace (a dict that owns the split-bin scratch of this call instead of the per-device cache).
+    ``guard``: a float32 request whose (Im s)^2 or s / |s| would leave the float32 range is accumulated from a complex128 copy
+    of the spectra and comes back as a float64 record, padded rows and channel-block tiling included (_stage_abc.amplitude_guard:
+    one reduction over the spectra and one small read-back per spectra object, for requests with these families only).  False:
+    the caller has decided already -- trial-sharded callers decide once for their group (parallel.group_guarded_spectra), the
+    tiling for the whole array; a captured pass cannot read back and is not guarded either (``ws_owner``)."""
+    if guard and ws_owner is None:
+        spectra = guarded_spectra(spectra, planes)
     if spectra.C > _stage_abc.MAX_KERNEL_SIGNALS:
         # planes-format spectra go straight to sc_fused2.hip, which plans its launches over any number of 32-channel blocks (round 6);
         # every other request beyond 256 signals is tiled over channel-block pairs

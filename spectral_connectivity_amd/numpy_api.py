@@ -157,7 +157,6 @@ class Connectivity(_TorchHostConnectivity):
         m = wide.multitaper
         NB = -(-wide.C // 16)
         full, n_obs_out = None, None
-        dt = np.dtype(np.float64 if wide.f64 else np.float32)
         for _, _, cols, src, dst in _lib.tile_plan(wide.C):
             sub_m = _channel_subset_multitaper(m, cols)
             sp = host().spectra_f64(sub_m) if wide.f64 else host().spectra(sub_m)
@@ -166,13 +165,16 @@ class Connectivity(_TorchHostConnectivity):
             nb_s = -(-len(cols) // 16)
             nt_s = nb_s * (nb_s + 1) // 2
             n_bins = part.shape[0]
+            dt = np.dtype(part.dtype)      # (float32 engine: float64 for a block pair outside the float32 range, _stage_abc.amplitude_guard)
             rec = np.array(host().download(part.buf, (n_bins, part.shape[1] // (nt_s * 256), nt_s, 256), dt))
             del part
             if full is None:
                 full, n_obs_out = np.zeros((n_bins, rec.shape[1], NB * (NB + 1) // 2, 256), dtype=dt), n_obs
+            elif dt.itemsize > full.dtype.itemsize:
+                full = full.astype(dt)
             full[:, :, dst] = rec[:, :, src]
         full = full.reshape(full.shape[0], -1)
-        return _Record(host().upload(full), full.shape, dt), n_obs_out
+        return _Record(host().upload(full), full.shape, full.dtype), n_obs_out
 
     def _accumulators(self, planes, defer_checks=False):
         for have, rec in self._accum_cache.items():

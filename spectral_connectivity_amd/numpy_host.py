@@ -128,6 +128,9 @@ class NumpyMemory:
     def is_f64(self, record):
         return record.f64
 
+    def read_scales(self, spectra):
+        return np.array(self.host.download(spectra.scale, (2 * spectra.C_alloc,), np.float32))
+
     def fill_nan(self, a):
         src = np.full(a.shape, np.nan, dtype=a.dtype)
         _lib.check(self.host.lib.sc_memcpy_h2d(a.buf.ptr, src.ctypes.data_as(c_void_p), src.nbytes, self.host.stream), "sc_memcpy_h2d")
@@ -393,6 +396,8 @@ class NumpyHost:
         if sp.P is not None and not _stage_abc.fused2_takes(sp.desc(expectation_type, n_freq, padded=True), planes):
             raise _lib.HipEngineError("planes-format spectra: this expectation type / plane set needs complex64 spectra "
                                       "(call spectra() without planes_hint)")
+        # (Im s)^2 / s/|s| outside the float32 range: a float64 record from a complex128 copy (_stage_abc.amplitude_guard)
+        sp = _stage_abc.amplitude_guard(self.memory, sp, planes)
         return _stage_abc.accumulate(self.memory, sp, expectation_type, planes, n_freq)
 
     def accumulate(self, sp, expectation_type, planes, n_freq=None):

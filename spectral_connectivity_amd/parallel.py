@@ -157,8 +157,9 @@ def _agreed_direct_exchange(accum, world, per, fpb, group):
     by one all-reduce of a failure flag -- if the direct form raised on ANY rank (a backend without all-to-all, RCCL missing for
     SC_EXCHANGE=library on one of them) every rank takes the library reduce-scatter from then on, so that no two ranks ever issue
     different collectives.  Once agreed, a failure of the direct exchange is an error (raised), not a silent switch."""
-    # (the C ABI's exchange carries float32 records on the GPU; double records of the float64 engine, or records on the host,
-    #  take the torch form -- the same on every rank, so not a failure)
+    # (the C ABI's exchange carries float32 records on the GPU; double records -- the float64 engine's, or a float32 request the
+    #  amplitude guard sent to float64, which group_guarded_spectra decides once for the group -- and records on the host take the
+    #  torch form: the same on every rank, so not a failure)
     library = exchange_algorithm() == "library" and accum.is_cuda and accum.dtype == torch.float32
     fn = _library_blocks if library else _direct_blocks
     key = (id(group) if group is not None else 0, library)
@@ -285,6 +286,23 @@ def _side_stream(device):
     return _side_streams[key]
 
 
+def group_guarded_spectra(spectra, planes, group=None):
+    """The amplitude guard of the float32 engine (engine.guarded_spectra), decided ONCE for the group: a float32 request with
+    (Im s)^2 or s / |s| is accumulated in float64 on EVERY rank when the coefficients of ANY rank's trials leave the float32 range
+    (one MAX all-reduce of a flag), so that all ranks exchange records of one type -- float32 and float64 records take different
+    collectives.  Requests without these families and complex128 spectra pass through without a collective: whether a request
+    has them is the same on every rank."""
+    from . import _stage_abc, engine
+    if spectra.f64 or not planes & _stage_abc.SQUARING_PLANES:
+        return spectra
+    flag = torch.tensor([1 if engine.out_of_range(spectra, planes) else 0], dtype=torch.int32)
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        if dist.get_backend(group) != "gloo":
+            flag = flag.to(spectra.device)
+        dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=group)
+    return engine.guarded_spectra(spectra, planes, decided=bool(int(flag.item())))
+
+
 def sharded_measures(spectra, planes, which, n_groups=4, dst=0, group=None, mark=None, equal_shards=False,
                      timing=None):
     """Stage B + exchange + epilogue for trial-sharded spectra, pipelined over frequency groups.
@@ -306,6 +324,7 @@ def sharded_measures(spectra, planes, which, n_groups=4, dst=0, group=None, mark
     world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
     rank = dist.get_rank(group) if world > 1 else 0
     xchg = not _no_exchange(group)             # world > 1, or a one-rank rehearsal of the exchange
+    spectra = group_guarded_spectra(spectra, planes, group)
     F, W, C = spectra.F, spectra.W, spectra.C
     n_groups = max(1, min(int(n_groups), F))
     main = torch.cuda.current_stream()
@@ -324,7 +343,7 @@ def sharded_measures(spectra, planes, which, n_groups=4, dst=0, group=None, mark
 
     for g in range(n_groups):
         f0, f1 = shard_bounds(F, n_groups, g)
-        accum, n_obs = engine.accumulate(spectra.freq_slice(f0, f1), "trials_tapers", planes, mark=mark, row_multiple=world)
+        accum, n_obs = engine.accumulate(spectra.freq_slice(f0, f1), "trials_tapers", planes, mark=mark, row_multiple=world, guard=False)
         n_bins = accum.shape[0]
         if xchg:
             ready = torch.cuda.Event()
@@ -509,6 +528,9 @@ class ShardedConnectivity(_connectivity_base()):
         assert rem == 0, "n_observations of a trial-averaging expectation is a multiple of the trial count"
         return per_trial * self._n_trials_total
 
+    def _guard_spectra(self, sp, planes):
+        return group_guarded_spectra(sp, planes, self._group)
+
     def _reduce_over_ranks(self, accum):
         """Replicated sum of the records (Granger, canonical, MVAR, global coherence read every bin)."""
         return all_reduce_sum_(accum, self._group)
@@ -524,8 +546,8 @@ class ShardedConnectivity(_connectivity_base()):
                 key = have
                 break
         if key is None:
-            sp = self._device(planes_hint=planes)
-            accum, n_obs = engine.accumulate(sp, self.expectation_type, planes, n_freq=self._n_freq)
+            sp = group_guarded_spectra(self._device(planes_hint=planes), planes, self._group)
+            accum, n_obs = engine.accumulate(sp, self.expectation_type, planes, n_freq=self._n_freq, guard=False)
             shard, lo, hi = reduce_scatter_bins(accum, self._group)
             key = planes
             self._sharded_cache[key] = (shard, accum.shape[0], self._n_observations_total(n_obs))

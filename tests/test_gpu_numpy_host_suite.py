@@ -48,6 +48,12 @@ for dtype, tol in ((np.complex64, 2e-5), (np.complex128, 1e-9)):
 m = sc.Multitaper(x[:, :, :6], **kw)
 np.testing.assert_allclose(m.fft(), so.multitaper_fft(x[:, :, :6], fs=100.0, NW=2)[0], rtol=1e-9, atol=1e-12)
 res = sc.multitaper_connectivity(x[:, :, :6], sampling_frequency=100.0, time_halfbandwidth_product=2, method=["coherence_magnitude", "power"])
+xm = x[:, :, :6] * 2.0 ** -43          # MEG in tesla: (Im s)^2 leaves the float32 range and the request is served in float64
+cm, cf = sc.Connectivity.from_multitaper(sc.Multitaper(xm, **kw), dtype=np.complex64), so.multitaper_fft(xm, fs=100.0, NW=2)[0]
+for name, tol in (("debiased_squared_weighted_phase_lag_index", 1e-4), ("phase_locking_value", 3e-5)):
+    got, ref = getattr(cm, name)(), getattr(so, name)(cf)
+    ok = ~np.isnan(ref)
+    assert np.array_equal(np.isnan(got), ~ok) and np.abs(got[ok] - ref[ok]).max() <= tol * max(1.0, np.abs(ref[ok]).max()), (name, np.abs(got[ok] - ref[ok]).max())
 assert "torch" not in sys.modules, "torch was imported"
 print("numpy host OK")
 """

@@ -101,11 +101,27 @@ def test_zero_and_tiny_power_channels_do_not_produce_infinities():
     x[..., 1] = 0.0
     x[..., 2] *= 1e-18
     c = sc.Connectivity.from_multitaper(sc.Multitaper(x, sampling_frequency=128.0, time_halfbandwidth_product=2))
-    for name in ("coherence_magnitude", "imaginary_coherence", "weighted_phase_lag_index", "phase_lag_index"):
+    for name in ("coherence_magnitude", "imaginary_coherence", "weighted_phase_lag_index", "phase_lag_index",
+                 "phase_locking_value", "pairwise_phase_consistency", "debiased_squared_phase_lag_index",
+                 "debiased_squared_weighted_phase_lag_index"):
         v = getattr(c, name)()
-        assert not np.isinf(v).any()
+        assert not np.isinf(v).any(), name
         fin = v[np.isfinite(v)]
-        assert (np.abs(fin) <= 1 + 1e-6).all()
+        assert (np.abs(fin) <= 1 + 1e-6).all(), name
+    # the pair of the two live channels against the float64 oracle: the phase-locking and the debiased measures do not depend on a
+    # channel's scale (bounds: test_gpu_parity's close32; 1e-4 for the debiased wPLI as in its test_seeded_vs_oracle_multi_tile; the
+    # debiased PLI exact up to float32 sign flips, none of which this input has)
+    from oracle import spectral_oracle as so
+    from test_gpu_parity import close32
+    coef, _ = so.multitaper_fft(x, fs=128.0, NW=2)
+    for name, tol in (("phase_locking_value", None), ("pairwise_phase_consistency", None), ("debiased_squared_phase_lag_index", None),
+                      ("debiased_squared_weighted_phase_lag_index", 1e-4)):
+        got, ref = getattr(c, name)()[..., 0, 2], getattr(so, name)(coef)[..., 0, 2]
+        np.testing.assert_array_equal(getattr(c, name)()[..., 2, 0], got, err_msg=name)
+        if tol is None:
+            close32(got, ref, what=name)
+        else:
+            close32(got, ref, rtol=tol, atol_scale=tol, what=name)
 
 
 def test_spectrogram_peak_follows_the_signal():

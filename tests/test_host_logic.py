@@ -675,6 +675,124 @@ def test_stage_b_call_sequences(monkeypatch):
     assert lib.args("sc_nonlinear_accumulate_f32")[0][1:4] == (real, every, every & ~CSM & ~UNIT)
 
 
+def test_amplitude_guard_call_sequences(monkeypatch):
+    """_stage_abc.amplitude_guard against the recording library: which requests are measured at all, the thresholds at the amplitudes
+    of real recordings, the verdict per request from one measurement, the complex128 copy and the float64 record stage B then
+    writes, the planes format's own criterion on its channel scales, and a group's decision handed in."""
+    import ctypes
+
+    from spectral_connectivity_amd import _lib, _stage_abc
+    F, W, R, K, C, Ca = 17, 3, 2, 2, 3, 4
+    n_bins, fpb, n_obs = 5, 8, 4
+    CSM, ABS, SQ, SIGN, UNIT = _lib.PLANE_CSM, _lib.PLANE_ABS_IM, _lib.PLANE_IM_SQ, _lib.PLANE_SIGN_IM, _lib.PLANE_UNIT
+    cross, every = CSM | ABS | SQ, CSM | ABS | SQ | SIGN | UNIT
+    strides = _stage_abc.dense_strides(W, R, K, Ca)
+    scan = ["sc_amplitude_range_work_bytes", "sc_amplitude_range_f32"]
+
+    def layout(d, planes, a, b, c, e):
+        a._obj.value, b._obj.value, c._obj.value, e._obj.value = n_bins, fpb, 1, n_obs
+        return 0
+
+    def amplitude(typical):
+        """sc_amplitude_range_f32 reporting coefficients of root mean square ``typical`` and maximum 4 x that on every channel."""
+        def fill(d_X, n_rows, n_ch, d_out, d_work, work_bytes, stream):
+            out = np.ctypeslib.as_array(ctypes.cast(d_out, ctypes.POINTER(ctypes.c_double)), (2, n_ch))
+            out[0], out[1] = typical ** 2 * n_rows, 4 * typical
+            return 0
+        return fill
+
+    def memory():
+        mem = _numpy_memory()
+        mem.download = lambda a: a
+        mem.read_scales = lambda sp: sp.scale
+        return mem
+
+    def guard(sp, planes, typical=1.0, decided=None, **answers):
+        lib, mem = _RecordingLibrary(sc_accum_layout=layout, sc_amplitude_range_f32=amplitude(typical), **answers), memory()
+        monkeypatch.setattr(_lib, "_lib", lib)
+        return lib, mem, _stage_abc.amplitude_guard(mem, sp, planes, decided)
+
+    def fresh():
+        return memory().spectra(np.zeros((F, W, R, K, Ca), np.complex64), (F, W, R, K, C), strides, 32, True, C_alloc=Ca)
+
+    # families that square no product, and complex128 spectra: nothing is measured
+    sp = fresh()
+    lib, _, got = guard(sp, CSM | ABS | SIGN)
+    assert got is sp and not lib.names()
+    X64 = memory().spectra(np.zeros((F, W, R, K, C), np.complex128), (F, W, R, K, C), _stage_abc.dense_strides(W, R, K, C), 32, True)
+    lib, _, got = guard(X64, every)
+    assert got is X64 and not lib.names()
+    # measured once, over every row, with the workspace the query names
+    lib, _, got = guard(sp, every, sc_amplitude_range_work_bytes=96)
+    assert got is sp and lib.names() == scan and lib.args(scan[0]) == [(F * W * R * K, Ca)]
+    assert lib.args(scan[1])[0][1:3] == (F * W * R * K, Ca) and lib.args(scan[1])[0][5] == 96
+    assert not guard(sp, every)[0].names()                                  # (kept on the spectra object)
+    # 2^-47 (MEG in tesla) is inside the float32 range for s / |s| and outside it for (Im s)^2; 2^-54 and 2^40 are outside for both
+    # or one of them; volts (2^-24) and 24-bit counts (2^19) are inside for everything
+    for typical, planes, wide in ((2.0 ** -47, UNIT, False), (2.0 ** -47, cross, True), (2.0 ** -54, UNIT, True), (2.0 ** 40, UNIT, False),
+                                  (2.0 ** 40, cross, True), (2.0 ** -24, every, False), (2.0 ** 19, every, False)):
+        sp = fresh()
+        lib, mem, got = guard(sp, planes, typical)
+        assert (got is not sp) == wide and got.f64 == wide, (typical, planes)
+        assert lib.names() == scan + (["sc_spectra_widen_f32"] if wide else []), (typical, planes)
+        if wide:
+            assert lib.args("sc_spectra_widen_f32")[0][1] == F * W * R * K * Ca and got.X.dtype == np.complex128
+            assert (got.F, got.W, got.R, got.K, got.C, got.C_alloc, got.strides) == (F, W, R, K, C, Ca, strides)
+            rec, _ = _stage_abc.accumulate(mem, got, "trials_tapers", planes)         # the float64 engine's call, a float64 record
+            assert lib.names()[-2:] == ["sc_accum_layout", "sc_accumulate_f64"] and rec.dtype == np.float64
+    # the verdict is per request, the measurement and the copy per object: (Im s)^2 at 2^-47 is widened, s / |s| afterwards is not
+    sp = fresh()
+    _, _, wide1 = guard(sp, cross, 2.0 ** -47)
+    lib, _, got = guard(sp, UNIT, 2.0 ** -47)
+    assert wide1 is not sp and got is sp and not lib.names()
+    lib, _, got = guard(sp, cross, 2.0 ** -47)
+    assert got is wide1 and not lib.names()
+    # a group's decision: no measurement here, the copy on True
+    sp = fresh()
+    lib, _, got = guard(sp, cross, decided=False)
+    assert got is sp and not lib.names()
+    lib, _, got = guard(sp, cross, decided=True)
+    assert got.f64 and lib.names() == ["sc_spectra_widen_f32"]
+    # planes-format spectra: the criterion is on the channel scales themselves (1 / scale 2^-30: volts; 2^-53: tesla), without a pass
+    # over the data; a family the format does not serve (s / |s|) is measured on the decoded coefficients
+    def planes_spectra(inverse):
+        scale = np.concatenate([np.full(Ca, 1.0 / inverse, np.float32), np.full(Ca, inverse, np.float32)])
+        return memory().spectra(None, (F, W, R, K, C), strides, 32, True, C_alloc=Ca, P=np.zeros(64, np.uint8), scale=scale)
+    sp = planes_spectra(2.0 ** -30)
+    lib, _, got = guard(sp, cross)
+    assert got is sp and not lib.names()
+    sp = planes_spectra(2.0 ** 13)                                           # (24-bit counts)
+    assert guard(sp, cross)[2] is sp
+    sp = planes_spectra(2.0 ** -53)
+    lib, _, got = guard(sp, cross)
+    assert got.f64 and lib.names() == ["sc_spectra_from_planes_f32", "sc_spectra_widen_f32"]
+
+
+def test_tiled_record_refuses_a_block_of_another_type(monkeypatch):
+    """engine._accumulate_blocked (more than 256 signals) places float32 tiles into a float32 record and float64 into float64: a block
+    pair that came back as the other type is an error, never a silent cast (the sum of (Im s)^2 of tesla-scaled data would be 0)."""
+    import torch
+
+    from spectral_connectivity_amd import _lib, engine
+
+    class Wide:
+        C, f64, device = 300, False, torch.device("cpu")
+
+    monkeypatch.setattr(engine, "accum_layout", lambda sp, et, planes, n_freq: (2, 4 * 190 * 256, 1, 6))      # 19 blocks of 16: 190 tiles
+    monkeypatch.setattr(engine, "_channel_subset", lambda sp, cols: type("Sub", (), {"C": int(len(cols))})())
+    seen = []
+
+    def accumulate(sub, et, planes, n_freq=None, mark=None, guard=True):
+        seen.append(guard)
+        nb = -(-sub.C // 16)
+        return torch.zeros((2, 4 * (nb * (nb + 1) // 2) * 256), dtype=torch.float64), 6
+
+    monkeypatch.setattr(engine, "accumulate", accumulate)
+    with pytest.raises(_lib.HipEngineError, match="float64"):
+        engine._accumulate_blocked(Wide(), "trials_tapers", _lib.PLANE_CSM | _lib.PLANE_ABS_IM | _lib.PLANE_IM_SQ, None, None, 1)
+    assert seen == [False]                                                   # (the decision was the whole array's, taken before the tiling)
+
+
 def test_stage_c_call_sequences(monkeypatch):
     """_stage_abc.measure / measure_multi against the recording library: shape and dtype of every kind of output, narrow and wide,
     the forms that sum partial records while they read, and the one-launch epilogue falling back to single calls."""
