@@ -586,6 +586,28 @@ int sc_imaginary_interaction_f64(const void* d_accum, int64_t n_bins, int64_t n_
                                  int n_groups, int max_group_size, double* d_mic, double* d_mim,
                                  int32_t* d_fail, void* stream);
 
+/* ---- the vectors that attain MIC (fp64; sc_canonical.hip; additive, ABI v8) ----
+ * Per (bin, group pair a < b), with R_g = L_g L_g^T, M = L_a^-1 I L_b^-T, p the unit eigenvector of M M^T for MIC^2 and
+ * q = M^T p / MIC:   filters  alpha = L_a^-T p, beta = L_b^-T q   (alpha^T R_a alpha = beta^T R_b beta = 1, alpha^T I beta = MIC)
+ *                    patterns a = L_a p = R_a alpha, b = L_b q = R_b beta   (I beta = MIC a, I^T alpha = MIC b).
+ * One joint sign per pair: the entry of pattern a with the largest magnitude (lowest index on a tie) is positive.
+ * Arguments, member table, checks and error codes of sc_imaginary_interaction_f64.
+ *   d_mic                  double [n_bins][n_groups][n_groups], symmetric, NaN diagonal
+ *   d_filters, d_patterns  double [n_bins][n_groups][n_groups][max_group_size]: entry [a][b][0 .. n_a) is group a's vector in
+ *                          its interaction with group b (both orders of a pair are filled), NaN beyond n_a, on the diagonal,
+ *                          for a pair whose MIC is NaN and for a pair whose M is exactly 0 (MIC 0: no direction is singled out)
+ *   d_fail                 int32 [1]: as sc_imaginary_interaction_f64
+ * One 256-thread workgroup per (bin, pair), persistent; parallel Jacobi on M M^T with a rotation log.  A pair whose groups
+ * have at most sc_interaction_vectors_lds_group(max_group_size) channels keeps its three blocks in LDS, the others in a
+ * stream-ordered scratch of 768 KB per workgroup; the rotation log takes 14 (n - 1) (n / 2) 24 bytes per workgroup
+ * (n = max_group_size rounded up to even: 2.7 MB at 128 channels; 256 ... 1024 workgroups), from the same allocation
+ * (hipMallocAsync / hipFreeAsync on `stream`, SC_ENOMEM if that fails). */
+int sc_interaction_vectors_lds_group(int max_group_size);
+int sc_imaginary_interaction_vectors_f64(const void* d_accum, int64_t n_bins, int64_t n_signals, uint32_t planes,
+                                         int64_t n_observations, const int32_t* d_members, const int32_t* d_sizes,
+                                         int n_groups, int max_group_size, double* d_mic, double* d_filters,
+                                         double* d_patterns, int32_t* d_fail, void* stream);
+
 /* ---- partial and multiple coherence (fp64, from the accumulated CSM; sc_partial.hip; additive, ABI v8) ----
  * The coherence of two signals after the linear influence of all the other signals is removed, and the share of a signal's
  * power that all the others explain linearly (the reference has neither).  Per bin record, with S the normalised Hermitian

@@ -168,6 +168,9 @@ SYMBOLS = {
                                            c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sc_imaginary_interaction_f64": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_void_p, c_void_p,
                                              c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sc_interaction_vectors_lds_group": (c_int, [c_int]),
+    "sc_imaginary_interaction_vectors_f64": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_void_p, c_void_p,
+                                                     c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sc_partial_coherence_max_signals": (c_int, []),
     "sc_partial_coherence_f64": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p]),

@@ -233,6 +233,21 @@ def imaginary_interaction(mem, accum, n_signals, planes, n_obs, members, sizes):
     return mic, mim, mem.read_int(fail)
 
 
+def imaginary_interaction_vectors(mem, accum, n_signals, planes, n_obs, members, sizes):
+    """The vectors that attain MIC (sc_imaginary_interaction_vectors_f64).  members / sizes: _lib.member_table of the groups.
+    Returns (MIC [n_bins, G, G], filters, patterns [n_bins, G, G, max group size] float64, n_fail)."""
+    G, n_bins, n_max = len(sizes), accum.shape[0], int(sizes.max())
+    d_members, d_sizes = mem.upload(members), mem.upload(sizes)
+    mic = mem.empty((n_bins, G, G), np.float64)
+    filters, patterns = mem.empty((n_bins, G, G, n_max), np.float64), mem.empty((n_bins, G, G, n_max), np.float64)
+    fail = mem.zeros((1,), np.int32)
+    _lib.check(_lib._handle().sc_imaginary_interaction_vectors_f64(mem.ptr(accum), n_bins, n_signals, _planes(mem, accum, planes),
+                                                                   n_obs, mem.ptr(d_members), mem.ptr(d_sizes), G, n_max,
+                                                                   mem.ptr(mic), mem.ptr(filters), mem.ptr(patterns), mem.ptr(fail),
+                                                                   mem.stream()), "sc_imaginary_interaction_vectors_f64")
+    return mic, filters, patterns, mem.read_int(fail)
+
+
 def partial_coherence(mem, accum, n_signals, planes, n_obs, want):
     """Partial and multiple coherence of every bin record (sc_partial.hip).  ``want``: names out of "coherency", "magnitude",
     "multiple" -- one call serves them all.  Returns ({name: device array}, n_fail): coherency complex128 and magnitude float64

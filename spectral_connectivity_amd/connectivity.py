@@ -16,6 +16,7 @@ the hot-path measures.  All arithmetic runs on an MI355X through ``libsc_hip.so`
 There is no NumPy fallback: without the HIP extension / a GPU every measure raises.
 """
 import warnings
+from collections import namedtuple
 from logging import getLogger
 
 import numpy as np
@@ -31,6 +32,9 @@ logger = getLogger(__name__)
 
 # kept for API parity with reference connectivity.py:67-75 (keys are what matters)
 EXPECTATION = dict.fromkeys(EXPECTATION_AXES)
+
+# what maximized_imaginary_coherence_vectors returns
+InteractionVectors = namedtuple("InteractionVectors", ("mic", "filters", "patterns", "labels", "members"))
 
 
 class _PendingSpectra:
@@ -701,6 +705,56 @@ class Connectivity:
         self._interaction_failed(n_fail)
         shape = self._kept_shape() + (self._n_freq, G, G)
         return engine.to_host(mic).reshape(shape), engine.to_host(mim).reshape(shape), labels
+
+    def maximized_imaginary_coherence_vectors(self, group_labels):
+        """The channel weights that attain ``maximized_imaginary_coherence`` and the topographies to plot for them (MNE-Connectivity's
+        ``patterns`` of ``mic``).  Per frequency and pair of groups a, b with R_g = Re S_gg and I = Im S_ab:
+
+        ``filters``: the weights alpha (group a), beta (group b) with alpha^T R_a alpha = beta^T R_b beta = 1 that maximise
+        alpha^T I beta = MIC -- Ewald's R^-1/2 u; project the data of a group onto its filter to get the interacting component.
+        ``patterns``: a = R_a alpha, b = R_b beta -- how strongly every channel sees that component (Haufe et al. 2014): these are
+        the maps to plot, not the filters.  I beta = MIC a and I^T alpha = MIC b.
+        One joint sign per pair is free: the entry of largest magnitude (lowest index on a tie) of the pattern of the group with
+        the lower label is positive.
+
+        Returns the named tuple (mic, filters, patterns, labels, members): ``mic`` [kept axes..., n_frequencies, G, G] as
+        maximized_imaginary_coherence; ``filters`` and ``patterns`` float64 [kept axes..., n_frequencies, G, G, n_max] with
+        entry [..., a, b, :n_a] the vector of group a in its interaction with group b (both orders of a pair are filled), NaN
+        beyond n_a and on the diagonal; ``labels`` = np.unique(group_labels); ``members[g]`` the channel indices of group g in the
+        order of the last axis.  Expectation, group sizes, rank rule and warnings of maximized_imaginary_coherence: a pair whose
+        MIC is NaN has NaN vectors.  A pair whose cross-spectrum is exactly real has MIC 0 and NaN vectors (no direction is
+        singled out; no warning).  Elsewhere the vectors are computed however small MIC is -- they mean nothing where MIC is not
+        distinguishable from 0, and where the two largest singular values nearly coincide they are one of many equally good
+        pairs (sc_canonical.hip).
+        """
+        from . import engine
+        import torch
+        labels, members, sizes, _ = self._interaction_groups(group_labels)      # (the labels are checked before any device work)
+        accum, n_obs, _ = self._csm_records("interaction", two_sided=False)
+        n_total = self._n_observations_total(n_obs)
+        keep = self._interaction_kept(sizes, n_total)
+        G, n_max = len(labels), int(sizes.max())
+        lo, hi, per = self._canonical_bins(accum.shape[0])
+        mic = torch.full((max(hi - lo, 0), G, G), float("nan"), dtype=torch.float64, device=accum.device)
+        filters = torch.full((max(hi - lo, 0), G, G, n_max), float("nan"), dtype=torch.float64, device=accum.device)
+        patterns = filters.clone()
+        n_fail = 0
+        if hi > lo and len(keep) >= 2:
+            sub_members, sub_sizes, _ = _lib.member_table([members[k, :sizes[k]] for k in keep])
+            a, f, p, n_fail = engine.imaginary_interaction_vectors(accum[lo:hi], self._shape5[4], _lib.PLANE_CSM, n_total,
+                                                                   sub_members, sub_sizes)
+            idx = torch.as_tensor(keep, device=accum.device)
+            mic[:, idx[:, None], idx[None, :]] = a
+            filters[:, idx[:, None], idx[None, :], :f.shape[-1]] = f
+            patterns[:, idx[:, None], idx[None, :], :p.shape[-1]] = p
+        mic = self._canonical_gather(mic, accum.shape[0], per)
+        filters = self._canonical_gather(filters, accum.shape[0], per)
+        patterns = self._canonical_gather(patterns, accum.shape[0], per)
+        self._interaction_failed(n_fail)
+        shape = self._kept_shape() + (self._n_freq, G, G)
+        return InteractionVectors(engine.to_host(mic).reshape(shape), engine.to_host(filters).reshape(shape + (n_max,)),
+                                  engine.to_host(patterns).reshape(shape + (n_max,)), labels,
+                                  [members[g, :sizes[g]].astype(np.int64) for g in range(G)])
 
     # ---- partial and multiple coherence (Bendat & Piersol 1986, ch. 7; Dahlhaus 2000) ----------------------------
     def partial_coherency(self, given=None, signals=None):

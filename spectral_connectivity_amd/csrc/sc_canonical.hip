@@ -748,6 +748,54 @@ __global__ void __launch_bounds__(256) canonical_big_kernel(CanonArgs a, cd* scr
     }
 }
 
+// ---- pieces the workgroup-per-pair kernels share (canonical_big_hh_kernel, interaction_vectors_kernel) ---------------------------
+// item of the (bin, group pair) list that persistent workgroups walk -> its bin and its pair ga < gb (pairs in the row order of the
+// upper triangle).  (The kernels above and canonical_big_hh_kernel keep these lines inline: calling this there costs the <false>
+// instantiation an SGPR)
+__device__ __forceinline__ void canon_item(const CanonArgs& a, int64_t item, int64_t& bin, int& ga, int& gb) {
+    bin = item / a.n_gpairs;
+    int gp = (int)(item - bin * a.n_gpairs);
+    int len = a.G - 1;
+    ga = 0;
+    while (gp >= len) { gp -= len; ++ga; --len; }
+    gb = ga + 1 + gp;
+}
+// The two whitening loops of a 256-thread workgroup on the na x nb block PM (row length ld, LDS or global), L Cholesky factors.
+// M <- L_a^-1 M, right-looking: row k is final once it is divided by L_a[k][k]; every row below loses its multiple of it
+__device__ __forceinline__ void canon_whiten_rows(cd* PA, cd* PM, int ld, int na, int nb, int tid) {
+    for (int k = 0; k < na; ++k) {
+        const double dk = PA[k * ld + k].x;
+        if (tid < nb) { const cd v = PM[k * ld + tid]; PM[k * ld + tid] = make_double2(v.x / dk, v.y / dk); }
+        __syncthreads();
+        const int rows = na - k - 1;
+        for (int e = tid; e < rows * nb; e += 256) {
+            const int i = k + 1 + e / nb, j = e % nb;
+            const cd t = zmul(PA[i * ld + k], PM[k * ld + j]);
+            cd v = PM[i * ld + j];
+            v.x -= t.x; v.y -= t.y;
+            PM[i * ld + j] = v;
+        }
+        __syncthreads();
+    }
+}
+// M <- M L_b^-H: column k is final once it is divided by L_b[k][k]; every column to its right loses conj(L_b[j][k]) times it
+__device__ __forceinline__ void canon_whiten_cols(cd* PB, cd* PM, int ld, int na, int nb, int tid) {
+    for (int k = 0; k < nb; ++k) {
+        const double dk = PB[k * ld + k].x;
+        if (tid < na) { const cd v = PM[tid * ld + k]; PM[tid * ld + k] = make_double2(v.x / dk, v.y / dk); }
+        __syncthreads();
+        const int cols = nb - k - 1;
+        for (int e = tid; e < na * cols; e += 256) {
+            const int i = e / cols, j = k + 1 + e % cols;
+            const cd t = zmul_conj(PM[i * ld + k], PB[j * ld + k]);
+            cd v = PM[i * ld + j];
+            v.x -= t.x; v.y -= t.y;
+            PM[i * ld + j] = v;
+        }
+        __syncthreads();
+    }
+}
+
 // ---- the same problem with the largest eigenvalue alone (round 6) -------------------------------------------------------------
 // canonical_big_kernel spends most of a problem in the parallel Jacobi (14 sweeps x (n - 1) rounds over the packed triangle:
 // 2 ms of 3.6 at 64 channels, 21 ms a problem at 128) for ONE number, the largest eigenvalue of B = M M^H.  Here B is reduced
@@ -797,39 +845,11 @@ __global__ void __launch_bounds__(256) canonical_big_hh_kernel(CanonArgs a, cd* 
         for (int e = tid; e < na * nb; e += 256) { const int i = e / nb, j = e % nb; PM[i * ld + j] = csm_cross<IM>(rec, a, ma[i], mb[j]); }
         __syncthreads();
         sc_wg_cholesky(PA, ld, na, &bad);
-        // M <- L_a^-1 M, right-looking: row k is final once it is divided by L_a[k][k]; every row below loses its multiple of it
-        for (int k = 0; k < na; ++k) {
-            const double dk = PA[k * ld + k].x;
-            if (tid < nb) { const cd v = PM[k * ld + tid]; PM[k * ld + tid] = make_double2(v.x / dk, v.y / dk); }
-            __syncthreads();
-            const int rows = na - k - 1;
-            for (int e = tid; e < rows * nb; e += 256) {
-                const int i = k + 1 + e / nb, j = e % nb;
-                const cd t = zmul(PA[i * ld + k], PM[k * ld + j]);
-                cd v = PM[i * ld + j];
-                v.x -= t.x; v.y -= t.y;
-                PM[i * ld + j] = v;
-            }
-            __syncthreads();
-        }
+        canon_whiten_rows(PA, PM, ld, na, nb, tid);
         for (int e = tid; e < nb * nb; e += 256) { const int i = e / nb, j = e % nb; if (j <= i) PB[i * ld + j] = csm_group<IM>(rec, a, mb[i], mb[j]); }
         __syncthreads();
         sc_wg_cholesky(PB, ld, nb, &bad);
-        // M <- M L_b^-H: column k is final once it is divided by L_b[k][k]; every column to its right loses conj(L_b[j][k]) times it
-        for (int k = 0; k < nb; ++k) {
-            const double dk = PB[k * ld + k].x;
-            if (tid < na) { const cd v = PM[tid * ld + k]; PM[tid * ld + k] = make_double2(v.x / dk, v.y / dk); }
-            __syncthreads();
-            const int cols = nb - k - 1;
-            for (int e = tid; e < na * cols; e += 256) {
-                const int i = e / cols, j = k + 1 + e % cols;
-                const cd t = zmul_conj(PM[i * ld + k], PB[j * ld + k]);
-                cd v = PM[i * ld + j];
-                v.x -= t.x; v.y -= t.y;
-                PM[i * ld + j] = v;
-            }
-            __syncthreads();
-        }
+        canon_whiten_cols(PB, PM, ld, na, nb, tid);
         // B = M M^H, full storage, column-major with leading dimension na (small pairs: where the factor blocks were)
         cd* B = (small || na <= CBH_LDS_N) ? Bl : Lag;
         for (int e = tid; e < na * na; e += 256) {
@@ -954,7 +974,226 @@ __global__ void __launch_bounds__(256) canonical_big_hh_kernel(CanonArgs a, cd* 
     }
 }
 
+// ---- the vectors that attain MIC -----------------------------------------------------------------------------
+// With R_g = Re S_gg = L_g L_g^T, I = Im S_ab and M = L_a^-1 I L_b^-T (the interaction view holds it as (0, M): every product
+// below reads the imaginary parts), p the unit eigenvector of B = M M^T for lambda_max = MIC^2 and q = M^T p / MIC:
+//     filters   alpha = L_a^-T p,  beta = L_b^-T q        patterns   a = L_a p,  b = L_b q.
+// The kernels above drop what the vectors are made of (no reflector is stored, B takes the place of the factor blocks), so this
+// one keeps L_a, L_b and M of a pair until the back-substitutions -- in LDS while the pair fits beside B (both groups of at most
+// `lds_n` channels: iv_lds_n), else in the workgroup's global scratch -- and diagonalises B (packed triangle in LDS) with the
+// parallel Jacobi of sc_jacobi.h, whose rotation log gives p = J_1 ... J_m e_k as global_coherence_big_kernel recovers its
+// vectors.  B is real in this view, so every rotation is real (Im s = 0 exactly) and the back-application is real arithmetic.
+// B sits on the smaller group's side; when that is the group with the higher label the cross block read is Im S_ba = -I^T and
+// the second vector changes sign with it.  One joint sign: the largest entry (lowest index on a tie) of the pattern of the
+// group with the lower label is positive.
+#define IV_SWEEPS CBIG_SWEEPS
+#define IV_STATIC_LDS 6144                     // reserve for the kernel's static LDS (red and a few scalars: 4144 bytes)
+#define IV_LDS_LIMIT (160 * 1024)
+
+struct IvArgs {
+    double* filters;       // [n_bins][G][G][vstride]
+    double* patterns;
+    double* log;           // [slots][IV_SWEEPS (Mb - 1)][Hb][3] rotation log, Mb = max group size rounded up to even, Hb = Mb / 2
+    cd* scratch;           // [slots][3][CBIG_C][CBIG_C] or NULL when every pair fits LDS
+    int vstride;           // = max group size
+    int bn;                // largest order of B the LDS layout holds (= max group size)
+    int lds_n, lds_ld;     // pairs of groups of at most lds_n channels stay in LDS; their row length
+};
+
+// dynamic LDS of a launch: the packed triangle of B and the Jacobi's tables for groups of up to bn channels, four vectors, and
+// three blocks of lds_n x (lds_n | 1)
+static size_t iv_lds_bytes(int bn, int lds_n) {
+    const size_t hm = (size_t)(bn + 1) / 2;
+    return ((size_t)bn * (bn + 1) / 2 + hm + (size_t)3 * lds_n * (lds_n | 1)) * sizeof(cd) + (4 * CBIG_C + hm) * sizeof(double) +
+           2 * hm * sizeof(int) + hm * (hm + 1) * sizeof(unsigned short) + 16;
+}
+// the largest group size up to which a pair keeps its blocks in LDS, in a launch whose largest group has max_group channels
+static int iv_lds_n(int max_group) {
+    int n = max_group;
+    while (n > 0 && iv_lds_bytes(max_group, n) + IV_STATIC_LDS > IV_LDS_LIMIT) --n;
+    return n;
+}
+extern "C" int sc_interaction_vectors_lds_group(int max_group_size) {
+    return max_group_size < 1 || max_group_size > CBIG_C ? 0 : iv_lds_n(max_group_size);
+}
+
+// x <- L^-T x for the two groups at once (threads 0 .. 127: group a, 128 .. 255: group b), column-oriented back-substitution
+__device__ inline void iv_back_substitute(const cd* La, const cd* Lb, int lda, int ldb, int na, int nb, double* xa, double* xb, int tid) {
+    const int nmax = na > nb ? na : nb;
+    for (int i = nmax - 1; i >= 0; --i) {
+        if (tid == 0 && i < na) xa[i] /= La[i * lda + i].x;
+        if (tid == 128 && i < nb) xb[i] /= Lb[i * ldb + i].x;
+        __syncthreads();
+        if (tid < 128) { if (i < na && tid < i) xa[tid] -= La[i * lda + tid].x * xa[i]; }
+        else { const int k = tid - 128; if (i < nb && k < i) xb[k] -= Lb[i * ldb + k].x * xb[i]; }
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(256) interaction_vectors_kernel(CanonArgs a, IvArgs v, int64_t n_items) {
+    extern __shared__ __align__(16) unsigned char cb_smem[];
+    const int hm = (v.bn + 1) / 2;
+    cd* B = reinterpret_cast<cd*>(cb_smem);                                    // packed upper triangle, bn (bn + 1) / 2
+    cd* rs = B + (size_t)v.bn * (v.bn + 1) / 2;                                // [hm]
+    cd* blocks = rs + hm;                                                      // [3][lds_n][lds_ld]
+    double* pv = reinterpret_cast<double*>(blocks + (size_t)3 * v.lds_n * v.lds_ld);   // [CBIG_C] p, then the pattern of a
+    double* qv = pv + CBIG_C;                                                  // q, then the pattern of b
+    double* xa = qv + CBIG_C;                                                  // the filter of a
+    double* xb = xa + CBIG_C;                                                  // the filter of b
+    double* rc = xb + CBIG_C;                                                  // [hm]
+    int* rp = reinterpret_cast<int*>(rc + hm);                                 // [2 hm]
+    unsigned short* blk_u = reinterpret_cast<unsigned short*>(rp + 2 * hm);    // [hm (hm + 1) / 2]
+    unsigned short* blk_v = blk_u + hm * (hm + 1) / 2;
+    __shared__ double red[2][256];
+    __shared__ double sh_lmax, sh_tr, sh_sign;
+    __shared__ int done, n_rounds, bad, tab_for, sh_src;
+    const int tid = threadIdx.x;
+    cd* Lag = v.scratch ? v.scratch + (size_t)blockIdx.x * 3 * CBIG_C * CBIG_C : nullptr;
+    const int Mb = v.bn + (v.bn & 1);
+    double* mylog = v.log + (size_t)blockIdx.x * IV_SWEEPS * (Mb - 1) * (Mb / 2) * 3;
+    if (tid == 0) tab_for = -1;
+    __syncthreads();
+    for (int64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+        int64_t bin;
+        int g_lo, g_hi;
+        canon_item(a, item, bin, g_lo, g_hi);
+        // B on the smaller group's side: ga is that group.  flip: the cross block read below is then Im S_ba = -(Im S_ab)^T
+        const bool flip = a.sizes[g_hi] < a.sizes[g_lo];
+        const int ga = flip ? g_hi : g_lo, gb = flip ? g_lo : g_hi;
+        const int na = a.sizes[ga], nb = a.sizes[gb];
+        const int32_t* ma = a.members + ga * a.mstride;
+        const int32_t* mb = a.members + gb * a.mstride;
+        const ScRec rec = a.accum + bin * a.v.floats_per_bin;
+        const bool in_lds = nb <= v.lds_n;                   // (na <= nb)
+        const int ld = in_lds ? v.lds_ld : CBIG_C;
+        cd* PA = in_lds ? blocks : Lag;
+        cd* PB = PA + (in_lds ? v.lds_n * v.lds_ld : CBIG_C * CBIG_C);
+        cd* PM = PB + (in_lds ? v.lds_n * v.lds_ld : CBIG_C * CBIG_C);
+        if (tid == 0) bad = 0;
+        for (int e = tid; e < na * na; e += 256) { const int i = e / na, j = e % na; if (j <= i) PA[i * ld + j] = csm_group<true>(rec, a, ma[i], ma[j]); }
+        for (int e = tid; e < nb * nb; e += 256) { const int i = e / nb, j = e % nb; if (j <= i) PB[i * ld + j] = csm_group<true>(rec, a, mb[i], mb[j]); }
+        for (int e = tid; e < na * nb; e += 256) { const int i = e / nb, j = e % nb; PM[i * ld + j] = csm_cross<true>(rec, a, ma[i], mb[j]); }
+        __syncthreads();
+        sc_wg_cholesky(PA, ld, na, &bad);
+        sc_wg_cholesky(PB, ld, nb, &bad);
+        canon_whiten_rows(PA, PM, ld, na, nb, tid);
+        canon_whiten_cols(PB, PM, ld, na, nb, tid);
+        // B = M M^H (real: M is (0, m)), packed upper triangle in LDS
+        for (int e = tid; e < na * na; e += 256) {
+            const int i = e / na, j = e % na;
+            if (i > j) continue;
+            double sacc = 0.0;
+            for (int k = 0; k < nb; ++k) sacc += PM[i * ld + k].y * PM[j * ld + k].y;
+            B[gc_tri(i, j, na)] = make_double2(sacc, 0.0);
+        }
+        const int H = (na + (na & 1)) / 2;
+        if (tab_for != H) {                        // pairing table of this group size (rebuilt only when the size changes)
+            __syncthreads();
+            gc_block_table(blk_u, blk_v, H, tid);
+            if (tid == 0) tab_for = H;
+        }
+        __syncthreads();
+        if (tid == 0) {                            // trace(B) = MIM before the rotations: the clamp of canon_store_interaction
+            double tr = 0.0;
+            for (int i = 0; i < na; ++i) tr += B[gc_tri(i, i, na)].x;
+            sh_tr = tr;
+        }
+        gc_jacobi(B, na, rc, rs, rp, blk_u, blk_v, red, &done, &n_rounds, mylog, IV_SWEEPS);
+        __syncthreads();
+        if (tid == 0) {
+            int src = 0;
+            double lmax = B[0].x;
+            for (int i = 1; i < na; ++i) { const double d = B[gc_tri(i, i, na)].x; if (d > lmax) { lmax = d; src = i; } }
+            sh_src = src; sh_lmax = lmax;
+        }
+        __syncthreads();
+        // p = J_1 ... J_m e_src, right to left; thread t rotates the entries of pair t of the round
+        for (int i = tid; i < na; i += 256) pv[i] = i == sh_src ? 1.0 : 0.0;
+        __syncthreads();
+        {
+            const int Mp = na + (na & 1);
+            const int total_rounds = n_rounds;
+            for (int rr = total_rounds - 1; rr >= 0; --rr) {
+                const int r = rr % (Mp - 1);
+                if (tid < H) {
+                    int x, y;
+                    if (tid == 0) { x = Mp - 1; y = r; }
+                    else { x = (r + tid) % (Mp - 1); y = (r - tid + (Mp - 1)) % (Mp - 1); }
+                    const int pi = x < y ? x : y, qi = x < y ? y : x;
+                    if (qi < na) {
+                        const double* lg = mylog + ((size_t)rr * H + tid) * 3;
+                        const double c = lg[0], s = lg[1];
+                        const double xp = pv[pi], xq = pv[qi];
+                        pv[pi] = c * xp + s * xq;
+                        pv[qi] = c * xq - s * xp;
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        const double tr = sh_tr;
+        const double mic = sqrt(fmin(fmax(sh_lmax, 0.0), tr));
+        const bool defined = !bad && tr > 0.0 && mic > 0.0;                   // (B = 0 exactly: MIC 0, no vectors)
+        // q = +-M^T p / MIC, the filters' right-hand sides, then the patterns L p, L q in place of p, q
+        for (int j = tid; j < nb; j += 256) {
+            double sacc = 0.0;
+            for (int i = 0; i < na; ++i) sacc += PM[i * ld + j].y * pv[i];
+            const double qj = (flip ? -sacc : sacc) / mic;
+            qv[j] = qj; xb[j] = qj;
+        }
+        for (int i = tid; i < na; i += 256) xa[i] = pv[i];
+        __syncthreads();
+        double pat = 0.0;
+        if (tid < 128) { if (tid < na) for (int k = 0; k <= tid; ++k) pat += PA[tid * ld + k].x * pv[k]; }
+        else { const int j = tid - 128; if (j < nb) for (int k = 0; k <= j; ++k) pat += PB[j * ld + k].x * qv[k]; }
+        __syncthreads();
+        if (tid < 128) { if (tid < na) pv[tid] = pat; }
+        else if (tid - 128 < nb) qv[tid - 128] = pat;
+        iv_back_substitute(PA, PB, ld, ld, na, nb, xa, xb, tid);
+        if (tid == 0) {
+            const double* lowp = flip ? qv : pv;             // the pattern of the group with the lower label
+            const int nl = flip ? nb : na;
+            double best = -1.0, val = 1.0;
+            for (int i = 0; i < nl; ++i) { const double m = fabs(lowp[i]); if (m > best) { best = m; val = lowp[i]; } }
+            sh_sign = val < 0.0 ? -1.0 : 1.0;
+            double* o = a.out + bin * a.G * a.G;
+            const double m = bad ? nan("") : mic;
+            o[ga * a.G + gb] = m;
+            o[gb * a.G + ga] = m;
+            if (bad) atomicAdd(a.fail, 1);
+        }
+        __syncthreads();
+        if (defined) {                                       // (the outputs are NaN-filled before the launch)
+            const double sg = sh_sign;
+            const size_t oa = (((size_t)bin * a.G + ga) * a.G + gb) * v.vstride, ob = (((size_t)bin * a.G + gb) * a.G + ga) * v.vstride;
+            for (int i = tid; i < na; i += 256) { v.filters[oa + i] = sg * xa[i]; v.patterns[oa + i] = sg * pv[i]; }
+            for (int j = tid; j < nb; j += 256) { v.filters[ob + j] = sg * xb[j]; v.patterns[ob + j] = sg * qv[j]; }
+        }
+        __syncthreads();
+    }
+}
+
 extern "C" int sc_canonical_max_group(void) { return CBIG_C; }
+
+// what both launch functions check and fill in
+static int canonical_args(const char* what, const void* d_accum, int64_t n_bins, int64_t n_signals, uint32_t planes,
+                          int64_t n_observations, const int32_t* d_members, const int32_t* d_sizes, int n_groups, int max_group_size,
+                          double* d_out, double* d_out_mim, int32_t* d_fail, CanonArgs* out) {
+    CanonArgs& a = *out;
+    const int rcv = sc_csm_view(planes, n_bins, n_bins, n_signals, n_observations, &a.v);
+    if (rcv != SC_OK) return rcv;
+    SC_REQUIRE(n_groups >= 1 && n_bins >= 1, "empty problem");
+    if (max_group_size > CBIG_C) {
+        sc_set_error("%s supports groups of at most %d channels (got %d)", what, CBIG_C, max_group_size);
+        return SC_EUNSUPPORTED;
+    }
+    a.accum = sc_rec(d_accum, planes); a.members = d_members; a.sizes = d_sizes; a.out = d_out; a.fail = d_fail;
+    a.out_mim = d_out_mim;
+    a.n_bins = n_bins; a.G = n_groups; a.n_gpairs = n_groups * (n_groups - 1) / 2;
+    a.mstride = max_group_size <= 32 ? 32 : CBIG_C;      // (the member table's row length is the caller's: sc_hip.h)
+    a.jtol = 1e-24;          // off^2 <= jtol dia^2: eigenvalues to ~1e-12 relative (quadratic convergence)
+    return SC_OK;
+}
 
 // The launches of both entry points: the tier of the largest group (<= 16 channels: factor + pair kernels; <= 64: a workgroup per
 // pair in LDS; <= 128: the same with the blocks in a global scratch) and its workspace.  IM: the interaction view, MIC into `out`
@@ -965,19 +1204,10 @@ static int canonical_launch(const char* what, const void* d_accum, int64_t n_bin
                             int64_t n_observations, const int32_t* d_members, const int32_t* d_sizes, int n_groups,
                             int max_group_size, double* d_out, double* d_out_mim, int32_t* d_fail, void* stream) {
     CanonArgs a;
-    const int rcv = sc_csm_view(planes, n_bins, n_bins, n_signals, n_observations, &a.v);
-    if (rcv != SC_OK) return rcv;
-    SC_REQUIRE(n_groups >= 1 && n_bins >= 1, "empty problem");
-    if (max_group_size > CBIG_C) {
-        sc_set_error("%s supports groups of at most %d channels (got %d)", what, CBIG_C, max_group_size);
-        return SC_EUNSUPPORTED;
-    }
+    const int rca = canonical_args(what, d_accum, n_bins, n_signals, planes, n_observations, d_members, d_sizes, n_groups,
+                                   max_group_size, d_out, d_out_mim, d_fail, &a);
+    if (rca != SC_OK) return rca;
     hipStream_t st = (hipStream_t)stream;
-    a.accum = sc_rec(d_accum, planes); a.members = d_members; a.sizes = d_sizes; a.out = d_out; a.fail = d_fail;
-    a.out_mim = d_out_mim;
-    a.n_bins = n_bins; a.G = n_groups; a.n_gpairs = n_groups * (n_groups - 1) / 2;
-    a.mstride = max_group_size <= 32 ? 32 : CBIG_C;      // (the member table's row length is the caller's: sc_hip.h)
-    a.jtol = 1e-24;          // off^2 <= jtol dia^2: eigenvalues to ~1e-12 relative (quadratic convergence)
     const int64_t total_out = n_bins * n_groups * n_groups;
     sc_internal_fill_nan(d_out, total_out, st);
     if (IM) sc_internal_fill_nan(d_out_mim, total_out, st);
@@ -1066,6 +1296,54 @@ extern "C" int sc_canonical_coherence_f64(const void* d_accum, int64_t n_bins, i
     SC_REQUIRE(d_accum && d_members && d_sizes && d_out && d_fail, "NULL argument");
     return canonical_launch<false>("canonical coherence", d_accum, n_bins, n_signals, planes, n_observations, d_members, d_sizes,
                                    n_groups, max_group_size, d_out, nullptr, d_fail, stream);
+}
+
+extern "C" int sc_imaginary_interaction_vectors_f64(const void* d_accum, int64_t n_bins, int64_t n_signals, uint32_t planes,
+                                                    int64_t n_observations, const int32_t* d_members, const int32_t* d_sizes,
+                                                    int n_groups, int max_group_size, double* d_mic, double* d_filters,
+                                                    double* d_patterns, int32_t* d_fail, void* stream) {
+    ScTimed timed_("imaginary_interaction_vectors", stream);
+    const char* what = "imaginary interaction vectors";
+    SC_REQUIRE(d_accum && d_members && d_sizes && d_mic && d_filters && d_patterns && d_fail, "NULL argument");
+    SC_REQUIRE(max_group_size >= 1, "empty groups");
+    CanonArgs a;
+    const int rca = canonical_args(what, d_accum, n_bins, n_signals, planes, n_observations, d_members, d_sizes, n_groups,
+                                   max_group_size, d_mic, nullptr, d_fail, &a);
+    if (rca != SC_OK) return rca;
+    if (max_group_size <= CB_C) a.mstride = CB_C;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t total_out = n_bins * n_groups * n_groups;
+    sc_internal_fill_nan(d_mic, total_out, st);
+    sc_internal_fill_nan(d_filters, total_out * max_group_size, st);
+    sc_internal_fill_nan(d_patterns, total_out * max_group_size, st);
+    (void)hipMemsetAsync(d_fail, 0, 4, st);
+    const int64_t items = n_bins * a.n_gpairs;
+    if (items > 0) {
+        IvArgs v;
+        v.filters = d_filters; v.patterns = d_patterns; v.vstride = max_group_size; v.bn = max_group_size;
+        v.lds_n = iv_lds_n(max_group_size); v.lds_ld = v.lds_n | 1;
+        const size_t lds = iv_lds_bytes(v.bn, v.lds_n);
+        int per_cu = (int)(IV_LDS_LIMIT / (lds + IV_STATIC_LDS));      // persistent workgroups a compute unit holds by LDS
+        per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
+        const int64_t want = (int64_t)256 * per_cu;
+        const int slots = (int)(items < want ? items : want);
+        const int Mb = v.bn + (v.bn & 1);
+        const size_t log_bytes = ((size_t)IV_SWEEPS * (Mb - 1) * (Mb / 2) * 3 * sizeof(double) * slots + 255) & ~(size_t)255;
+        const size_t sbytes = v.lds_n < max_group_size ? (size_t)slots * 3 * CBIG_C * CBIG_C * sizeof(cd) : 0;
+        char* work = nullptr;
+        if (hipMallocAsync((void**)&work, log_bytes + sbytes, st) != hipSuccess) {
+            sc_set_error("%s: workspace allocation of %zu bytes failed", what, log_bytes + sbytes);
+            return SC_ENOMEM;
+        }
+        v.log = reinterpret_cast<double*>(work);
+        v.scratch = sbytes ? reinterpret_cast<cd*>(work + log_bytes) : nullptr;
+        const hipError_t rcl = hipFuncSetAttribute((const void*)interaction_vectors_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (rcl == hipSuccess) hipLaunchKernelGGL(interaction_vectors_kernel, dim3((unsigned)slots), dim3(256), lds, st, a, v, items);
+        (void)hipFreeAsync(work, st);
+        SC_CHECK_HIP(rcl);
+    }
+    SC_CHECK_HIP(hipGetLastError());
+    return SC_OK;
 }
 
 extern "C" int sc_imaginary_interaction_f64(const void* d_accum, int64_t n_bins, int64_t n_signals, uint32_t planes,

@@ -521,6 +521,12 @@ def imaginary_interaction(accum, n_signals, planes, n_obs, members, sizes):
     return _stage_d.imaginary_interaction(TorchMemory(accum.device), accum, n_signals, planes, n_obs, members, sizes)
 
 
+def imaginary_interaction_vectors(accum, n_signals, planes, n_obs, members, sizes):
+    """members / sizes: _lib.member_table of the groups.  Returns (MIC [n_bins, G, G], filters, patterns [n_bins, G, G, max group
+    size] float64, n_fail)."""
+    return _stage_d.imaginary_interaction_vectors(TorchMemory(accum.device), accum, n_signals, planes, n_obs, members, sizes)
+
+
 def partial_coherence(accum, n_signals, planes, n_obs, want):
     """Partial and multiple coherence of every bin record (sc_partial.hip): _stage_d.partial_coherence.  Returns ({name: tensor}
     for the names of ``want`` out of "coherency", "magnitude", "multiple", n_fail)."""

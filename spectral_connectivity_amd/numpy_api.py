@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib, _stage_abc, _stage_d
 from .connectivity import Connectivity as _TorchHostConnectivity
-from .connectivity import _PendingSpectra
+from .connectivity import InteractionVectors, _PendingSpectra
 from .numpy_host import DeviceArray as _Record      # accumulator records on the device: [n_bins][floats_per_bin] float32 / float64
 
 _host = None
@@ -294,6 +294,30 @@ class Connectivity(_TorchHostConnectivity):
             self._interaction_failed(n_fail)
         shape = self._kept_shape() + (self._n_freq, G, G)
         return mic.reshape(shape), mim.reshape(shape), labels
+
+    def maximized_imaginary_coherence_vectors(self, group_labels):
+        labels, members, sizes, _ = self._interaction_groups(group_labels)      # (the labels are checked before any device work)
+        rec, n_obs, _ = self._csm_records("interaction", two_sided=False)
+        n_total = self._n_observations_total(n_obs)
+        keep = self._interaction_kept(sizes, n_total)
+        G, n_bins, n_max = len(labels), rec.shape[0], int(sizes.max())
+        mic = np.full((n_bins, G, G), np.nan)
+        filters, patterns = np.full((n_bins, G, G, n_max), np.nan), np.full((n_bins, G, G, n_max), np.nan)
+        if len(keep) >= 2:
+            mem = self._memory()
+            sub_members, sub_sizes, _ = _lib.member_table([members[k, :sizes[k]] for k in keep])
+            a, f, p, n_fail = _stage_d.imaginary_interaction_vectors(mem, rec, self._shape5[4], _lib.PLANE_CSM, n_total, sub_members,
+                                                                     sub_sizes)
+            n_sub = int(sub_sizes.max())
+            mic[np.ix_(np.arange(n_bins), keep, keep)] = mem.download(a)
+            cells = np.ix_(np.arange(n_bins), keep, keep, np.arange(n_sub))
+            filters[cells], patterns[cells] = mem.download(f), mem.download(p)
+            self._interaction_failed(n_fail)
+        shape = self._kept_shape() + (self._n_freq, G, G)
+        return InteractionVectors(mic.reshape(shape), filters.reshape(shape + (n_max,)), patterns.reshape(shape + (n_max,)), labels,
+                                  [members[g, :sizes[g]].astype(np.int64) for g in range(G)])
+
+    maximized_imaginary_coherence_vectors.__doc__ = _TorchHostConnectivity.maximized_imaginary_coherence_vectors.__doc__
 
     def _partial_coherence(self, name):
         C, _, shape, dtype = self._partial_shape(name)

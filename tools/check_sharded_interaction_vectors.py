@@ -1,0 +1,70 @@
+"""parallel.ShardedConnectivity on the MIC vectors: every rank builds it from ITS share of the trials, the bins are split over
+the ranks and gathered (the filters and patterns with their extra trailing axis); every rank must get what one process gets from
+all the trials.  Run under torch.distributed.run; SC_BENCH_BACKEND=gloo lets all ranks share one GPU (debug / CI on a 1-GPU box)."""
+import os
+import sys
+
+import numpy as np
+import torch
+import torch.distributed as dist
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from spectral_connectivity_amd import parallel  # noqa: E402
+
+
+def main():
+    import spectral_connectivity_amd as sc
+    world, rank = int(os.environ["WORLD_SIZE"]), int(os.environ["RANK"])
+    backend = os.environ.get("SC_BENCH_BACKEND", "nccl")
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    if backend != "nccl":
+        local %= max(torch.cuda.device_count(), 1)
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    dist.init_process_group(backend, **({"device_id": dev} if backend == "nccl" else {}))
+    rng = np.random.default_rng(12)
+    T, R, C = 512, 9, 14                                      # 9 trials: unequal shards
+    e = rng.standard_normal((T, R, C))
+    x = np.zeros_like(e)
+    for t in range(2, T):
+        x[t] = 0.4 * x[t - 1] - 0.2 * x[t - 2] + e[t]
+        x[t, :, 1:] += 0.3 * x[t - 2, :, :-1]
+    kw = dict(sampling_frequency=200.0, time_halfbandwidth_product=2, n_time_samples_per_window=128,
+              n_time_samples_per_step=128)
+    labels = np.array(["c", "a", "b"] * 4 + ["a", "b"])
+    lo, hi = parallel.shard_bounds(R, world, rank)
+    # The two estimates sum the trials in different orders, so their records differ by rounding and a vector by that times its
+    # eigenvector amplification (unbounded where two singular values cross): the values, shapes, NaN cells and members are
+    # compared everywhere, the vectors where the two sides span the same direction -- which must be nearly everywhere.
+    for dtype, tol in ((np.complex64, 1e-4), (np.complex128, 1e-9)):
+        mine = parallel.ShardedConnectivity.from_multitaper(sc.Multitaper(x[:, lo:hi], **kw), dtype=dtype)
+        whole = sc.Connectivity.from_multitaper(sc.Multitaper(x, **kw), dtype=dtype)
+        a = mine.maximized_imaginary_coherence_vectors(labels)
+        b = whole.maximized_imaginary_coherence_vectors(labels)
+        assert a.mic.shape == b.mic.shape == (4, 65, 3, 3) and a.filters.shape == b.filters.shape == (4, 65, 3, 3, 5), a.filters.shape
+        assert a.patterns.shape == b.patterns.shape == (4, 65, 3, 3, 5)
+        assert list(a.labels) == list(b.labels) == ["a", "b", "c"]
+        assert all(np.array_equal(p, q) for p, q in zip(a.members, b.members)) and [len(m) for m in a.members] == [5, 5, 4]
+        for name in ("mic", "filters", "patterns"):
+            assert np.array_equal(np.isnan(getattr(a, name)), np.isnan(getattr(b, name))), name
+        ok = ~np.isnan(b.mic)
+        err = np.abs(a.mic[ok] - b.mic[ok]).max()
+        assert err <= tol * max(1.0, np.abs(b.mic[ok]).max()), f"mic ({np.dtype(dtype)}): {err}"
+        # every finite entry of this rank's gathered arrays was computed by some rank: interior bins hold finite vectors
+        assert np.isfinite(a.filters[:, 1:-1, 0, 1]).all() and np.isfinite(a.patterns[:, 1:-1, 2, 0, :4]).all()
+        pa, pb = np.nan_to_num(a.patterns[:, 1:-1]), np.nan_to_num(b.patterns[:, 1:-1])
+        cos = np.abs((pa * pb).sum(-1)) / np.maximum(np.linalg.norm(pa, axis=-1) * np.linalg.norm(pb, axis=-1), 1e-300)
+        off = ~np.eye(3, dtype=bool)
+        close = cos[..., off] >= 1 - 1e3 * tol
+        assert close.mean() >= 0.9, f"patterns ({np.dtype(dtype)}): only {close.mean():.2f} of the pairs agree"
+        same = np.abs(a.patterns[:, 1:-1] - b.patterns[:, 1:-1])[..., off, :]
+        same = np.nanmax(same, axis=-1)[close]
+        assert np.median(same) <= 100 * tol, f"patterns ({np.dtype(dtype)}): median difference {np.median(same)}"
+    dist.barrier()
+    if rank == 0:
+        print("sharded interaction vectors OK")
+    dist.destroy_process_group()
+
+
+if __name__ == "__main__":
+    main()
