@@ -665,6 +665,37 @@ int sc_partial_coherence_given_f64(const void* d_accum, int64_t n_bins, int64_t 
                                    int n_given, void* d_coherency /*complex128 [n_bins][a][a]*/, double* d_magnitude,
                                    double* d_multiple /*[n_bins][a]*/, int32_t* d_fail /*[2]*/, void* stream);
 
+/* ---- total, instantaneous and lagged linear dependence (fp64; sc_dependence.hip; additive, ABI v8) ----
+ * Pascual-Marqui's decomposition of the linear dependence between two groups of signals (arXiv:0706.1776; Phil. Trans. R. Soc. A
+ * 369:3768, 2011; "lagged coherence" of LORETA-KEY and FieldTrip; the reference has none of it).  Per (bin, pair of disjoint
+ * groups a, b with p and q signals, J = a then b), S the normalised Hermitian cross-spectral matrix:
+ *     F_total         = ln det S_aa    + ln det S_bb    - ln det S_JJ        = -sum_k ln(1 - rho_k^2), rho_k the canonical coherences
+ *     F_instantaneous = ln det Re S_aa + ln det Re S_bb - ln det Re S_JJ
+ *     F_lagged        = F_total - F_instantaneous                            0 wherever the cross-spectrum is real
+ * (Pascual-Marqui's coherences are 1 - exp(-F).)  All three are symmetric in (a, b) and unchanged under S -> D S D; the kernels
+ * work on the unit-diagonal matrix.  Arguments, member table and stride, checks and error codes of sc_imaginary_interaction_f64.
+ *   d_total, d_instantaneous, d_lagged   double [n_bins][n_groups][n_groups], symmetric, NaN diagonal; any may be NULL, not all
+ *                 three (SC_EINVAL)
+ *   d_fail        int32 [1]: the (bin, pair) problems that failed, NaN in every output -- a member without finite positive power
+ *                 (or outside the record), or a pivot of one of the unit-diagonal Cholesky factorisations that is not finite or
+ *                 <= n 2^-52 (n = p + q, for the block of b alone n = q)
+ * A pair with p + q > n_observations has a singular joint matrix: it is left NaN, not computed and not counted.  A pair with
+ * p + q > sc_linear_dependence_max_joint() = 128 gives SC_EUNSUPPORTED before any kernel is launched, the message naming the
+ * size: from max_group_size alone where that decides (a group of 128 has no partner), else -- only when two groups of
+ * max_group_size would exceed the limit -- from the two largest entries of d_sizes, which are then read back first (one small
+ * copy and a wait on `stream`).
+ * max_group_size = 1 (every group a single signal; any n_signals): one thread per entry, closed forms of the coherency c,
+ *     -log1p(-|c|^2), -log1p(-(Re c)^2), log1p((Im c)^2 / (1 - |c|^2)); NaN and counted where 1 - |c|^2 <= 0.  No workspace.
+ * Groups: a 256-thread persistent workgroup per (bin, pair) factorises the packed lower triangle of S'_JJ in LDS (132 KB at
+ * n = 128), then of Re S'_JJ with a real-typed routine on half the bytes; 2 sum_{k >= p} ln L_kk of each is ln det (JJ) -
+ * ln det (aa).  The determinants of the b blocks come from a first launch per (bin, group) that fills a [n_bins][n_groups][2]
+ * table in a stream-ordered workspace (hipMallocAsync / hipFreeAsync on `stream`; SC_ENOMEM if that fails). */
+int sc_linear_dependence_max_joint(void);
+int sc_linear_dependence_f64(const void* d_accum, int64_t n_bins, int64_t n_signals, uint32_t planes,
+                             int64_t n_observations, const int32_t* d_members, const int32_t* d_sizes,
+                             int n_groups, int max_group_size, double* d_total, double* d_instantaneous,
+                             double* d_lagged, int32_t* d_fail, void* stream);
+
 /* ---- delete-one jackknife of power and coherence (sc_jackknife.hip; additive, ABI v8) ------------------------
  * Standard errors that rest on the data (Thomson & Chave 1991; Chronux coherencyc / mtspectrumc with err = [2 p]); the
  * reference has only the closed forms of statistics.py.  Per kept index and bin the delete units u = 1 .. n hold g

@@ -171,6 +171,9 @@ SYMBOLS = {
     "sc_interaction_vectors_lds_group": (c_int, [c_int]),
     "sc_imaginary_interaction_vectors_f64": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_void_p, c_void_p,
                                                      c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sc_linear_dependence_max_joint": (c_int, []),
+    "sc_linear_dependence_f64": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_void_p, c_void_p,
+                                         c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sc_partial_coherence_max_signals": (c_int, []),
     "sc_partial_coherence_f64": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p]),
@@ -355,6 +358,16 @@ def interaction_groups(group_labels, n_signals, max_group):
     (labels, members, sizes, stride) -- ``labels`` = np.unique of ``group_labels``, then member_table of the groups in that
     order.  ValueError for a label list of the wrong length, fewer than two groups and a group of more than ``max_group``
     channels (sc_canonical_max_group())."""
+    labels, groups = _labelled_groups(group_labels, n_signals)
+    for lab, g in zip(labels, groups):
+        if len(g) > max_group:
+            raise ValueError(f"imaginary interaction: group {lab.item()!r} has {len(g)} channels; a group may have at most "
+                             f"{max_group}")
+    return (labels,) + member_table(groups)
+
+
+def _labelled_groups(group_labels, n_signals):
+    """(np.unique of the labels, the channel indices of every group) after the label checks of interaction_groups."""
     import numpy as np
     group_labels = np.asarray(group_labels)
     if group_labels.ndim != 1 or len(group_labels) != n_signals:
@@ -362,12 +375,37 @@ def interaction_groups(group_labels, n_signals, max_group):
     labels = np.unique(group_labels)
     if len(labels) < 2:
         raise ValueError(f"imaginary interaction needs at least two groups of signals (got {len(labels)})")
-    groups = [np.flatnonzero(group_labels == lab) for lab in labels]
-    for lab, g in zip(labels, groups):
-        if len(g) > max_group:
-            raise ValueError(f"imaginary interaction: group {lab.item()!r} has {len(g)} channels; a group may have at most "
-                             f"{max_group}")
+    return labels, [np.flatnonzero(group_labels == lab) for lab in labels]
+
+
+def dependence_groups(group_labels, n_signals, max_joint):
+    """Labels of linear_dependence, checked before any device work (both hosts): (labels, members, sizes, stride) as
+    interaction_groups, with its label checks and messages.  ``group_labels`` None: every signal is its own group, labels =
+    np.arange(n_signals).  ValueError for a pair of groups with more than ``max_joint`` signals together
+    (sc_linear_dependence_max_joint()): the two largest groups decide."""
+    import numpy as np
+    if group_labels is None:
+        if n_signals < 2:
+            raise ValueError(f"linear dependence needs at least two signals (got {n_signals})")
+        labels, groups = np.arange(n_signals), [np.array([c]) for c in range(n_signals)]
+    else:
+        labels, groups = _labelled_groups(group_labels, n_signals)
+    if len(groups) >= 2:
+        a, b = sorted(np.argsort([len(g) for g in groups], kind="stable")[-2:].tolist())
+        m = len(groups[a]) + len(groups[b])
+        if m > max_joint:
+            raise ValueError(f"linear dependence: groups {labels[a].item()!r} and {labels[b].item()!r} have {m} signals together; "
+                             f"a pair of groups may have at most {max_joint}")
     return (labels,) + member_table(groups)
+
+
+def dependence_rank_skipped(sizes, n_obs):
+    """Number of group pairs with more signals together than the ``n_obs`` observations: their joint cross-spectral matrix is
+    singular and the device leaves them NaN."""
+    import numpy as np
+    s = np.asarray(sizes, dtype=np.int64)
+    over = (s[:, None] + s[None, :]) > n_obs
+    return int(np.triu(over, 1).sum())
 
 
 def interaction_kept(sizes, n_obs):

@@ -248,6 +248,22 @@ def imaginary_interaction_vectors(mem, accum, n_signals, planes, n_obs, members,
     return mic, filters, patterns, mem.read_int(fail)
 
 
+def linear_dependence(mem, accum, n_signals, planes, n_obs, members, sizes, want):
+    """Total, instantaneous and lagged linear dependence between the groups (sc_dependence.hip).  members / sizes:
+    _lib.member_table of the groups; ``want``: names out of "total", "instantaneous", "lagged" -- one call serves them all.
+    Returns ({name: [n_bins, G, G] float64 device array}, n_fail)."""
+    G, n_bins = len(sizes), accum.shape[0]
+    d_members, d_sizes = mem.upload(members), mem.upload(sizes)
+    out = {name: mem.empty((n_bins, G, G), np.float64) for name in want}
+    fail = mem.zeros((1,), np.int32)
+    _lib.check(_lib._handle().sc_linear_dependence_f64(mem.ptr(accum), n_bins, n_signals, _planes(mem, accum, planes), n_obs,
+                                                       mem.ptr(d_members), mem.ptr(d_sizes), G, int(sizes.max()),
+                                                       _ptr(mem, out.get("total")), _ptr(mem, out.get("instantaneous")),
+                                                       _ptr(mem, out.get("lagged")), mem.ptr(fail), mem.stream()),
+               "sc_linear_dependence_f64")
+    return out, mem.read_int(fail)
+
+
 def partial_coherence(mem, accum, n_signals, planes, n_obs, want):
     """Partial and multiple coherence of every bin record (sc_partial.hip).  ``want``: names out of "coherency", "magnitude",
     "multiple" -- one call serves them all.  Returns ({name: device array}, n_fail): coherency complex128 and magnitude float64

@@ -35,6 +35,7 @@ EXPECTATION = dict.fromkeys(EXPECTATION_AXES)
 
 # what maximized_imaginary_coherence_vectors returns
 InteractionVectors = namedtuple("InteractionVectors", ("mic", "filters", "patterns", "labels", "members"))
+LinearDependence = namedtuple("LinearDependence", ("total", "instantaneous", "lagged", "labels"))
 
 
 class _PendingSpectra:
@@ -755,6 +756,69 @@ class Connectivity:
         return InteractionVectors(engine.to_host(mic).reshape(shape), engine.to_host(filters).reshape(shape + (n_max,)),
                                   engine.to_host(patterns).reshape(shape + (n_max,)), labels,
                                   [members[g, :sizes[g]].astype(np.int64) for g in range(G)])
+
+    # ---- total, instantaneous and lagged linear dependence (Pascual-Marqui 2007, arXiv:0706.1776) -----------------
+    def linear_dependence(self, group_labels=None):
+        """Pascual-Marqui's decomposition of the linear dependence between each pair of signal groups a, b (J their union) into an
+        instantaneous (zero-lag) and a lagged part, per frequency, with S the cross-spectral matrix:
+
+        ``total``          ln det S_aa + ln det S_bb - ln det S_JJ = -sum_k ln(1 - rho_k^2) over the canonical coherences
+        ``instantaneous``  the same of Re S
+        ``lagged``         total - instantaneous: 0 wherever the cross-spectrum is real, so instantaneous mixing (volume
+                           conduction, source leakage) cannot create it
+
+        All are >= 0 and unchanged by real invertible mixing inside a group (the total also by complex mixing); Pascual-Marqui's
+        coherences are 1 - exp(-F).  ``group_labels`` None: every signal is its own group (``lagged_coherence`` gives the
+        pairwise lagged coherence directly).
+
+        Returns the named tuple (total, instantaneous, lagged, labels): float64 arrays [kept axes..., n_frequencies, G, G],
+        symmetric with a NaN diagonal, over the object's ``expectation_type``; ``labels`` = np.unique(group_labels) (np.arange of
+        the signals without labels).  A pair of groups may have up to sc_linear_dependence_max_joint() = 128 signals together
+        (ValueError beyond, naming the pair; single signals: any number).  A pair with more signals than observations has a
+        singular joint matrix: NaN (one warning counts the pairs), as is a (frequency, pair) whose matrices the device cannot
+        factorise -- a signal without power, or not positive definite to rounding (one warning counts them).  sc_dependence.hip,
+        DESIGN 4.15.
+        """
+        out, labels = self._linear_dependence(group_labels, ("total", "instantaneous", "lagged"))
+        return LinearDependence(out["total"], out["instantaneous"], out["lagged"], labels)
+
+    def lagged_coherence(self):
+        """Lagged coherence of each pair of signals (Pascual-Marqui 2007; LORETA-KEY, FieldTrip): the squared quantity
+        rho^2_lag = (Im c)^2 / (1 - (Re c)^2) of the coherency c, = 1 - exp(-F_lagged) of ``linear_dependence()``; in [0, 1], 0
+        wherever the cross-spectrum is real.  float64 [kept axes..., n_frequencies, n_signals, n_signals], symmetric with a NaN
+        diagonal.  NaN entries and warnings as ``linear_dependence``."""
+        out, _ = self._linear_dependence(None, ("lagged",))
+        return -np.expm1(-out["lagged"])
+
+    def _dependence_groups(self, group_labels):
+        return _lib.dependence_groups(group_labels, self._shape5[4], int(_lib.load().sc_linear_dependence_max_joint()))
+
+    def _dependence_warnings(self, sizes, n_total, n_fail):
+        n_skipped = _lib.dependence_rank_skipped(sizes, n_total)
+        if n_skipped:
+            logger.warning(f"linear dependence: {n_skipped} group pairs have more signals together than the {n_total} observations "
+                           "(singular joint cross-spectral matrix): NaN")
+        if n_fail:
+            logger.warning(f"linear dependence: {n_fail} (frequency, pair) problems have a signal without power or a cross-spectral "
+                           "matrix that is not positive definite to rounding (NaN output)")
+
+    def _linear_dependence(self, group_labels, want):
+        """({name: [kept axes..., n_frequencies, G, G] float64} for the names of ``want``, labels)."""
+        from . import engine
+        import torch
+        labels, members, sizes, _ = self._dependence_groups(group_labels)       # (the labels are checked before any device work)
+        accum, n_obs, _ = self._csm_records("interaction", two_sided=False)
+        n_total = self._n_observations_total(n_obs)
+        G = len(labels)
+        lo, hi, per = self._canonical_bins(accum.shape[0])
+        n_fail = 0
+        if hi > lo:
+            res, n_fail = engine.linear_dependence(accum[lo:hi], self._shape5[4], _lib.PLANE_CSM, n_total, members, sizes, want)
+        else:                                  # more processes than bins: this one has nothing to evaluate
+            res = {name: torch.empty((0, G, G), dtype=torch.float64, device=accum.device) for name in want}
+        self._dependence_warnings(sizes, n_total, n_fail)
+        shape = self._kept_shape() + (self._n_freq, G, G)
+        return {name: engine.to_host(self._canonical_gather(res[name], accum.shape[0], per)).reshape(shape) for name in want}, labels
 
     # ---- partial and multiple coherence (Bendat & Piersol 1986, ch. 7; Dahlhaus 2000) ----------------------------
     def partial_coherency(self, given=None, signals=None):

@@ -527,6 +527,12 @@ def imaginary_interaction_vectors(accum, n_signals, planes, n_obs, members, size
     return _stage_d.imaginary_interaction_vectors(TorchMemory(accum.device), accum, n_signals, planes, n_obs, members, sizes)
 
 
+def linear_dependence(accum, n_signals, planes, n_obs, members, sizes, want):
+    """Total, instantaneous and lagged linear dependence between the groups (sc_dependence.hip): _stage_d.linear_dependence.
+    Returns ({name: [n_bins, G, G] float64 tensor} for the names in ``want``, n_fail)."""
+    return _stage_d.linear_dependence(TorchMemory(accum.device), accum, n_signals, planes, n_obs, members, sizes, want)
+
+
 def partial_coherence(accum, n_signals, planes, n_obs, want):
     """Partial and multiple coherence of every bin record (sc_partial.hip): _stage_d.partial_coherence.  Returns ({name: tensor}
     for the names of ``want`` out of "coherency", "magnitude", "multiple", n_fail)."""

@@ -319,6 +319,16 @@ class Connectivity(_TorchHostConnectivity):
 
     maximized_imaginary_coherence_vectors.__doc__ = _TorchHostConnectivity.maximized_imaginary_coherence_vectors.__doc__
 
+    def _linear_dependence(self, group_labels, want):
+        labels, members, sizes, _ = self._dependence_groups(group_labels)       # (the labels are checked before any device work)
+        rec, n_obs, _ = self._csm_records("interaction", two_sided=False)
+        n_total = self._n_observations_total(n_obs)
+        mem = self._memory()
+        res, n_fail = _stage_d.linear_dependence(mem, rec, self._shape5[4], _lib.PLANE_CSM, n_total, members, sizes, want)
+        self._dependence_warnings(sizes, n_total, n_fail)
+        shape = self._kept_shape() + (self._n_freq, len(labels), len(labels))
+        return {name: np.array(mem.download(res[name])).reshape(shape) for name in want}, labels
+
     def _partial_coherence(self, name):
         C, _, shape, dtype = self._partial_shape(name)
         rec, n_obs, _ = self._csm_records("interaction", two_sided=False)
