@@ -608,6 +608,30 @@ int sc_imaginary_interaction_vectors_f64(const void* d_accum, int64_t n_bins, in
                                          int n_groups, int max_group_size, double* d_mic, double* d_filters,
                                          double* d_patterns, int32_t* d_fail, void* stream);
 
+/* ---- the vectors that attain canonical coherence, and its whole spectrum (fp64; sc_canonical.hip; additive, ABI v8) ----
+ * Per (bin, group pair a < b) of the records as sc_canonical_coherence_f64 reads them, with S_gg = L_g L_g^H, M = L_a^-1 S_ab L_b^-H,
+ * rho_1 >= rho_2 >= ... the singular values of M (the canonical coherences; sc_canonical_coherence_f64 gives rho_1^2), p the unit
+ * eigenvector of M M^H for rho_1^2 and q = M^H p / rho_1:
+ *     filters  alpha = L_a^-H p, beta = L_b^-H q   (alpha^H S_aa alpha = beta^H S_bb beta = 1, alpha^H S_ab beta = rho_1, real)
+ *     patterns a = L_a p = S_aa alpha, b = L_b q = S_bb beta   (S_ab beta = rho_1 a, S_ab^H alpha = rho_1 b).
+ * One joint unit phase per pair: the entry of pattern a with the largest magnitude (lowest index on a tie) is real and positive.
+ * Arguments, member table, checks and error codes of sc_imaginary_interaction_vectors_f64.
+ *   d_coherence            double [n_bins][n_groups][n_groups]: rho_1, symmetric, NaN diagonal
+ *   d_coherences           double [n_bins][n_groups][n_groups][max_group_size]: rho_k = sqrt(clamp(lambda_k, 0, 1)), descending,
+ *                          the same in [a][b] and [b][a]; NaN beyond min(n_a, n_b), on the diagonal and for a failed pair
+ *   d_filters, d_patterns  double [n_bins][n_groups][n_groups][max_group_size][2] (re, im): entry [a][b][0 .. n_a) is group a's
+ *                          vector in its pairing with group b (both orders of a pair are filled), NaN beyond n_a, on the diagonal,
+ *                          for a failed pair and for a pair whose M is exactly 0 (every rho_k 0: no direction is singled out)
+ *   d_fail                 int32 [1]: number of pairs with a group block that was not positive definite (NaN in every output)
+ * One 256-thread workgroup per (bin, pair), persistent; parallel Jacobi on the packed Hermitian M M^H with a rotation log.  A pair
+ * whose groups have at most sc_canonical_vectors_lds_group(max_group_size) channels keeps its three blocks in LDS, the others in
+ * a stream-ordered scratch; workspace as sc_imaginary_interaction_vectors_f64. */
+int sc_canonical_vectors_lds_group(int max_group_size);
+int sc_canonical_coherence_vectors_f64(const void* d_accum, int64_t n_bins, int64_t n_signals, uint32_t planes,
+                                       int64_t n_observations, const int32_t* d_members, const int32_t* d_sizes,
+                                       int n_groups, int max_group_size, double* d_coherence, double* d_coherences,
+                                       double* d_filters, double* d_patterns, int32_t* d_fail, void* stream);
+
 /* ---- partial and multiple coherence (fp64, from the accumulated CSM; sc_partial.hip; additive, ABI v8) ----
  * The coherence of two signals after the linear influence of all the other signals is removed, and the share of a signal's
  * power that all the others explain linearly (the reference has neither).  Per bin record, with S the normalised Hermitian

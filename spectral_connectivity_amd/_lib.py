@@ -171,6 +171,9 @@ SYMBOLS = {
     "sc_interaction_vectors_lds_group": (c_int, [c_int]),
     "sc_imaginary_interaction_vectors_f64": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_void_p, c_void_p,
                                                      c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sc_canonical_vectors_lds_group": (c_int, [c_int]),
+    "sc_canonical_coherence_vectors_f64": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_void_p, c_void_p,
+                                                   c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sc_linear_dependence_max_joint": (c_int, []),
     "sc_linear_dependence_f64": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_void_p, c_void_p,
                                          c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

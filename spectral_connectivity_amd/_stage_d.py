@@ -248,6 +248,23 @@ def imaginary_interaction_vectors(mem, accum, n_signals, planes, n_obs, members,
     return mic, filters, patterns, mem.read_int(fail)
 
 
+def canonical_coherence_vectors(mem, accum, n_signals, planes, n_obs, members, sizes):
+    """The vectors that attain canonical coherence and every canonical coherence (sc_canonical_coherence_vectors_f64).
+    members / sizes: _lib.member_table of the groups.  Returns (coherence [n_bins, G, G], coherences [n_bins, G, G, n_max],
+    filters, patterns [n_bins, G, G, n_max, 2] (re, im), all float64, n_fail)."""
+    G, n_bins, n_max = len(sizes), accum.shape[0], int(sizes.max())
+    d_members, d_sizes = mem.upload(members), mem.upload(sizes)
+    coherence, coherences = mem.empty((n_bins, G, G), np.float64), mem.empty((n_bins, G, G, n_max), np.float64)
+    filters, patterns = mem.empty((n_bins, G, G, n_max, 2), np.float64), mem.empty((n_bins, G, G, n_max, 2), np.float64)
+    fail = mem.zeros((1,), np.int32)
+    _lib.check(_lib._handle().sc_canonical_coherence_vectors_f64(mem.ptr(accum), n_bins, n_signals, _planes(mem, accum, planes),
+                                                                 n_obs, mem.ptr(d_members), mem.ptr(d_sizes), G, n_max,
+                                                                 mem.ptr(coherence), mem.ptr(coherences), mem.ptr(filters),
+                                                                 mem.ptr(patterns), mem.ptr(fail), mem.stream()),
+               "sc_canonical_coherence_vectors_f64")
+    return coherence, coherences, filters, patterns, mem.read_int(fail)
+
+
 def linear_dependence(mem, accum, n_signals, planes, n_obs, members, sizes, want):
     """Total, instantaneous and lagged linear dependence between the groups (sc_dependence.hip).  members / sizes:
     _lib.member_table of the groups; ``want``: names out of "total", "instantaneous", "lagged" -- one call serves them all.

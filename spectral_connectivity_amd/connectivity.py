@@ -35,6 +35,7 @@ EXPECTATION = dict.fromkeys(EXPECTATION_AXES)
 
 # what maximized_imaginary_coherence_vectors returns
 InteractionVectors = namedtuple("InteractionVectors", ("mic", "filters", "patterns", "labels", "members"))
+CanonicalVectors = namedtuple("CanonicalVectors", ("coherence", "coherences", "filters", "patterns", "labels", "members"))
 LinearDependence = namedtuple("LinearDependence", ("total", "instantaneous", "lagged", "labels"))
 
 
@@ -630,6 +631,91 @@ class Connectivity:
                              "<= the group size (their coherence is then 1) -- the whitening kernel takes up to "
                              f"{max_group} channels per group")
         return labels, groups, small
+
+    def canonical_coherence_vectors(self, group_labels):
+        """The channel weights that attain the canonical coherence of each pair of channel groups, the topographies to plot for
+        them, and every further canonical coherence of the pair.  Per frequency and pair of groups a, b of the cross-spectral
+        matrix S (always averaged over trials and tapers, as ``canonical_coherence``), with rho_1 >= rho_2 >= ... the singular
+        values of S_aa^-1/2 S_ab S_bb^-1/2:
+
+        ``coherence``: rho_1 (``canonical_coherence`` returns its square, as the reference does).
+        ``coherences``: every rho_k, descending; -sum_k ln(1 - rho_k^2) is ``linear_dependence().total``.
+        ``filters``: the complex weights alpha (group a), beta (group b) with alpha^H S_aa alpha = beta^H S_bb beta = 1 that
+        maximise alpha^H S_ab beta = rho_1 (real) -- project the data of a group onto its filter to get the coupled component.
+        ``patterns``: a = S_aa alpha, b = S_bb beta -- how strongly every channel sees that component (Haufe et al. 2014): these
+        are the maps to plot, not the filters.  S_ab beta = rho_1 a and S_ab^H alpha = rho_1 b.
+        One joint unit phase per pair is free: the entry of largest magnitude (lowest index on a tie) of the pattern of the group
+        with the lower label is real and positive (the rule of ``global_coherence``).
+
+        Returns the named tuple (coherence, coherences, filters, patterns, labels, members): ``coherence`` float64
+        [n_time_windows, n_frequencies, G, G], NaN diagonal; ``coherences`` float64 [..., G, G, n_max], NaN beyond min(n_a, n_b) and
+        on the diagonal; ``filters`` and ``patterns`` complex128 [..., G, G, n_max] with entry [..., a, b, :n_a] the vector of group a
+        in its pairing with group b (both orders of a pair are filled), NaN beyond n_a and on the diagonal; ``labels`` =
+        np.unique(group_labels); ``members[g]`` the channel indices of group g in the order of the last axis.  Group sizes, the
+        ValueError for a group that is too large and the warning for blocks that are not positive definite (NaN in every output
+        of the pair) are those of ``canonical_coherence``.  A group with at least as many channels as observations has coherence 1
+        with every other group: ``coherences[..., :min(n_a, n_b)]`` is 1 and the vectors are NaN (no direction is singled out).
+        A pair whose cross-spectrum is exactly 0 has coherences 0 and NaN vectors (no warning).  Elsewhere the vectors are
+        computed however small rho_1 is -- they mean nothing where rho_1 is not distinguishable from 0, and where rho_1 and
+        rho_2 nearly coincide they are one of many equally good pairs (sc_canonical.hip).
+        """
+        from . import engine
+        import torch
+        group_labels = self._canonical_labels(group_labels)                     # (the labels are checked before any device work)
+        accum, n_obs, _ = self._csm_records("canonical", "trials_tapers", two_sided=False)
+        n_total = self._n_observations_total(n_obs)
+        labels, groups, small = self._canonical_groups(group_labels, n_total)
+        G, n_max = len(groups), max(len(g) for g in groups)
+        lo, hi, per = self._canonical_bins(accum.shape[0])
+        n_part = max(hi - lo, 0)
+        coherence = torch.ones((n_part, G, G), dtype=torch.float64, device=accum.device)
+        coherence[:, torch.arange(G), torch.arange(G)] = float("nan")
+        coherences = torch.as_tensor(self._canonical_ones(groups), device=accum.device).expand(n_part, G, G, n_max).clone()
+        filters = torch.full((n_part, G, G, n_max, 2), float("nan"), dtype=torch.float64, device=accum.device)
+        patterns = filters.clone()
+        n_fail = 0
+        if hi > lo and len(small) >= 2:
+            sub_members, sub_sizes, _ = _lib.member_table([groups[k] for k in small])
+            c, cs, f, p, n_fail = engine.canonical_coherence_vectors(accum[lo:hi], self._shape5[4], _lib.PLANE_CSM, n_total,
+                                                                     sub_members, sub_sizes)
+            idx = torch.as_tensor(small, device=accum.device)
+            coherence[:, idx[:, None], idx[None, :]] = c
+            coherences[:, idx[:, None], idx[None, :]] = float("nan")
+            coherences[:, idx[:, None], idx[None, :], :cs.shape[-1]] = cs
+            filters[:, idx[:, None], idx[None, :], :f.shape[-2]] = f
+            patterns[:, idx[:, None], idx[None, :], :p.shape[-2]] = p
+        parts = [self._canonical_gather(t, accum.shape[0], per) for t in (coherence, coherences, filters, patterns)]
+        self._canonical_failed(n_fail)
+        return self._canonical_vectors_result([engine.to_host(t) for t in parts], labels, groups)
+
+    def _canonical_labels(self, group_labels):
+        group_labels = np.asarray(group_labels)
+        if group_labels.shape != (self._shape5[4],):
+            raise ValueError(f"canonical_coherence_vectors: group_labels needs one label per signal ({self._shape5[4]}), got shape "
+                             f"{group_labels.shape}")
+        return group_labels
+
+    @staticmethod
+    def _canonical_ones(groups):
+        """coherences before the device fills the pairs it evaluates [G, G, n_max]: 1 up to min(n_a, n_b) (every canonical
+        coherence of a pair with a group that spans the observation space is 1), NaN beyond and on the diagonal."""
+        G, n_max = len(groups), max(len(g) for g in groups)
+        ones = np.full((G, G, n_max), np.nan)
+        for a in range(G):
+            for b in range(G):
+                if a != b:
+                    ones[a, b, :min(len(groups[a]), len(groups[b]))] = 1.0
+        return ones
+
+    def _canonical_vectors_result(self, host, labels, groups):
+        """The named tuple from the four host arrays [n_bins, G, G(, n_max(, 2))]: (re, im) pairs become complex128."""
+        coherence, coherences, filters, patterns = (np.ascontiguousarray(t) for t in host)
+        G, n_max = len(groups), coherences.shape[-1]
+        shape = (self._shape5[0], self._n_freq, G, G)
+        return CanonicalVectors(coherence.reshape(shape), coherences.reshape(shape + (n_max,)),
+                                filters.view(np.complex128).reshape(shape + (n_max,)),
+                                patterns.view(np.complex128).reshape(shape + (n_max,)), labels,
+                                [np.asarray(g, dtype=np.int64) for g in groups])
 
     def _canonical_failed(self, n_fail):
         if n_fail:

@@ -1002,15 +1002,16 @@ struct IvArgs {
 
 // dynamic LDS of a launch: the packed triangle of B and the Jacobi's tables for groups of up to bn channels, four vectors, and
 // three blocks of lds_n x (lds_n | 1)
-static size_t iv_lds_bytes(int bn, int lds_n) {
+// (vec: the size of a vector entry -- double here, cd for the canonical vectors below)
+static size_t iv_lds_bytes(int bn, int lds_n, size_t vec = sizeof(double)) {
     const size_t hm = (size_t)(bn + 1) / 2;
-    return ((size_t)bn * (bn + 1) / 2 + hm + (size_t)3 * lds_n * (lds_n | 1)) * sizeof(cd) + (4 * CBIG_C + hm) * sizeof(double) +
+    return ((size_t)bn * (bn + 1) / 2 + hm + (size_t)3 * lds_n * (lds_n | 1)) * sizeof(cd) + 4 * CBIG_C * vec + hm * sizeof(double) +
            2 * hm * sizeof(int) + hm * (hm + 1) * sizeof(unsigned short) + 16;
 }
 // the largest group size up to which a pair keeps its blocks in LDS, in a launch whose largest group has max_group channels
-static int iv_lds_n(int max_group) {
+static int iv_lds_n(int max_group, size_t vec = sizeof(double)) {
     int n = max_group;
-    while (n > 0 && iv_lds_bytes(max_group, n) + IV_STATIC_LDS > IV_LDS_LIMIT) --n;
+    while (n > 0 && iv_lds_bytes(max_group, n, vec) + IV_STATIC_LDS > IV_LDS_LIMIT) --n;
     return n;
 }
 extern "C" int sc_interaction_vectors_lds_group(int max_group_size) {
@@ -1168,6 +1169,206 @@ __global__ void __launch_bounds__(256) interaction_vectors_kernel(CanonArgs a, I
             const size_t oa = (((size_t)bin * a.G + ga) * a.G + gb) * v.vstride, ob = (((size_t)bin * a.G + gb) * a.G + ga) * v.vstride;
             for (int i = tid; i < na; i += 256) { v.filters[oa + i] = sg * xa[i]; v.patterns[oa + i] = sg * pv[i]; }
             for (int j = tid; j < nb; j += 256) { v.filters[ob + j] = sg * xb[j]; v.patterns[ob + j] = sg * qv[j]; }
+        }
+        __syncthreads();
+    }
+}
+
+// ---- the vectors that attain canonical coherence, and its whole spectrum ----------------------------------------
+// The complex-Hermitian sibling of interaction_vectors_kernel, on the records as canonical coherence reads them (csm_group<false>,
+// csm_cross<false>): S_gg = L_g L_g^H, M = L_a^-1 S_ab L_b^-H, B = M M^H (packed Hermitian triangle in LDS) with eigenvalues
+// rho_1^2 >= rho_2^2 >= ..., p the unit eigenvector for rho_1^2 -- from the complex rotation log, J = [[c, s], [-conj s, c]] -- and
+// q = M^H p / rho_1:
+//     filters   alpha = L_a^-H p,  beta = L_b^-H q        patterns   a = L_a p,  b = L_b q        coherences  rho_k, descending.
+// Same residency rule, workspace and item walk as the kernel above; the four vectors are complex, so the LDS edge is
+// iv_lds_n(n, sizeof(cd)).  When B sits on the side of the group with the higher label the cross block read is S_ba = S_ab^H: M
+// becomes M^H and p, q change roles -- no sign changes.  One joint unit phase: the entry of largest magnitude (lowest index on a
+// tie) of the pattern of the group with the lower label is real and positive (global_coherence's rule).
+struct CvArgs {
+    double* coherences;    // [n_bins][G][G][vstride]
+    cd* filters;           // [n_bins][G][G][vstride]
+    cd* patterns;
+    double* log;           // as IvArgs
+    cd* scratch;
+    int vstride, bn, lds_n, lds_ld;
+};
+
+extern "C" int sc_canonical_vectors_lds_group(int max_group_size) {
+    return max_group_size < 1 || max_group_size > CBIG_C ? 0 : iv_lds_n(max_group_size, sizeof(cd));
+}
+
+// x <- L^-H x for the two groups at once (threads 0 .. 127: group a, 128 .. 255: group b), column-oriented back-substitution
+__device__ inline void cv_back_substitute(const cd* La, const cd* Lb, int lda, int ldb, int na, int nb, cd* xa, cd* xb, int tid) {
+    const int nmax = na > nb ? na : nb;
+    for (int i = nmax - 1; i >= 0; --i) {
+        if (tid == 0 && i < na) { const double d = La[i * lda + i].x; xa[i] = make_double2(xa[i].x / d, xa[i].y / d); }
+        if (tid == 128 && i < nb) { const double d = Lb[i * ldb + i].x; xb[i] = make_double2(xb[i].x / d, xb[i].y / d); }
+        __syncthreads();
+        if (tid < 128) {
+            if (i < na && tid < i) { const cd t = zmul_conj(xa[i], La[i * lda + tid]); xa[tid].x -= t.x; xa[tid].y -= t.y; }
+        } else {
+            const int k = tid - 128;
+            if (i < nb && k < i) { const cd t = zmul_conj(xb[i], Lb[i * ldb + k]); xb[k].x -= t.x; xb[k].y -= t.y; }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(256) canonical_vectors_kernel(CanonArgs a, CvArgs v, int64_t n_items) {
+    extern __shared__ __align__(16) unsigned char cb_smem[];
+    const int hm = (v.bn + 1) / 2;
+    cd* B = reinterpret_cast<cd*>(cb_smem);                                    // packed upper triangle, bn (bn + 1) / 2
+    cd* rs = B + (size_t)v.bn * (v.bn + 1) / 2;                                // [hm]
+    cd* blocks = rs + hm;                                                      // [3][lds_n][lds_ld]
+    cd* pv = blocks + (size_t)3 * v.lds_n * v.lds_ld;                          // [CBIG_C] p, then the pattern of a
+    cd* qv = pv + CBIG_C;                                                      // q, then the pattern of b
+    cd* xa = qv + CBIG_C;                                                      // the filter of a
+    cd* xb = xa + CBIG_C;                                                      // the filter of b
+    double* rc = reinterpret_cast<double*>(xb + CBIG_C);                       // [hm]
+    int* rp = reinterpret_cast<int*>(rc + hm);                                 // [2 hm]
+    unsigned short* blk_u = reinterpret_cast<unsigned short*>(rp + 2 * hm);    // [hm (hm + 1) / 2]
+    unsigned short* blk_v = blk_u + hm * (hm + 1) / 2;
+    __shared__ double red[2][256];                           // the Jacobi's reduction; then the eigenvalues and their sorted copy
+    __shared__ double sh_tr;
+    __shared__ cd sh_phase;
+    __shared__ int done, n_rounds, bad, tab_for, sh_src;
+    const int tid = threadIdx.x;
+    cd* Lag = v.scratch ? v.scratch + (size_t)blockIdx.x * 3 * CBIG_C * CBIG_C : nullptr;
+    const int Mb = v.bn + (v.bn & 1);
+    double* mylog = v.log + (size_t)blockIdx.x * IV_SWEEPS * (Mb - 1) * (Mb / 2) * 3;
+    if (tid == 0) tab_for = -1;
+    __syncthreads();
+    for (int64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+        int64_t bin;
+        int g_lo, g_hi;
+        canon_item(a, item, bin, g_lo, g_hi);
+        // B on the smaller group's side: ga is that group.  flip: the cross block read below is then S_ba = S_ab^H
+        const bool flip = a.sizes[g_hi] < a.sizes[g_lo];
+        const int ga = flip ? g_hi : g_lo, gb = flip ? g_lo : g_hi;
+        const int na = a.sizes[ga], nb = a.sizes[gb];
+        const int32_t* ma = a.members + ga * a.mstride;
+        const int32_t* mb = a.members + gb * a.mstride;
+        const ScRec rec = a.accum + bin * a.v.floats_per_bin;
+        const bool in_lds = nb <= v.lds_n;                   // (na <= nb)
+        const int ld = in_lds ? v.lds_ld : CBIG_C;
+        cd* PA = in_lds ? blocks : Lag;
+        cd* PB = PA + (in_lds ? v.lds_n * v.lds_ld : CBIG_C * CBIG_C);
+        cd* PM = PB + (in_lds ? v.lds_n * v.lds_ld : CBIG_C * CBIG_C);
+        if (tid == 0) bad = 0;
+        for (int e = tid; e < na * na; e += 256) { const int i = e / na, j = e % na; if (j <= i) PA[i * ld + j] = csm_group<false>(rec, a, ma[i], ma[j]); }
+        for (int e = tid; e < nb * nb; e += 256) { const int i = e / nb, j = e % nb; if (j <= i) PB[i * ld + j] = csm_group<false>(rec, a, mb[i], mb[j]); }
+        for (int e = tid; e < na * nb; e += 256) { const int i = e / nb, j = e % nb; PM[i * ld + j] = csm_cross<false>(rec, a, ma[i], mb[j]); }
+        __syncthreads();
+        sc_wg_cholesky(PA, ld, na, &bad);
+        sc_wg_cholesky(PB, ld, nb, &bad);
+        canon_whiten_rows(PA, PM, ld, na, nb, tid);
+        canon_whiten_cols(PB, PM, ld, na, nb, tid);
+        // B = M M^H, packed upper triangle in LDS (the diagonal exactly real)
+        for (int e = tid; e < na * na; e += 256) {
+            const int i = e / na, j = e % na;
+            if (i > j) continue;
+            cd sacc = make_double2(0.0, 0.0);
+            for (int k = 0; k < nb; ++k) { const cd t = zmul_conj(PM[i * ld + k], PM[j * ld + k]); sacc.x += t.x; sacc.y += t.y; }
+            if (i == j) sacc.y = 0.0;
+            B[gc_tri(i, j, na)] = sacc;
+        }
+        const int H = (na + (na & 1)) / 2;
+        if (tab_for != H) {                        // pairing table of this group size (rebuilt only when the size changes)
+            __syncthreads();
+            gc_block_table(blk_u, blk_v, H, tid);
+            if (tid == 0) tab_for = H;
+        }
+        __syncthreads();
+        if (tid == 0) {                            // trace(B) before the rotations: exactly 0 only where the cross block is 0
+            double tr = 0.0;
+            for (int i = 0; i < na; ++i) tr += B[gc_tri(i, i, na)].x;
+            sh_tr = tr;
+        }
+        gc_jacobi(B, na, rc, rs, rp, blk_u, blk_v, red, &done, &n_rounds, mylog, IV_SWEEPS);
+        __syncthreads();
+        // the spectrum in descending order by rank counting (equal values: the lower index first); rank 0 names the eigenvector
+        if (tid < na) red[0][tid] = B[gc_tri(tid, tid, na)].x;
+        __syncthreads();
+        if (tid < na) {
+            const double mine = red[0][tid];
+            int rank = 0;
+            for (int j = 0; j < na; ++j) { const double o = red[0][j]; rank += (o > mine || (o == mine && j < tid)) ? 1 : 0; }
+            if (rank < na) red[1][rank] = mine;    // (NaN eigenvalues of a failed block all count 0: such a pair stays NaN below)
+            if (rank == 0) sh_src = tid;
+        }
+        __syncthreads();
+        // p = J_1 ... J_m e_src, right to left; thread t rotates the entries of pair t of the round
+        for (int i = tid; i < na; i += 256) pv[i] = make_double2(i == sh_src ? 1.0 : 0.0, 0.0);
+        __syncthreads();
+        {
+            const int Mp = na + (na & 1);
+            const int total_rounds = n_rounds;
+            for (int rr = total_rounds - 1; rr >= 0; --rr) {
+                const int r = rr % (Mp - 1);
+                if (tid < H) {
+                    int x, y;
+                    if (tid == 0) { x = Mp - 1; y = r; }
+                    else { x = (r + tid) % (Mp - 1); y = (r - tid + (Mp - 1)) % (Mp - 1); }
+                    const int pi = x < y ? x : y, qi = x < y ? y : x;
+                    if (qi < na) {
+                        const double* lg = mylog + ((size_t)rr * H + tid) * 3;
+                        const double c = lg[0];
+                        const cd se = make_double2(lg[1], lg[2]);
+                        const cd xp = pv[pi], xq = pv[qi];
+                        const cd t1 = zmul(se, xq), t2 = zmul_conj(xp, se);          // s x_q, conj(s) x_p
+                        pv[pi] = make_double2(c * xp.x + t1.x, c * xp.y + t1.y);
+                        pv[qi] = make_double2(c * xq.x - t2.x, c * xq.y - t2.y);
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        const double tr = sh_tr;
+        const double lmax = fmax(red[1][0], 0.0);
+        const double rho = sqrt(lmax);                       // (unclamped above: q = M^H p / rho has unit norm)
+        const bool defined = !bad && tr > 0.0 && rho > 0.0;                   // (B = 0 exactly: coherences 0, no vectors)
+        // q = M^H p / rho_1, the filters' right-hand sides, then the patterns L p, L q in place of p, q
+        for (int j = tid; j < nb; j += 256) {
+            cd sacc = make_double2(0.0, 0.0);
+            for (int i = 0; i < na; ++i) { const cd t = zmul_conj(pv[i], PM[i * ld + j]); sacc.x += t.x; sacc.y += t.y; }
+            const cd qj = make_double2(sacc.x / rho, sacc.y / rho);
+            qv[j] = qj; xb[j] = qj;
+        }
+        for (int i = tid; i < na; i += 256) xa[i] = pv[i];
+        __syncthreads();
+        cd pat = make_double2(0.0, 0.0);
+        if (tid < 128) { if (tid < na) for (int k = 0; k <= tid; ++k) { const cd t = zmul(PA[tid * ld + k], pv[k]); pat.x += t.x; pat.y += t.y; } }
+        else { const int j = tid - 128; if (j < nb) for (int k = 0; k <= j; ++k) { const cd t = zmul(PB[j * ld + k], qv[k]); pat.x += t.x; pat.y += t.y; } }
+        __syncthreads();
+        if (tid < 128) { if (tid < na) pv[tid] = pat; }
+        else if (tid - 128 < nb) qv[tid - 128] = pat;
+        cv_back_substitute(PA, PB, ld, ld, na, nb, xa, xb, tid);
+        if (tid == 0) {
+            const cd* lowp = flip ? qv : pv;                 // the pattern of the group with the lower label
+            const int nl = flip ? nb : na;
+            double best = -1.0;
+            cd val = make_double2(1.0, 0.0);
+            for (int i = 0; i < nl; ++i) { const double m2 = lowp[i].x * lowp[i].x + lowp[i].y * lowp[i].y; if (m2 > best) { best = m2; val = lowp[i]; } }
+            const double ab = sqrt(best);
+            sh_phase = ab > 0.0 ? make_double2(val.x / ab, -val.y / ab) : make_double2(1.0, 0.0);
+            double* o = a.out + bin * a.G * a.G;
+            const double m = bad ? nan("") : fmin(rho, 1.0);
+            o[ga * a.G + gb] = m;
+            o[gb * a.G + ga] = m;
+            if (bad) atomicAdd(a.fail, 1);
+        }
+        __syncthreads();
+        const size_t oa = (((size_t)bin * a.G + ga) * a.G + gb) * v.vstride, ob = (((size_t)bin * a.G + gb) * a.G + ga) * v.vstride;
+        if (!bad) {                                          // (the outputs are NaN-filled before the launch)
+            for (int k = tid; k < na; k += 256) {
+                const double r = sqrt(fmin(fmax(red[1][k], 0.0), 1.0));
+                v.coherences[oa + k] = r; v.coherences[ob + k] = r;
+            }
+        }
+        if (defined) {
+            const cd ph = sh_phase;
+            for (int i = tid; i < na; i += 256) { v.filters[oa + i] = zmul(xa[i], ph); v.patterns[oa + i] = zmul(pv[i], ph); }
+            for (int j = tid; j < nb; j += 256) { v.filters[ob + j] = zmul(xb[j], ph); v.patterns[ob + j] = zmul(qv[j], ph); }
         }
         __syncthreads();
     }
@@ -1339,6 +1540,57 @@ extern "C" int sc_imaginary_interaction_vectors_f64(const void* d_accum, int64_t
         v.scratch = sbytes ? reinterpret_cast<cd*>(work + log_bytes) : nullptr;
         const hipError_t rcl = hipFuncSetAttribute((const void*)interaction_vectors_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (rcl == hipSuccess) hipLaunchKernelGGL(interaction_vectors_kernel, dim3((unsigned)slots), dim3(256), lds, st, a, v, items);
+        (void)hipFreeAsync(work, st);
+        SC_CHECK_HIP(rcl);
+    }
+    SC_CHECK_HIP(hipGetLastError());
+    return SC_OK;
+}
+
+extern "C" int sc_canonical_coherence_vectors_f64(const void* d_accum, int64_t n_bins, int64_t n_signals, uint32_t planes,
+                                                  int64_t n_observations, const int32_t* d_members, const int32_t* d_sizes,
+                                                  int n_groups, int max_group_size, double* d_coherence, double* d_coherences,
+                                                  double* d_filters, double* d_patterns, int32_t* d_fail, void* stream) {
+    ScTimed timed_("canonical_coherence_vectors", stream);
+    const char* what = "canonical coherence vectors";
+    SC_REQUIRE(d_accum && d_members && d_sizes && d_coherence && d_coherences && d_filters && d_patterns && d_fail, "NULL argument");
+    SC_REQUIRE(max_group_size >= 1, "empty groups");
+    CanonArgs a;
+    const int rca = canonical_args(what, d_accum, n_bins, n_signals, planes, n_observations, d_members, d_sizes, n_groups,
+                                   max_group_size, d_coherence, nullptr, d_fail, &a);
+    if (rca != SC_OK) return rca;
+    if (max_group_size <= CB_C) a.mstride = CB_C;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t total_out = n_bins * n_groups * n_groups;
+    sc_internal_fill_nan(d_coherence, total_out, st);
+    sc_internal_fill_nan(d_coherences, total_out * max_group_size, st);
+    sc_internal_fill_nan(d_filters, total_out * max_group_size * 2, st);
+    sc_internal_fill_nan(d_patterns, total_out * max_group_size * 2, st);
+    (void)hipMemsetAsync(d_fail, 0, 4, st);
+    const int64_t items = n_bins * a.n_gpairs;
+    if (items > 0) {
+        CvArgs v;
+        v.coherences = d_coherences;
+        v.filters = reinterpret_cast<cd*>(d_filters); v.patterns = reinterpret_cast<cd*>(d_patterns);
+        v.vstride = max_group_size; v.bn = max_group_size;
+        v.lds_n = iv_lds_n(max_group_size, sizeof(cd)); v.lds_ld = v.lds_n | 1;
+        const size_t lds = iv_lds_bytes(v.bn, v.lds_n, sizeof(cd));
+        int per_cu = (int)(IV_LDS_LIMIT / (lds + IV_STATIC_LDS));      // persistent workgroups a compute unit holds by LDS,
+        per_cu = per_cu < 1 ? 1 : (per_cu > 3 ? 3 : per_cu);           // and by registers (130 VGPRs: 3 waves a SIMD)
+        const int64_t want = (int64_t)256 * per_cu;
+        const int slots = (int)(items < want ? items : want);
+        const int Mb = v.bn + (v.bn & 1);
+        const size_t log_bytes = ((size_t)IV_SWEEPS * (Mb - 1) * (Mb / 2) * 3 * sizeof(double) * slots + 255) & ~(size_t)255;
+        const size_t sbytes = v.lds_n < max_group_size ? (size_t)slots * 3 * CBIG_C * CBIG_C * sizeof(cd) : 0;
+        char* work = nullptr;
+        if (hipMallocAsync((void**)&work, log_bytes + sbytes, st) != hipSuccess) {
+            sc_set_error("%s: workspace allocation of %zu bytes failed", what, log_bytes + sbytes);
+            return SC_ENOMEM;
+        }
+        v.log = reinterpret_cast<double*>(work);
+        v.scratch = sbytes ? reinterpret_cast<cd*>(work + log_bytes) : nullptr;
+        const hipError_t rcl = hipFuncSetAttribute((const void*)canonical_vectors_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (rcl == hipSuccess) hipLaunchKernelGGL(canonical_vectors_kernel, dim3((unsigned)slots), dim3(256), lds, st, a, v, items);
         (void)hipFreeAsync(work, st);
         SC_CHECK_HIP(rcl);
     }

@@ -527,6 +527,12 @@ def imaginary_interaction_vectors(accum, n_signals, planes, n_obs, members, size
     return _stage_d.imaginary_interaction_vectors(TorchMemory(accum.device), accum, n_signals, planes, n_obs, members, sizes)
 
 
+def canonical_coherence_vectors(accum, n_signals, planes, n_obs, members, sizes):
+    """members / sizes: _lib.member_table of the groups.  Returns (coherence [n_bins, G, G], coherences [n_bins, G, G, max group
+    size], filters, patterns [n_bins, G, G, max group size, 2] (re, im) float64, n_fail)."""
+    return _stage_d.canonical_coherence_vectors(TorchMemory(accum.device), accum, n_signals, planes, n_obs, members, sizes)
+
+
 def linear_dependence(accum, n_signals, planes, n_obs, members, sizes, want):
     """Total, instantaneous and lagged linear dependence between the groups (sc_dependence.hip): _stage_d.linear_dependence.
     Returns ({name: [n_bins, G, G] float64 tensor} for the names in ``want``, n_fail)."""

@@ -262,6 +262,33 @@ class Connectivity(_TorchHostConnectivity):
             self._canonical_failed(n_fail)
         return res.reshape(self._shape5[0], self._n_freq, n_g, n_g), labels
 
+    def canonical_coherence_vectors(self, group_labels):
+        group_labels = self._canonical_labels(group_labels)                     # (the labels are checked before any device work)
+        rec, n_obs, _ = self._csm_records("canonical", "trials_tapers", two_sided=False)
+        n_total = self._n_observations_total(n_obs)
+        labels, groups, small = self._canonical_groups(group_labels, n_total)
+        G, n_bins, n_max = len(groups), rec.shape[0], max(len(g) for g in groups)
+        coherence = np.ones((n_bins, G, G))
+        coherence[:, np.arange(G), np.arange(G)] = np.nan
+        coherences = np.broadcast_to(self._canonical_ones(groups), (n_bins, G, G, n_max)).copy()
+        filters, patterns = np.full((n_bins, G, G, n_max, 2), np.nan), np.full((n_bins, G, G, n_max, 2), np.nan)
+        if len(small) >= 2:
+            mem = self._memory()
+            sub_members, sub_sizes, _ = _lib.member_table([groups[k] for k in small])
+            c, cs, f, p, n_fail = _stage_d.canonical_coherence_vectors(mem, rec, self._shape5[4], _lib.PLANE_CSM, n_total, sub_members,
+                                                                       sub_sizes)
+            n_sub = int(sub_sizes.max())
+            cells = np.ix_(np.arange(n_bins), small, small)
+            coherence[cells] = mem.download(c)
+            coherences[cells] = np.nan
+            cells = np.ix_(np.arange(n_bins), small, small, np.arange(n_sub))
+            coherences[cells] = mem.download(cs)
+            filters[cells], patterns[cells] = mem.download(f), mem.download(p)
+            self._canonical_failed(n_fail)
+        return self._canonical_vectors_result((coherence, coherences, filters, patterns), labels, groups)
+
+    canonical_coherence_vectors.__doc__ = _TorchHostConnectivity.canonical_coherence_vectors.__doc__
+
     def _jackknife_sums(self, mask, over_id, n_units):
         if self._shape5[4] > 256:
             # (this host holds no complex spectra of more than 256 signals: _WideSeries, _decode_planes)

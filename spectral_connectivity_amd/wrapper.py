@@ -41,7 +41,7 @@ _NOT_IN_DATASET = {
     "generalized_partial_directed_coherence", "direct_directed_transfer_function",
     "blockwise_spectral_granger_prediction", "conditional_spectral_granger_prediction",
     "maximized_imaginary_coherence", "multivariate_interaction_measure", "maximized_imaginary_coherence_vectors", "jackknife",
-    "partial_coherency", "partial_coherence_magnitude", "multiple_coherence_magnitude", "linear_dependence", "lagged_coherence",
+    "canonical_coherence_vectors", "partial_coherency", "partial_coherence_magnitude", "multiple_coherence_magnitude", "linear_dependence", "lagged_coherence",
 }
 _PARTIAL = ("partial_coherency", "partial_coherence_magnitude", "multiple_coherence_magnitude")
 _MT_SKIP = {"time_series", "fft", "tapers", "frequencies", "time"}
@@ -60,7 +60,8 @@ def _xarray():
 
 def _check_method(method):
     if method in ("group_delay", "canonical_coherence", "blockwise_spectral_granger_prediction", "maximized_imaginary_coherence",
-                  "multivariate_interaction_measure", "maximized_imaginary_coherence_vectors", "jackknife", "linear_dependence") or "directed" in method:
+                  "multivariate_interaction_measure", "maximized_imaginary_coherence_vectors", "jackknife", "linear_dependence",
+                  "canonical_coherence_vectors") or "directed" in method:
         raise ValueError(
             f"The method '{method}' is not supported by the xarray interface. "
             f"Please use the Connectivity class directly instead:\n\n"
