@@ -275,15 +275,17 @@ __global__ void __launch_bounds__(NT) global_coherence_big_kernel(GcBigArgs b) {
             // unit phase: the largest component real and positive (one thread per vector finds it)
             cd* phase = reinterpret_cast<cd*>(red);     // [kb <= NT]: the reduction scratch is idle here
             for (int k = tid; k < kb; k += NT) {
-                double best = -1.0;
+                double best = -1.0, ss = 0.0;
                 cd bb = make_double2(1.0, 0.0);
                 for (int i = 0; i < C; ++i) {
                     const cd v = xv[k * C + i];
                     const double m2 = v.x * v.x + v.y * v.y;
+                    ss += m2;
                     if (m2 > best) { best = m2; bb = v; }
                 }
-                const double ab = sqrt(best);
-                phase[k] = ab > 0.0 ? make_double2(bb.x / ab, -bb.y / ab) : make_double2(1.0, 0.0);
+                // (unit norm restored: sweeps x (C - 1) rotations, each unitary to a rounding, had moved it by ~C 2^-52)
+                const double ab = sqrt(best), sc = ss > 0.0 ? 1.0 / sqrt(ss) : 1.0;
+                phase[k] = ab > 0.0 ? make_double2(bb.x / ab * sc, -bb.y / ab * sc) : make_double2(sc, 0.0);
             }
             __syncthreads();
             for (int e = tid; e < kb * C; e += NT) {
@@ -305,7 +307,7 @@ __global__ void __launch_bounds__(NT) global_coherence_big_kernel(GcBigArgs b) {
 // passes over the trailing block per step, C^3 x 16 bytes in all = 268 MB at 256 signals), find its eigenvalues by
 // bisection on the Sturm count (one thread per eigenvalue, to the last bit of ||T||), the requested eigenvectors of T by
 // inverse iteration (one thread per vector: pivoted tridiagonal LU, three solves; vectors of eigenvalues closer than
-// 1e-3 ||T|| are orthogonalised against each other, twice, like LAPACK's dstein), and back-transform them through the
+// 2^-6 ||T|| are orthogonalised against each other, twice, like LAPACK's dstein does at 1e-3), and back-transform them through the
 // stored reflectors (x = H_0 H_1 ... H_{C-2} y).  One 256-thread workgroup per (window, bin); the matrix (full storage,
 // column-major) and the per-vector work arrays live in a per-workgroup global scratch (L2-resident).
 struct GcEighArgs {
@@ -429,11 +431,14 @@ __global__ void __launch_bounds__(GE_NT) global_coherence_eigh_kernel(GcEighArgs
         double gl = 0.0, gu = 0.0, tn = 0.0;
         {
             double lo = 1e300, hi = -1e300, nr = 0.0, emax = 0.0;
+            bool alone = false;                            // row tid of T has no off-diagonal entry: d[tid] is an eigenvalue as it stands
+            if (tid == 0) sh_scalar[3] = 0.0;
             if (tid < C) {
                 const double el = tid > 0 ? fabs(e[tid - 1]) : 0.0, er = tid + 1 < C ? fabs(e[tid]) : 0.0;
                 lo = d[tid] - el - er; hi = d[tid] + el + er; nr = fabs(d[tid]) + el + er;
                 e2[tid] = e[tid] * e[tid];
                 emax = e2[tid];
+                alone = el == 0.0 && er == 0.0;
             }
             red[tid] = lo; __syncthreads();
             for (int s = GE_NT / 2; s > 0; s >>= 1) { if (tid < s) red[tid] = fmin(red[tid], red[tid + s]); __syncthreads(); }
@@ -448,9 +453,11 @@ __global__ void __launch_bounds__(GE_NT) global_coherence_eigh_kernel(GcEighArgs
             for (int s = GE_NT / 2; s > 0; s >>= 1) { if (tid < s) red[tid] = fmax(red[tid], red[tid + s]); __syncthreads(); }
             emax = red[0]; __syncthreads();
             sh_scalar[2] = 2.2250738585072014e-308 * fmax(1.0, emax);      // pivmin
+            if (alone) sh_scalar[3] = 1.0;                                  // (reset before the barriers of the reductions above)
         }
         __syncthreads();
         const double pivmin = sh_scalar[2];
+        const bool any_alone = sh_scalar[3] != 0.0;
         const double eps = 2.220446049250313e-16;
         {
             const double pad = 2.0 * tn * eps * C + 2.0 * pivmin;
@@ -472,7 +479,17 @@ __global__ void __launch_bounds__(GE_NT) global_coherence_eigh_kernel(GcEighArgs
                 }
                 if (cnt > tid) hi = mid; else lo = mid;    // cnt = eigenvalues below mid
             }
-            ev[tid] = 0.5 * (lo + hi);
+            double v = 0.5 * (lo + hi);
+            // An uncoupled diagonal entry inside the final interval IS the eigenvalue (a dead channel, a diagonal or block-diagonal
+            // matrix: reflections that were the identity).  Around 0 the relative stopping rule never fires, the midpoint after 120
+            // halvings is +-1e-35 ||T||, and the clamp below turned the positive ones into a non-zero power of a dead channel.
+            if (any_alone) {
+                for (int i = 0; i < C; ++i) {
+                    const bool al = (i == 0 || e2[i - 1] == 0.0) && e2[i] == 0.0;      // (e2[C - 1] = 0)
+                    if (al && d[i] >= lo && d[i] <= hi) { v = d[i]; break; }
+                }
+            }
+            ev[tid] = v;
         }
         __syncthreads();
         double* val = a.values + (p * a.v.N + n) * K;
@@ -542,10 +559,13 @@ __global__ void __launch_bounds__(GE_NT) global_coherence_eigh_kernel(GcEighArgs
             const double sc = ss > 0.0 ? 1.0 / sqrt(ss) : 1.0;
             for (int i = 0; i < C; ++i) WK(5, i, t) *= sc;
         };
-        // vectors of one cluster (eigenvalues closer than 1e-3 ||T||) are orthogonalised in ascending order, classical
-        // Gram-Schmidt applied twice: thread i computes <y_i, y_j>, then thread `row` updates element `row` of y_j
+        // vectors of one cluster (eigenvalues closer than 2^-6 ||T||) are orthogonalised in ascending order, classical
+        // Gram-Schmidt applied twice: thread i computes <y_i, y_j>, then thread `row` updates element `row` of y_j.
+        // (dstein's 1e-3 ||T|| until the record-level suite: inverse iteration leaves <y_i, y_j> ~ eps ||T|| / |l_i - l_j|, so two
+        // vectors just outside a cluster were orthogonal to 425 x 2^-52 only, where LAPACK's zheevd stays below 18; at 2^-6 the
+        // worst pair left alone is 16 times further apart)
         auto orthogonalise = [&]() {
-            const double ortol = 1e-3 * tn;
+            const double ortol = 0.015625 * tn;
             int c0 = 0;                                    // first vector of the current cluster (uniform: read from LDS)
             for (int j = 1; j < K; ++j) {
                 if (shift[j] - shift[j - 1] >= ortol) { c0 = j; continue; }

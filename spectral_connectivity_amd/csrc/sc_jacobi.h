@@ -39,16 +39,25 @@ __device__ inline void gc_jacobi(cd* A, int C, double* rc, cd* rs, int* rp, cons
     if (tid == 0) *n_rounds = 0;
     __syncthreads();
     for (int sweep = 0; sweep < max_sweeps; ++sweep) {
-        double off = 0.0, dia = 0.0;              // off = the whole packed triangle, dia = its diagonal
-        for (int i = tid; i < C; i += NT) { const cd v = A[gc_tri(i, i, C)]; dia += v.x * v.x; }
-        for (int e = tid; e < C * (C + 1) / 2; e += NT) off += A[e].x * A[e].x + A[e].y * A[e].y;
+        // off = the entries above the diagonal, dia = the diagonal, summed apart.  (Until the record-level suite of global coherence
+        // off was the whole triangle minus dia: a difference of two sums that agree to 16 digits long before off <= 1e-28 dia, so
+        // its rounding ended the sweeps at off ~ 1e-16 dia and the vectors were eigenvectors to 1e-8 ||A|| only.)
+        double off = 0.0, dia = 0.0;
+        {
+            int row = 0, first = 0;               // the row of entry e and the index of that row's diagonal entry
+            for (int e = tid; e < C * (C + 1) / 2; e += NT) {
+                while (e >= first + (C - row)) { first += C - row; ++row; }
+                const double m2 = A[e].x * A[e].x + A[e].y * A[e].y;
+                if (e == first) dia += A[e].x * A[e].x; else off += m2;
+            }
+        }
         red[0][tid] = off; red[1][tid] = dia;
         __syncthreads();
         for (int s = NT / 2; s > 0; s >>= 1) {
             if (tid < s) { red[0][tid] += red[0][tid + s]; red[1][tid] += red[1][tid + s]; }
             __syncthreads();
         }
-        if (tid == 0) { const double o = red[0][0] - red[1][0]; *done = (o <= 1e-28 * red[1][0] || o <= 0.0) ? 1 : 0; }
+        if (tid == 0) *done = (red[0][0] <= 1e-28 * red[1][0]) ? 1 : 0;
         __syncthreads();
         if (*done) break;
         for (int r = 0; r < M - 1; ++r) {
@@ -104,11 +113,16 @@ __device__ inline void gc_jacobi(cd* A, int C, double* rc, cd* rs, int* rp, cons
                 const cd n10 = make_double2(zmul(suc, t00).x + cu * t10.x, zmul(suc, t00).y + cu * t10.y);
                 const cd n11 = make_double2(zmul(suc, t01).x + cu * t11.x, zmul(suc, t01).y + cu * t11.y);
                 if (u == v) {
-                    // diagonal block: Hermitian, off-diagonal annihilated by construction
-                    gc_set(A, up, up, C, make_double2(n00.x, 0.0));
+                    // diagonal block: Hermitian, off-diagonal annihilated by construction; the diagonal moves by -+ t |a_pq| with
+                    // t = tan = Re(s conj a_pq) / (c |a_pq|) (Rutishauser's form: the increment vanishes with the off-diagonal entry,
+                    // where c (c a_pp - ...) - ... rounds at the size of the eigenvalue in every one of sweeps x (C - 1) rounds)
                     if (uhas) {
-                        gc_set(A, uq, uq, C, make_double2(n11.x, 0.0));
+                        const double dlt = (su.x * b01.x + su.y * b01.y) / cu;
+                        gc_set(A, up, up, C, make_double2(b00.x - dlt, 0.0));
+                        gc_set(A, uq, uq, C, make_double2(b11.x + dlt, 0.0));
                         gc_set(A, up, uq, C, make_double2(0.0, 0.0));
+                    } else {
+                        gc_set(A, up, up, C, make_double2(n00.x, 0.0));
                     }
                 } else {
                     gc_set(A, up, vp, C, n00);

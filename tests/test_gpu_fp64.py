@@ -321,8 +321,9 @@ def test_cfg4_full_size_granger_elementwise(sc):
 
 @pytest.mark.parametrize("C", [65, 128, 129, 256])
 def test_global_coherence_large_float64(sc, C):
-    """Global coherence of 65 ... 256 signals from double records (packed Jacobi in LDS up to 128 signals, in a global
-    scratch beyond): squared singular values of the oracle to 1e-11, dominant vector as a line."""
+    """Global coherence of 65 ... 256 signals from double records (the Householder kernel global_coherence_eigh_kernel<256>; the
+    packed Jacobi kernels are diagnostics, SC_GLOBAL_EIG=jacobi): squared singular values of the oracle to 1e-11, dominant vector
+    as a line."""
     from oracle import spectral_oracle as so
     x = np.random.default_rng(C).standard_normal((64, 110, C))
     x[:, :, : C // 2] += np.random.default_rng(1).standard_normal((64, 110, 1))

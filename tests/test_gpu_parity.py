@@ -738,8 +738,9 @@ def test_f10_global_coherence_vs_reference(sc, golden, rank):
 
 
 def test_global_coherence_large_even_and_odd(sc):
-    """33, 64 (matrix + eigenvectors in LDS) and 65, 97, 128 signals (packed matrix in LDS, eigenvectors from the
-    logged rotations) against the oracle SVD: values, and vectors as lines for the dominant component."""
+    """33, 64, 65, 97 and 128 signals -- since round 6 all of them the Householder kernel (global_coherence_eigh_kernel<256>,
+    from 33 signals on; the Jacobi kernels that ran here before stay reachable with SC_GLOBAL_EIG=jacobi and have their own cases in
+    tests/test_gpu_global_coherence.py) -- against the oracle SVD: values, and vectors as lines for the dominant component."""
     for C in (33, 64, 65, 97, 128):
         x = np.random.default_rng(C).standard_normal((128, 40, C))
         x[:, :, : C // 2] += np.random.default_rng(1).standard_normal((128, 40, 1))
@@ -756,9 +757,9 @@ def test_global_coherence_large_even_and_odd(sc):
 
 @pytest.mark.parametrize("C", [129, 200, 255, 256])
 def test_global_coherence_beyond_128_signals(sc, C):
-    """129 ... 256 signals: the packed matrix no longer fits LDS and lives in a global scratch (the same Jacobi kernel on
-    an L2-resident triangle); values and the dominant vector against the oracle's SVD (float64 engine:
-    tests/test_gpu_fp64.py)."""
+    """129 ... 256 signals: the Householder kernel (global_coherence_eigh_kernel<256>) with the matrix and the work arrays in a
+    per-workgroup global scratch (the Jacobi kernel on an L2-resident triangle that ran here before is a diagnostic now:
+    SC_GLOBAL_EIG=jacobi); values and the dominant vector against the oracle's SVD (float64 engine: tests/test_gpu_fp64.py)."""
     x = np.random.default_rng(C).standard_normal((64, 110, C))
     x[:, :, : C // 2] += np.random.default_rng(1).standard_normal((64, 110, 1))
     kw = dict(sampling_frequency=128.0, time_halfbandwidth_product=2, n_time_samples_per_window=32)
