@@ -560,11 +560,12 @@ int sc_global_coherence_f64(const void* d_accum, int64_t n_groups, int64_t n_fre
  *               max_group_size <= 16, 32 if <= 32, else 128 (max supported: sc_canonical_max_group() = 128)
  *   d_sizes     int32 [n_groups]
  *   d_out       double [n_bins][n_groups][n_groups], symmetric, NaN diagonal
- *   d_fail      int32 [1]: number of group blocks that were not positive definite
+ *   d_fail      int32 [1]: number of (bin, group pair) items with a group block that was not positive definite (their
+ *               entries of d_out are NaN; a bad group counts once for every pair it is in)
  * Groups of <= 16 channels take a stream-ordered workspace of n_bins * n_groups * 4 KB for the
  * inverted group factors, groups beyond 64 channels one of 768 KB per persistent workgroup (<= 256) for the blocks of
  * the pair in flight (hipMallocAsync / hipFreeAsync on `stream`); SC_ENOMEM if that fails.  17 ... 64 channels: a
- * workgroup per (bin, group pair) with the whole problem in LDS (round 6), no workspace. */
+ * persistent workgroup per (bin, group pair) item with the whole problem in LDS (round 6), no workspace. */
 int sc_canonical_max_group(void);
 int sc_canonical_coherence_f64(const void* d_accum, int64_t n_bins, int64_t n_signals, uint32_t planes,
                                int64_t n_observations, const int32_t* d_members, const int32_t* d_sizes,

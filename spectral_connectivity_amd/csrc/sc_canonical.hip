@@ -8,9 +8,13 @@
 //     sigma_max( L_g^-1 S_gh L_h^-H )^2,     S_gg = L_g L_g^H (Cholesky),
 // (identical when every group has full row rank, n_obs >= c_g), i.e.
 // per (bin, group pair) two small Cholesky factorisations, two triangular solves and the top
-// eigenvalue of a c_g x c_g Hermitian matrix (cyclic complex Jacobi, eigenvalues only).
-// One thread per (bin, group pair), fp64, matrices in per-lane scratch: the work is
-// O(bins * pairs * c^3) and tiny next to stage B.
+// eigenvalue of a c_g x c_g Hermitian matrix, all fp64.  Three tiers by the largest group of a launch
+// (canonical_launch): up to 16 channels a wave per (bin, pair) on factors computed once per bin
+// (canonical_factor_kernel + canonical_pair_hh_kernel), up to 64 a persistent workgroup per item with the
+// whole problem in LDS, up to 128 the same with the blocks in a global scratch (canonical_big_hh_kernel);
+// lambda_max by Householder tridiagonalisation and multisection on the Sturm sequence.  The Jacobi
+// kernels of the first rounds (canonical_kernel: one THREAD per item, matrices in per-lane scratch;
+// canonical_pair_kernel; canonical_big_kernel) remain behind SC_CANON_EIG=jacobi for cross-checks.
 //
 // The same kernels give the multivariate imaginary coherence of Ewald, Marzetti, Zappasodi, Meinecke & Nolte 2012
 // (NeuroImage 62:1964-1971) through a second READ VIEW of the records (template parameter IM): group blocks Re S_gg, cross
@@ -27,7 +31,7 @@ struct CanonArgs {
     const int32_t* members;   // [G][CMAX] channel indices, -1 padded
     const int32_t* sizes;     // [G]
     double* out;              // [n_bins][G][G]
-    int32_t* fail;            // [1] count of non positive-definite group blocks
+    int32_t* fail;            // [1] count of (bin, pair) items with a group block that is not positive definite
     ScCsmView v;              // the records (single bins: N = F = n_bins)
     int64_t n_bins;
     int G, n_gpairs;
@@ -52,9 +56,15 @@ __device__ inline cd csm_cross(ScRec rec, const CanonArgs& a, int i, int j) {
 }
 
 // interaction view: MIC = sqrt(lambda_max) and MIM = trace(B) of a pair; B is positive semi-definite, so lambda_max <= trace(B)
-// (the clamp keeps MIC^2 <= MIM to the last bit and makes MIC exactly 0 where B is 0).  NaN for both when a block failed.
+// (the clamp and the step below keep the rounded MIC x MIC <= MIM to the last bit and make MIC exactly 0 where B is 0).  NaN for
+// both when a block failed.
 __device__ inline void canon_store_interaction(const CanonArgs& a, int64_t bin, int ga, int gb, double lmax, double tr, bool ok) {
-    const double mic = ok ? sqrt(fmin(fmax(lmax, 0.0), tr)) : nan(""), mim = ok ? tr : nan("");
+    double mic = ok ? sqrt(fmin(fmax(lmax, 0.0), tr)) : nan("");
+    const double mim = ok ? tr : nan("");
+    // (the rounded square of a rounded root can lie one unit above its argument: with lambda_max = trace(B), a group of one
+    //  channel, MIC x MIC came out above MIM in the last bit; one step down is enough with a correctly rounded root, the
+    //  square moves by two units of the root's)
+    for (int k = 0; k < 2 && ok && __dmul_rn(mic, mic) > tr; ++k) mic = nextafter(mic, 0.0);
     double* o = a.out + bin * a.G * a.G;
     double* p = a.out_mim + bin * a.G * a.G;
     o[ga * a.G + gb] = mic;
@@ -378,8 +388,10 @@ __global__ void __launch_bounds__(64 * CB_WAVES) canonical_pair_kernel(CanonArgs
                     double c = 1.0;
                     cd se = make_double2(0.0, 0.0);
                     // Rotation angle in f32 with the hardware's 1-ulp rcp / rsq (no IEEE division sequences, no fp64
-                    // Newton steps on 8 lanes), then (c, s) re-normalised in fp64 to first order: the rotation is
-                    // unitary to 1e-14, it merely leaves ~1e-7 of the pivot behind, which the next sweep removes.
+                    // Newton steps on 8 lanes), then (c, s) re-normalised in fp64 to second order: the rotation is
+                    // unitary to 1e-21, it merely leaves ~1e-7 of the pivot behind, which the diagonal block below
+                    // KEEPS and the next sweep removes.  (First order left every rotation 1e-14 off unitary: 2.6e-13
+                    // of lambda_max after the ~100 rounds of a 16 x 16 problem.)
                     const cd bb = B[pi * CB_C + qi];
                     const float bx = (float)bb.x, by = (float)bb.y;
                     const float ab2 = bx * bx + by * by;
@@ -391,7 +403,8 @@ __global__ void __launch_bounds__(64 * CB_WAVES) canonical_pair_kernel(CanonArgs
                         const float cf = __builtin_amdgcn_rsqf(1.f + t * t);
                         const float sn = t * cf * rab;
                         const double cd0 = (double)cf, sx = (double)(sn * bx), sy = (double)(sn * by);
-                        const double fix = 1.5 - 0.5 * (cd0 * cd0 + sx * sx + sy * sy);     // 1 / sqrt(r), r = 1 + O(1e-7)
+                        const double dl = (cd0 * cd0 + sx * sx + sy * sy) - 1.0;            // r = 1 + dl, dl = O(1e-7)
+                        const double fix = 1.0 - 0.5 * dl + 0.375 * dl * dl;                // 1 / sqrt(r) + O(dl^3)
                         c = cd0 * fix;
                         se = make_double2(sx * fix, sy * fix);
                     }
@@ -423,8 +436,10 @@ __global__ void __launch_bounds__(64 * CB_WAVES) canonical_pair_kernel(CanonArgs
                     if (bu == bv) {
                         B[up * CB_C + up] = make_double2(n00.x, 0.0);
                         B[uq * CB_C + uq] = make_double2(n11.x, 0.0);
-                        B[up * CB_C + uq] = make_double2(0.0, 0.0);
-                        B[uq * CB_C + up] = make_double2(0.0, 0.0);
+                        // (not 0: the angle is good to f32, and dropping the 1e-7 |pivot| it leaves is no similarity -- it moved
+                        //  lambda_max by up to 1e-8 as long as the eigenvectors were dense, tests/test_gpu_canonical_values.py (h))
+                        B[up * CB_C + uq] = n01;
+                        B[uq * CB_C + up] = make_double2(n01.x, -n01.y);
                     } else {
                         B[up * CB_C + vp] = n00;
                         B[up * CB_C + vq] = n01;
@@ -538,12 +553,18 @@ __device__ double cb_top_eigenvalue(cd (&a)[4], cd* vb, int lane) {
     double lo = dmax * sc1, hi = 1.0;
     for (int round = 0; round < 9 && hi > lo; ++round) {
         const double x = lane == 63 ? hi : lo + (hi - lo) * ((double)(lane + 1) * (1.0 / 64.0));
+        // x > lambda_max iff the leading principal minors p_q of T - x alternate in sign, p_q (-1)^q > 0.  The signs are compared, not
+        // multiplied: with sixteen eigenvalues within 1e-11 of x the minors are ~1e-176 and the product of two consecutive ones is
+        // below the smallest double -- `p2 * p1 < 0` then held for no lane and the loop left with the Gershgorin bracket still open
+        // (rho_1^2 off by 1e4 x 2^-52, tests/test_gpu_canonical_values.py (d)).  A pair of minors that are both small is scaled up
+        // (the recurrence is linear in (p0, p1): the signs stay), so the minors themselves cannot underflow either.
         double p0 = 1.0, p1 = d[0] - x;
         bool above = p1 < 0.0;
 #pragma unroll
         for (int q = 1; q < 16; ++q) {
-            const double p2 = (d[q] - x) * p1 - e2[q - 1] * p0;
-            above = above && (p2 * p1 < 0.0);
+            double p2 = (d[q] - x) * p1 - e2[q - 1] * p0;
+            above = above && ((q & 1) ? p2 > 0.0 : p2 < 0.0);
+            if (fabs(p1) + fabs(p2) < 0x1p-400) { p1 *= 0x1p400; p2 *= 0x1p400; }
             p0 = p1; p1 = p2;
         }
         const unsigned long long mask = __builtin_amdgcn_ballot_w64(above);
@@ -957,7 +978,7 @@ __global__ void __launch_bounds__(256) canonical_big_hh_kernel(CanonArgs a, cd* 
             }
         }
         if (tid == 0) {
-            double v = 0.5 * (lo + hi);
+            double v = fmax(0.5 * (lo + hi), 0.0);            // (B = 0: the last bracket is +- pivmin around 0, B >= 0: never below)
             if constexpr (IM) {
                 double tr = 0.0;                             // trace(B) = trace(T): the reflections are unitary similarities
                 for (int i = 0; i < na; ++i) tr += dg[i];
