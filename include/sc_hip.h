@@ -4,7 +4,8 @@
  * This is the drop-in boundary for ONE path of the reference: time series ->
  * DPSS-tapered sliding-window FFT -> cross-spectral matrix -> expectation ->
  * coherence / PLI / wPLI / PLV / PPC (-> pairwise spectral Granger, canonical coherence;
- * delete-one jackknife standard errors of power, coherence and the phase-lag family).
+ * delete-one jackknife standard errors of power, coherence and the phase-lag family;
+ * the expectation-type measures of a few seed signals against a list of signals).
  * It replaces the reference's array-backend plug point, the import-time switch
  * `xp = cupy | numpy` plus `fft/ifft/...` (transforms.py:405-439, connectivity.py:31-65,
  * minimum_phase_decomposition.py:14-26), for the call sites listed per function below.
@@ -813,6 +814,46 @@ int sc_jackknife_phase_totals_f32(const void* d_X /*float2*/, const sc_spectra_d
 int sc_jackknife_phase_totals_f64(const void* d_X /*double2*/, const sc_spectra_desc* desc, uint32_t planes, int over,
                                   int64_t unit_begin, int64_t unit_end, double* d_record, void* d_workspace,
                                   int64_t workspace_bytes, void* stream);
+
+/* ---- seed-based connectivity: a few signals against a list of signals (sc_seed.hip; additive, ABI v8) ---------------------
+ * What MNE-Connectivity's indices=(seeds, targets) and FieldTrip's channelcmb ask for (the reference has no such call): each of
+ * n_seeds signals against each of n_targets signals, for the ten expectation-type measures, in ONE pass over the complex64 /
+ * complex128 spectra whatever the measures -- S * C products per observation instead of the C^2 / 2 of the all-pairs records, a
+ * record of S * C entries per plane and bin instead of C^2 / 2, no limit of the all-pairs kernels on n_signals.
+ *   d_seeds, d_targets  int32 device arrays of signal indices; d_targets == NULL: target t is signal t (n_targets == n_signals).
+ *                       The cross-spectrum is s = x_seed conj(x_target).  An index outside [0, n_signals) reads as a signal
+ *                       of zeros (no load is issued for it); the hosts refuse such a list before they call.
+ *   planes              which sums the record holds: any non-empty set of SC_PLANE_CSM, _ABS_IM, _IM_SQ, _SIGN_IM, _UNIT (as in
+ *                       the accumulator records; _UNIT is the product of the unit phasors x / |x| of the two factors), and
+ *                       SC_SEED_PLANE_POWER for sum |x_seed|^2, sum |x_target|^2 (what the coherency family divides by).
+ *   d_record            double [n_bins][planes in accumulator order][n_seeds][n_targets], then with SC_SEED_PLANE_POWER
+ *                       double [n_seeds], double [n_targets] per bin: sc_seed_record_layout doubles per bin, n_bins = kept
+ *                       groups x desc->n_freq as in sc_accum_layout.  Un-normalised sums, fp64 on both engines (products in the
+ *                       spectra's precision): the records of trial shards add.  Written whole.
+ *   d_workspace         sc_seed_accumulate_workspace_bytes, 16-byte aligned (0 where bins x target tiles x seed chunks fill the
+ *                       device; otherwise the observations are split over several workgroups whose partial records are added
+ *                       in split order: no floating-point atomics, bit-identical from run to run)
+ * sc_seed_measure_f64: record -> measures, SC_M_COHERENCY (complex), _COHERENCE_MAGNITUDE, _COHERENCE_PHASE,
+ * _IMAGINARY_COHERENCE (these four need SC_PLANE_CSM | SC_SEED_PLANE_POWER), SC_M_PLV, _PPC (SC_PLANE_UNIT), SC_M_PLI,
+ * _DEBIASED_PLI2 (_SIGN_IM), SC_M_WPLI (_CSM | _ABS_IM), SC_M_DEBIASED_WPLI2 (_CSM | _ABS_IM | _IM_SQ): d_outs[m] is
+ * [n_bins][n_seeds][n_targets] of double / double2 (wide[m] != 0) or float / float2, with the algebra of sc_measure_* entry for
+ * entry, n_observations the count of the whole job; where seed s IS target t the value is what that measure has on its diagonal.
+ * SC_EINVAL before any launch for a NULL pointer, n_seeds outside 1 ... sc_seed_connectivity_max_seeds(), n_targets outside
+ * 1 ... 32768, planes outside the set above (or SC_SEED_PLANE_POWER alone), a measure that is not one of the ten or whose planes
+ * the record lacks, and a workspace smaller than the query's answer. */
+#define SC_SEED_PLANE_POWER 0x20u
+int sc_seed_connectivity_max_seeds(void);
+int sc_seed_record_layout(int64_t n_seeds, int64_t n_targets, uint32_t planes, int64_t* doubles_per_bin);
+int64_t sc_seed_accumulate_workspace_bytes(const sc_spectra_desc* desc, int64_t n_seeds, int64_t n_targets, uint32_t planes);
+int sc_seed_accumulate_f32(const void* d_X /*float2*/, const sc_spectra_desc* desc, const int32_t* d_seeds, int64_t n_seeds,
+                           const int32_t* d_targets, int64_t n_targets, uint32_t planes, double* d_record, void* d_workspace,
+                           int64_t workspace_bytes, void* stream);
+int sc_seed_accumulate_f64(const void* d_X /*double2*/, const sc_spectra_desc* desc, const int32_t* d_seeds, int64_t n_seeds,
+                           const int32_t* d_targets, int64_t n_targets, uint32_t planes, double* d_record, void* d_workspace,
+                           int64_t workspace_bytes, void* stream);
+int sc_seed_measure_f64(const double* d_record, int64_t n_bins, const int32_t* d_seeds, int64_t n_seeds, const int32_t* d_targets,
+                        int64_t n_targets, uint32_t planes, int64_t n_observations, int n_measures, const int* measures,
+                        const int* wide, void* const* d_outs, void* stream);
 
 /* ---- host-pointer side of the boundary: memory, copies, streams (sc_memory.hip, ABI v3) ---------------------
  * What the reference's CuPy backend does with `xp.asarray(time_series)` on the way in and `.get()` on the way out

@@ -203,6 +203,15 @@ SYMBOLS = {
                                               c_int64, c_void_p]),
     "sc_jackknife_phase_totals_f64": (c_int, [c_void_p, POINTER(SpectraDesc), c_uint32, c_int, c_int64, c_int64, c_void_p, c_void_p,
                                               c_int64, c_void_p]),
+    "sc_seed_connectivity_max_seeds": (c_int, []),
+    "sc_seed_record_layout": (c_int, [c_int64, c_int64, c_uint32, c_int64_p]),
+    "sc_seed_accumulate_workspace_bytes": (c_int64, [POINTER(SpectraDesc), c_int64, c_int64, c_uint32]),
+    "sc_seed_accumulate_f32": (c_int, [c_void_p, POINTER(SpectraDesc), c_void_p, c_int64, c_void_p, c_int64, c_uint32, c_void_p,
+                                       c_void_p, c_int64, c_void_p]),
+    "sc_seed_accumulate_f64": (c_int, [c_void_p, POINTER(SpectraDesc), c_void_p, c_int64, c_void_p, c_int64, c_uint32, c_void_p,
+                                       c_void_p, c_int64, c_void_p]),
+    "sc_seed_measure_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_uint32, c_int64, c_int,
+                                    POINTER(c_int), POINTER(c_int), POINTER(c_void_p), c_void_p]),
     "sc_measure_f32": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_int, c_void_p, c_void_p]),
     # host-pointer side (sc_memory.hip)
     "sc_device_alloc": (c_int, [POINTER(c_void_p), c_size_t, c_void_p]),
@@ -562,6 +571,70 @@ def jackknife_blocks(names, n_bins, n_signals):
         out.append((k, at, size, shape))
         at += 3 * size
     return out, at
+
+
+# ---- seed-based connectivity (sc_seed.hip): the request, checked before any device work (both hosts) -------------------------------
+SEED_PLANE_POWER = 0x20          # SC_SEED_PLANE_POWER: sum |x_seed|^2, sum |x_target|^2 of a seed record
+# measure name -> (SC_M_* code of sc_seed_measure_f64, planes of the seed record it reads)
+SEED_MEASURES = {
+    "coherency": (M_COHERENCY, PLANE_CSM | SEED_PLANE_POWER),
+    "coherence_magnitude": (M_COHERENCE_MAGNITUDE, PLANE_CSM | SEED_PLANE_POWER),
+    "coherence_phase": (M_COHERENCE_PHASE, PLANE_CSM | SEED_PLANE_POWER),
+    "imaginary_coherence": (M_IMAGINARY_COHERENCE, PLANE_CSM | SEED_PLANE_POWER),
+    "phase_locking_value": (M_PLV, PLANE_UNIT),
+    "pairwise_phase_consistency": (M_PPC, PLANE_UNIT),
+    "phase_lag_index": (M_PLI, PLANE_SIGN_IM),
+    "weighted_phase_lag_index": (M_WPLI, PLANE_CSM | PLANE_ABS_IM),
+    "debiased_squared_phase_lag_index": (M_DEBIASED_PLI2, PLANE_SIGN_IM),
+    "debiased_squared_weighted_phase_lag_index": (M_DEBIASED_WPLI2, PLANE_CSM | PLANE_ABS_IM | PLANE_IM_SQ),
+}
+
+
+def seed_record_doubles(n_seeds, n_targets, planes):
+    """Doubles per bin of a seed record (sc_seed_record_layout restated): two planes for the cross-spectrum and for the unit
+    phasors, one for each other family, [n_seeds][n_targets] each, then the two power vectors."""
+    n_planes = sum(width for bit, width in ((PLANE_CSM, 2), (PLANE_ABS_IM, 1), (PLANE_IM_SQ, 1), (PLANE_SIGN_IM, 1), (PLANE_UNIT, 2))
+                   if planes & bit)
+    return n_planes * n_seeds * n_targets + ((n_seeds + n_targets) if planes & SEED_PLANE_POWER else 0)
+
+
+def _seed_indices(values, what, n_signals):
+    import numpy as np
+    arr = np.asarray(values)
+    if arr.ndim != 1 or arr.size == 0:
+        raise ValueError(f"seed_connectivity: {what} must be a non-empty list of signal indices")
+    if arr.dtype == bool or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError(f"seed_connectivity: {what} must be integers (got {arr.dtype})")
+    bad = (arr < 0) | (arr >= n_signals)
+    if bad.any():
+        raise ValueError(f"seed_connectivity: {what} index {int(arr[bad][0])} is outside [0, {n_signals})")
+    if len(np.unique(arr)) != arr.size:
+        raise ValueError(f"seed_connectivity: {what} holds an index twice")
+    return arr.astype(np.int32)
+
+
+def seed_request(seeds, targets, measures, n_signals, max_seeds):
+    """(seeds int32, targets int32 or None for all signals in order, names in the order asked, SC_M_* codes, planes of the record)
+    of Connectivity.seed_connectivity; ValueError -- with the valid choices spelled out -- for an unknown, empty or repeated
+    measure, an empty list, an index that is out of range, not an integer or repeated, and more than ``max_seeds`` seeds."""
+    measures = [measures] if isinstance(measures, str) else list(measures)
+    valid = ", ".join(SEED_MEASURES)
+    if not measures:
+        raise ValueError(f"seed_connectivity: measures is empty; choose from {valid}")
+    unknown = [m for m in measures if m not in SEED_MEASURES]
+    if unknown:
+        raise ValueError(f"seed_connectivity: unknown measure {unknown[0]!r}; choose from {valid}")
+    if len(set(measures)) != len(measures):
+        raise ValueError(f"seed_connectivity: a measure is asked for twice ({measures})")
+    seeds = _seed_indices(seeds, "seeds", n_signals)
+    if len(seeds) > max_seeds:
+        raise ValueError(f"seed_connectivity: at most {max_seeds} seeds per call (got {len(seeds)})")
+    if targets is not None:
+        targets = _seed_indices(targets, "targets", n_signals)
+    planes = 0
+    for m in measures:
+        planes |= SEED_MEASURES[m][1]
+    return seeds, targets, measures, [SEED_MEASURES[m][0] for m in measures], planes
 
 
 def library_path():

@@ -376,3 +376,39 @@ def jackknife_phase_totals(mem, spectra, expectation_type, planes, over, n_freq=
     _lib.check(fn(mem.ptr(spectra.X), byref(d), planes, over, lo, hi, mem.ptr(record), _ptr(mem, ws), ws_bytes, mem.stream()),
                "sc_jackknife_phase_totals")
     return record, n_obs
+
+
+def seed_connectivity(mem, spectra, expectation_type, seeds, targets, planes, measures, wide, n_freq=None, reduce=None,
+                      n_observations=None):
+    """Seed-based connectivity (sc_seed.hip): ONE pass over the complex64 / complex128 spectra (``spectra.X``, described by
+    ``spectra.desc``) sums the seed record of ``planes`` (_lib.SEED_MEASURES) for the signals ``seeds`` against ``targets`` (int32
+    arrays; None: every signal in order), then one small launch turns it into the ``measures`` (SC_M_* codes), each as doubles
+    where its ``wide`` flag is set and floats otherwise.  The record is un-normalised, so trial shards add it: ``reduce`` (record
+    -> record summed over the processes) and ``n_observations`` (local count -> the job's) are the caller's.  Returns the list of
+    device arrays [n_bins, n_seeds, n_targets], in the order of ``measures``."""
+    from . import _stage_abc
+    lib = _lib._handle()
+    d = spectra.desc(expectation_type, n_freq)
+    n_seeds, n_targets = len(seeds), spectra.C if targets is None else len(targets)
+    per_bin = c_int64()
+    _lib.check(lib.sc_seed_record_layout(n_seeds, n_targets, planes, byref(per_bin)), "sc_seed_record_layout")
+    n_bins, _, _, n_obs = _stage_abc.accum_layout(spectra, expectation_type, _lib.PLANE_CSM, n_freq)      # (the planes do not matter)
+    d_seeds = mem.upload(np.ascontiguousarray(seeds, dtype=np.int32))
+    d_targets = None if targets is None else mem.upload(np.ascontiguousarray(targets, dtype=np.int32))
+    ws_bytes = int(lib.sc_seed_accumulate_workspace_bytes(byref(d), n_seeds, n_targets, planes))
+    ws = mem.empty((ws_bytes,), np.uint8) if ws_bytes else None
+    record = mem.empty((n_bins, per_bin.value), np.float64)
+    fn = lib.sc_seed_accumulate_f64 if spectra.f64 else lib.sc_seed_accumulate_f32
+    _lib.check(fn(mem.ptr(spectra.X), byref(d), mem.ptr(d_seeds), n_seeds, _ptr(mem, d_targets), n_targets, planes, mem.ptr(record),
+                  _ptr(mem, ws), ws_bytes, mem.stream()), "sc_seed_accumulate")
+    if reduce is not None:
+        record = reduce(record)
+    n_total = n_obs if n_observations is None else n_observations(n_obs)
+    outs = [mem.empty((n_bins, n_seeds, n_targets), (np.complex128 if w else np.complex64) if m == _lib.M_COHERENCY else
+                      (np.float64 if w else np.float32)) for m, w in zip(measures, wide)]
+    n = len(measures)
+    _lib.check(lib.sc_seed_measure_f64(mem.ptr(record), n_bins, mem.ptr(d_seeds), n_seeds, _ptr(mem, d_targets), n_targets, planes,
+                                       n_total, n, (ctypes.c_int * n)(*measures), (ctypes.c_int * n)(*(int(bool(w)) for w in wide)),
+                                       (ctypes.c_void_p * n)(*(mem.ptr(o).value for o in outs)), mem.stream()), "sc_seed_measure_f64")
+    return outs
+

@@ -37,6 +37,7 @@ EXPECTATION = dict.fromkeys(EXPECTATION_AXES)
 InteractionVectors = namedtuple("InteractionVectors", ("mic", "filters", "patterns", "labels", "members"))
 CanonicalVectors = namedtuple("CanonicalVectors", ("coherence", "coherences", "filters", "patterns", "labels", "members"))
 LinearDependence = namedtuple("LinearDependence", ("total", "instantaneous", "lagged", "labels"))
+SeedConnectivity = namedtuple("SeedConnectivity", ("values", "seeds", "targets"))
 
 
 class _PendingSpectra:
@@ -1179,6 +1180,46 @@ class Connectivity:
         """Sum of the partial sums over the processes that hold the trials (nothing to add here).  ``table``: the measures the
         mask ``mask`` is of (default _lib.JACKKNIFE_MEASURES)."""
         return out
+
+    # ---- seed-based connectivity: a few signals against a list of signals (sc_seed.hip) --------------------------------------
+    def seed_connectivity(self, seeds, targets=None, measures=("coherence_magnitude",)):
+        """The expectation-type measures of a few reference signals (an EMG or ECG lead, a stimulus sensor, a seed LFP) against a
+        list of signals -- MNE-Connectivity's ``indices=(seeds, targets)``, FieldTrip's ``channelcmb`` -- without the all-pairs
+        matrix: n_seeds x n_targets products per observation instead of n_signals^2 / 2, and ONE pass over the spectra whatever the
+        measures (the all-pairs methods take one per accumulator family).
+
+        ``seeds``: distinct signal indices in [0, n_signals), at most ``sc_seed_connectivity_max_seeds()`` (64).  ``targets``:
+        distinct signal indices in any order, or None for every signal in order; seeds may be among them.  ``measures``: any
+        non-empty subset, without repeats, of "coherency", "coherence_magnitude", "coherence_phase", "imaginary_coherence",
+        "phase_locking_value", "pairwise_phase_consistency", "phase_lag_index", "weighted_phase_lag_index",
+        "debiased_squared_phase_lag_index" and "debiased_squared_weighted_phase_lag_index".
+
+        Returns ``SeedConnectivity(values, seeds, targets)``: ``values[name]`` has the shape [kept axes..., n_frequencies, n_seeds,
+        n_targets] and the dtype of the method of that name, and ``values[name][..., s, t]`` is what
+        ``getattr(self, name)()[..., seeds[s], targets[t]]`` returns: the cross-spectrum is x_seed conj(x_target), so the
+        antisymmetric measures have the sign of that entry, and where a seed is its own target the entry is the method's diagonal
+        (NaN for the coherency family, Im s forced to 0 for the phase-lag family); a coherence phase of a real negative
+        cross-spectrum is +pi or -pi as in the method (above or below the diagonal).  ValueError, before any device work, for an
+        unknown, empty or repeated measure, an empty list, an index that is out of range, not an integer or repeated, and too
+        many seeds.  The float32 engine's amplitude guard applies as for the methods (section 4.3.1 of DESIGN.md)."""
+        C = int(self._shape5[4])
+        seeds, targets, names, codes, planes = _lib.seed_request(seeds, targets, measures, C,
+                                                                 int(_lib.load().sc_seed_connectivity_max_seeds()))
+        sp = self._seed_spectra(planes & ~_lib.SEED_PLANE_POWER)
+        from . import _stage_d
+        mem = self._memory(sp.X)
+        outs = _stage_d.seed_connectivity(mem, sp, self.expectation_type, seeds, targets, planes, codes,
+                                          [self._wide_output(code) for code in codes], n_freq=self._n_freq,
+                                          reduce=self._reduce_over_ranks, n_observations=self._n_observations_total)
+        targets = np.arange(C, dtype=np.int32) if targets is None else targets
+        shape = self._kept_shape() + (self._n_freq, len(seeds), len(targets))
+        return SeedConnectivity({name: mem.download(out).reshape(shape) for name, out in zip(names, outs)}, seeds, targets)
+
+    def _seed_spectra(self, planes):
+        """The complex64 / complex128 spectra seed_connectivity reads: asked for without a planes hint (the kernel reads
+        coefficients; spectra already held as f16 pieces are decoded once), and their complex128 copy where (Im s)^2 or s / |s| of
+        this request would leave the float32 range (_guard_spectra, as _accumulators applies it)."""
+        return self._guard_spectra(self._device(), planes)
 
     def conditional_spectral_granger_prediction(self):
         """Power at node i explained by node j given every other signal, out[..., i, j] = j -> i | rest (diagonal NaN;

@@ -305,6 +305,15 @@ class Connectivity(_TorchHostConnectivity):
             self._spectra = self._decode_planes(sp)
         return super()._jackknife_phase_sums(mask, planes, over_id, n_units)
 
+    def _seed_spectra(self, planes):
+        if self._shape5[4] > 256:
+            raise ValueError("seed_connectivity of more than 256 signals needs device spectra of the whole array: use the PyTorch host "
+                             "(SC_HIP_HOST=torch)")
+        sp = self._device()
+        if getattr(sp, "P", None) is not None:          # (the kernel reads complex64: spectra held as f16 pieces are decoded once)
+            self._spectra = sp = self._decode_planes(sp)
+        return _stage_abc.amplitude_guard(host().memory, sp, planes)
+
     def _imaginary_interaction(self, group_labels):
         labels, members, sizes, _ = self._interaction_groups(group_labels)      # (the labels are checked before any device work)
         rec, n_obs, _ = self._csm_records("interaction", two_sided=False)
