@@ -855,6 +855,67 @@ int sc_seed_measure_f64(const double* d_record, int64_t n_bins, const int32_t* d
                         int64_t n_targets, uint32_t planes, int64_t n_observations, int n_measures, const int* measures,
                         const int* wide, void* const* d_outs, void* stream);
 
+/* ---- delete-one jackknife of seed-based connectivity (sc_seed_jackknife.hip; additive, ABI v8) ------------------------------
+ * The statistic of sc_jackknife_* and sc_jackknife_phase_* above -- units, `over`, unit range, d_u = theta(total - unit) -
+ * theta(total), the output triple (theta, sum_u d_u, sum_u d_u^2) -- for each of n_seeds signals against each of n_targets
+ * signals, with d_seeds, d_targets, the index rules and s = x_seed conj(x_target) of sc_seed_accumulate_*: n_seeds x n_targets
+ * entries per unit instead of C^2 / 2, no [n_bins][C][C] array.  One mask covers both families, on the scales given there:
+ *     SC_SEED_JACKKNIFE_COHERENCE_MAGNITUDE  theta = atanh(|S| / sqrt(P_seed P_target))           reads SC_PLANE_CSM | SC_SEED_PLANE_POWER
+ *     SC_SEED_JACKKNIFE_IMAGINARY_COHERENCE  theta = Im S / sqrt(P_seed P_target), signed         reads SC_PLANE_CSM | SC_SEED_PLANE_POWER
+ *     SC_SEED_JACKKNIFE_PLI                  theta = N / n                                        reads SC_PLANE_SIGN_IM
+ *     SC_SEED_JACKKNIFE_WPLI                 theta = (A / n) / w, w = B / n, 1 where w < 2^-52    reads SC_PLANE_CSM | _ABS_IM
+ *     SC_SEED_JACKKNIFE_DEBIASED_PLI2        theta = (n (N / n)^2 - 1) / (n - 1)                  reads SC_PLANE_SIGN_IM
+ *     SC_SEED_JACKKNIFE_DEBIASED_WPLI2       theta = (A^2 - Q) / (B^2 - Q), NaN where B^2 - Q == 0   reads SC_PLANE_CSM | _ABS_IM | _IM_SQ
+ * with S = sum s, A = Im S, B = sum |Im s|, N = sum sign(Im s), Q = sum (Im s)^2, P = sum |x|^2 and n = n_units_total g
+ * observations (n' = (n_units_total - 1) g in a delete-one set).  Unit sums are taken in the spectra's precision (the sign count
+ * is an integer); the subtraction, the statistic and the sums are fp64 on both engines.  The sums of d are taken about the first
+ * unit's deviation of a workgroup and moved back, so an entry whose units all have the same deviation has sum d^2 = (sum d)^2 / k
+ * exactly.  Where seed s IS target t the three outputs are NaN; a NaN d_u makes the entry's sums NaN; a signal without power
+ * gives NaN in the coherency pair.
+ *
+ * sc_seed_jackknife_totals_*: the totals from the spectra themselves, as a seed record of doubles (sc_seed_record_layout) with
+ * `planes` = a set of SC_PLANE_CSM, _ABS_IM, _IM_SQ, _SIGN_IM with at least one of them, and SC_SEED_PLANE_POWER (SC_PLANE_UNIT
+ * is refused): the same walk and the same unit sums as sc_seed_jackknife_*, added over the units [unit_begin, unit_end) in fp64,
+ * so a total is the sum of exactly the unit sums that are subtracted from it.  Written whole; records of trial shards add;
+ * sc_seed_measure_f64 reads it like any seed record.
+ *   d_total      such a record, summed over every rank's units; `planes` must hold what the requested measures read
+ *   d_out        double [sc_seed_jackknife_layout out_doubles]: for each requested measure in the order above three
+ *                double [n_bins][n_seeds][n_targets] arrays -- theta, sum_u d_u, sum_u d_u^2 over the units walked (partial
+ *                sums of different processes add; theta is the same in all of them)
+ *   d_workspace  sc_seed_jackknife_workspace_bytes / sc_seed_jackknife_totals_workspace_bytes, 16-byte aligned (0 where bins x
+ *                target tiles x seed chunks fill the device; otherwise the units are split over up to 256 workgroups of at least
+ *                16 units whose partial sums are added in split order: no floating-point atomics, bit-identical from run to run)
+ * SC_EINVAL (with sc_last_error) before any launch for everything sc_jackknife_phase_* and sc_seed_accumulate_* refuse -- a NULL
+ * argument, bad counts, an empty or unknown mask or plane set, a bad `over`, a kept trial axis under over = trials, fewer than two
+ * units, a unit range outside the spectra, a debiased measure whose delete-one sets hold fewer than two observations, a workspace
+ * that is too small or misaligned -- and for a total record that lacks a plane a requested measure reads. */
+#define SC_SEED_JACKKNIFE_COHERENCE_MAGNITUDE 0x1u
+#define SC_SEED_JACKKNIFE_IMAGINARY_COHERENCE 0x2u
+#define SC_SEED_JACKKNIFE_PLI 0x4u
+#define SC_SEED_JACKKNIFE_WPLI 0x8u
+#define SC_SEED_JACKKNIFE_DEBIASED_PLI2 0x10u
+#define SC_SEED_JACKKNIFE_DEBIASED_WPLI2 0x20u
+int sc_seed_jackknife_layout(const sc_spectra_desc* desc, int64_t n_seeds, int64_t n_targets, uint32_t measures, int over,
+                             int64_t* n_bins, int64_t* n_units, int64_t* unit_size, int64_t* out_doubles);
+int64_t sc_seed_jackknife_workspace_bytes(const sc_spectra_desc* desc, int64_t n_seeds, int64_t n_targets, uint32_t measures,
+                                          int over, int64_t unit_begin, int64_t unit_end);
+int64_t sc_seed_jackknife_totals_workspace_bytes(const sc_spectra_desc* desc, int64_t n_seeds, int64_t n_targets, uint32_t planes,
+                                                 int over, int64_t unit_begin, int64_t unit_end);
+int sc_seed_jackknife_totals_f32(const void* d_X /*float2*/, const sc_spectra_desc* desc, const int32_t* d_seeds, int64_t n_seeds,
+                                 const int32_t* d_targets, int64_t n_targets, uint32_t planes, int over, int64_t unit_begin,
+                                 int64_t unit_end, double* d_record, void* d_workspace, int64_t workspace_bytes, void* stream);
+int sc_seed_jackknife_totals_f64(const void* d_X /*double2*/, const sc_spectra_desc* desc, const int32_t* d_seeds, int64_t n_seeds,
+                                 const int32_t* d_targets, int64_t n_targets, uint32_t planes, int over, int64_t unit_begin,
+                                 int64_t unit_end, double* d_record, void* d_workspace, int64_t workspace_bytes, void* stream);
+int sc_seed_jackknife_f32(const void* d_X /*float2*/, const sc_spectra_desc* desc, const int32_t* d_seeds, int64_t n_seeds,
+                          const int32_t* d_targets, int64_t n_targets, const double* d_total, uint32_t planes, uint32_t measures,
+                          int over, int64_t unit_begin, int64_t unit_end, int64_t n_units_total, double* d_out, void* d_workspace,
+                          int64_t workspace_bytes, void* stream);
+int sc_seed_jackknife_f64(const void* d_X /*double2*/, const sc_spectra_desc* desc, const int32_t* d_seeds, int64_t n_seeds,
+                          const int32_t* d_targets, int64_t n_targets, const double* d_total, uint32_t planes, uint32_t measures,
+                          int over, int64_t unit_begin, int64_t unit_end, int64_t n_units_total, double* d_out, void* d_workspace,
+                          int64_t workspace_bytes, void* stream);
+
 /* ---- host-pointer side of the boundary: memory, copies, streams (sc_memory.hip, ABI v3) ---------------------
  * What the reference's CuPy backend does with `xp.asarray(time_series)` on the way in and `.get()` on the way out
  * (transforms.py:405-439, connectivity.py:31-65): with these a host that has only ctypes + NumPy drives the whole path

@@ -19,9 +19,9 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsc_hip.so")
 OBJ_DIR = os.path.join(os.path.dirname(HERE), "build", "obj")
 SOURCES = ["sc_api.hip", "sc_taper.hip", "sc_mtfft.hip", "sc_mtfft_long.hip", "sc_mtfft_mixed.hip", "sc_mtfft_f64.hip", "sc_csm.hip", "sc_nonlinear.hip", "sc_fused.hip", "sc_fused2.hip", "sc_measure.hip",
-           "sc_wilson.hip", "sc_wilson_fft.hip", "sc_wilson_pair.hip", "sc_mvar.hip", "sc_conditional.hip", "sc_blockwise.hip", "sc_global.hip", "sc_canonical.hip", "sc_partial.hip", "sc_dependence.hip", "sc_jackknife.hip", "sc_seed.hip", "sc_f64.hip",
+           "sc_wilson.hip", "sc_wilson_fft.hip", "sc_wilson_pair.hip", "sc_mvar.hip", "sc_conditional.hip", "sc_blockwise.hip", "sc_global.hip", "sc_canonical.hip", "sc_partial.hip", "sc_dependence.hip", "sc_jackknife.hip", "sc_seed.hip", "sc_seed_jackknife.hip", "sc_f64.hip",
            "sc_timing.hip", "sc_memory.hip", "sc_comm.hip"]
-HEADERS = ["sc_common.h", "sc_stage.h", "sc_fused_common.h", "sc_fused_plan.h", "sc_fused_split.h", "sc_jacobi.h", "sc_wilson_fft.h", "sc_wilson_loop.h", "sc_workspace.h", "sc_complex.h", "sc_measure_value.h", "sc_mtfft_bfly.h", os.path.join("..", "..", "include", "sc_hip.h")]
+HEADERS = ["sc_common.h", "sc_stage.h", "sc_fused_common.h", "sc_fused_plan.h", "sc_fused_split.h", "sc_jacobi.h", "sc_wilson_fft.h", "sc_wilson_loop.h", "sc_workspace.h", "sc_complex.h", "sc_measure_value.h", "sc_jackknife_value.h", "sc_seed_layout.h", "sc_mtfft_bfly.h", os.path.join("..", "..", "include", "sc_hip.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wno-unused-result", "-fno-slp-vectorize"]
 
 

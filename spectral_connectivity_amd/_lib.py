@@ -212,6 +212,18 @@ SYMBOLS = {
                                        c_void_p, c_int64, c_void_p]),
     "sc_seed_measure_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_uint32, c_int64, c_int,
                                     POINTER(c_int), POINTER(c_int), POINTER(c_void_p), c_void_p]),
+    "sc_seed_jackknife_layout": (c_int, [POINTER(SpectraDesc), c_int64, c_int64, c_uint32, c_int, c_int64_p, c_int64_p, c_int64_p,
+                                         c_int64_p]),
+    "sc_seed_jackknife_workspace_bytes": (c_int64, [POINTER(SpectraDesc), c_int64, c_int64, c_uint32, c_int, c_int64, c_int64]),
+    "sc_seed_jackknife_totals_workspace_bytes": (c_int64, [POINTER(SpectraDesc), c_int64, c_int64, c_uint32, c_int, c_int64, c_int64]),
+    "sc_seed_jackknife_totals_f32": (c_int, [c_void_p, POINTER(SpectraDesc), c_void_p, c_int64, c_void_p, c_int64, c_uint32, c_int,
+                                             c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "sc_seed_jackknife_totals_f64": (c_int, [c_void_p, POINTER(SpectraDesc), c_void_p, c_int64, c_void_p, c_int64, c_uint32, c_int,
+                                             c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "sc_seed_jackknife_f32": (c_int, [c_void_p, POINTER(SpectraDesc), c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_uint32,
+                                      c_uint32, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "sc_seed_jackknife_f64": (c_int, [c_void_p, POINTER(SpectraDesc), c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_uint32,
+                                      c_uint32, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     "sc_measure_f32": (c_int, [c_void_p, c_int64, c_int64, c_uint32, c_int64, c_int, c_void_p, c_void_p]),
     # host-pointer side (sc_memory.hip)
     "sc_device_alloc": (c_int, [POINTER(c_void_p), c_size_t, c_void_p]),
@@ -635,6 +647,43 @@ def seed_request(seeds, targets, measures, n_signals, max_seeds):
     for m in measures:
         planes |= SEED_MEASURES[m][1]
     return seeds, targets, measures, [SEED_MEASURES[m][0] for m in measures], planes
+
+
+# ---- delete-one jackknife of seed-based connectivity (sc_seed_jackknife.hip): the request, checked before any device work -----------
+# measure name -> (bit of the `measures` mask of sc_seed_jackknife_*, transform, planes of the total record it reads); dict order =
+# order of the blocks in the library's output: the pair measures of JACKKNIFE_MEASURES, then JACKKNIFE_PHASE_MEASURES
+SEED_JACKKNIFE_MEASURES = {
+    "coherence_magnitude": (0x1, "fisher_z", PLANE_CSM | SEED_PLANE_POWER),
+    "imaginary_coherence": (0x2, "identity", PLANE_CSM | SEED_PLANE_POWER),
+    "phase_lag_index": (0x4, "identity", PLANE_SIGN_IM),
+    "weighted_phase_lag_index": (0x8, "identity", PLANE_CSM | PLANE_ABS_IM),
+    "debiased_squared_phase_lag_index": (0x10, "identity", PLANE_SIGN_IM),
+    "debiased_squared_weighted_phase_lag_index": (0x20, "identity", PLANE_CSM | PLANE_ABS_IM | PLANE_IM_SQ),
+}
+
+
+def seed_jackknife_request(seeds, targets, measures, over, expectation_type, n_trials, n_observations, n_signals, max_seeds):
+    """(seeds int32, targets int32 or None for all signals in order, names in output order, sc_seed_jackknife_* mask, planes of the
+    total record, `over` code, n_units) of Connectivity.seed_jackknife: the index rules of seed_request and the rules of
+    jackknife_request / jackknife_phase_request, each checked by its own function.  ValueError for what they refuse, for "power"
+    (not a pair measure) and for a measure asked for twice."""
+    old, new = jackknife_split(measures)
+    if "power" in old:
+        raise ValueError("seed_jackknife: 'power' is not a measure of a (seed, target) pair; choose from "
+                         + ", ".join(repr(k) for k in SEED_JACKKNIFE_MEASURES) + " (Connectivity.jackknife has the power)")
+    if len(set(old + new)) != len(old + new):
+        raise ValueError(f"seed_jackknife: a measure is asked for twice ({list(old + new)})")
+    plans = [jackknife_request(old, over, expectation_type, n_trials, n_observations)] if old else []
+    if new:
+        plans.append(jackknife_phase_request(new, over, expectation_type, n_trials, n_observations))
+    seeds, targets = seed_request(seeds, targets, ("coherency",), n_signals, max_seeds)[:2]
+    asked = {k for plan in plans for k in plan[0]}
+    names = [k for k in SEED_JACKKNIFE_MEASURES if k in asked]
+    mask = planes = 0
+    for k in names:
+        mask |= SEED_JACKKNIFE_MEASURES[k][0]
+        planes |= SEED_JACKKNIFE_MEASURES[k][2]
+    return seeds, targets, names, mask, planes, plans[0][2], plans[0][3]
 
 
 def library_path():

@@ -412,3 +412,52 @@ def seed_connectivity(mem, spectra, expectation_type, seeds, targets, planes, me
                                        (ctypes.c_void_p * n)(*(mem.ptr(o).value for o in outs)), mem.stream()), "sc_seed_measure_f64")
     return outs
 
+
+
+def _seed_jackknife_setup(mem, spectra, expectation_type, seeds, targets, n_freq):
+    """(library, descriptor, n_seeds, n_targets, device seeds, device targets or None) of the two seed-jackknife drivers."""
+    d = spectra.desc(expectation_type, n_freq)
+    d_seeds = mem.upload(np.ascontiguousarray(seeds, dtype=np.int32))
+    d_targets = None if targets is None else mem.upload(np.ascontiguousarray(targets, dtype=np.int32))
+    return _lib._handle(), d, len(seeds), spectra.C if targets is None else len(targets), d_seeds, d_targets
+
+
+def seed_jackknife_totals(mem, spectra, expectation_type, seeds, targets, planes, over, n_freq=None, unit_range=None):
+    """The total record of seed_jackknife from the spectra themselves (sjk_kernel<TOTALS> of sc_seed_jackknife.hip): float64 device
+    array [n_bins, sc_seed_record_layout doubles] with the families ``planes`` (_lib.SEED_JACKKNIFE_MEASURES), the sums over the
+    units ``unit_range`` of these spectra (default: all) for ``seeds`` against ``targets`` (int32 arrays; None: every signal in
+    order); the records of trial shards add."""
+    lib, d, n_seeds, n_targets, d_seeds, d_targets = _seed_jackknife_setup(mem, spectra, expectation_type, seeds, targets, n_freq)
+    per_bin, n_bins, n_units = c_int64(), c_int64(), c_int64()
+    _lib.check(lib.sc_seed_record_layout(n_seeds, n_targets, planes, byref(per_bin)), "sc_seed_record_layout")
+    _lib.check(lib.sc_seed_jackknife_layout(byref(d), n_seeds, n_targets, 0x1, over, byref(n_bins), byref(n_units), None, None),
+               "sc_seed_jackknife_layout")
+    lo, hi = (0, n_units.value) if unit_range is None else unit_range
+    ws_bytes = int(lib.sc_seed_jackknife_totals_workspace_bytes(byref(d), n_seeds, n_targets, planes, over, lo, hi))
+    ws = mem.empty((ws_bytes,), np.uint8) if ws_bytes else None
+    record = mem.empty((n_bins.value, per_bin.value), np.float64)
+    fn = lib.sc_seed_jackknife_totals_f64 if spectra.f64 else lib.sc_seed_jackknife_totals_f32
+    _lib.check(fn(mem.ptr(spectra.X), byref(d), mem.ptr(d_seeds), n_seeds, _ptr(mem, d_targets), n_targets, planes, over, lo, hi,
+                  mem.ptr(record), _ptr(mem, ws), ws_bytes, mem.stream()), "sc_seed_jackknife_totals")
+    return record
+
+
+def seed_jackknife(mem, spectra, expectation_type, seeds, targets, total, planes, measures, over, n_units_total, n_freq=None,
+                   unit_range=None):
+    """Delete-one jackknife sums of seed-based connectivity (sjk_kernel of sc_seed_jackknife.hip): ONE walk over the complex64 /
+    complex128 spectra for every measure of the mask ``measures`` (_lib.SEED_JACKKNIFE_MEASURES) against the total record ``total``
+    of seed_jackknife_totals (any rank's sum) with the families ``planes``.  ``over``, ``n_units_total``, ``unit_range``: as for
+    ``jackknife``.  Returns (float64 device array: per measure of the mask, in table order, theta, sum d and sum d^2 as [n_bins,
+    n_seeds, n_targets] each; n_bins)."""
+    lib, d, n_seeds, n_targets, d_seeds, d_targets = _seed_jackknife_setup(mem, spectra, expectation_type, seeds, targets, n_freq)
+    n_bins, n_units, n_out = c_int64(), c_int64(), c_int64()
+    _lib.check(lib.sc_seed_jackknife_layout(byref(d), n_seeds, n_targets, measures, over, byref(n_bins), byref(n_units), None,
+                                            byref(n_out)), "sc_seed_jackknife_layout")
+    lo, hi = (0, n_units.value) if unit_range is None else unit_range
+    ws_bytes = int(lib.sc_seed_jackknife_workspace_bytes(byref(d), n_seeds, n_targets, measures, over, lo, hi))
+    ws = mem.empty((ws_bytes,), np.uint8) if ws_bytes else None
+    out = mem.empty((n_out.value,), np.float64)
+    fn = lib.sc_seed_jackknife_f64 if spectra.f64 else lib.sc_seed_jackknife_f32
+    _lib.check(fn(mem.ptr(spectra.X), byref(d), mem.ptr(d_seeds), n_seeds, _ptr(mem, d_targets), n_targets, mem.ptr(total), planes,
+                  measures, over, lo, hi, n_units_total, mem.ptr(out), _ptr(mem, ws), ws_bytes, mem.stream()), "sc_seed_jackknife")
+    return out, n_bins.value

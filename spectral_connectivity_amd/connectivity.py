@@ -38,6 +38,7 @@ InteractionVectors = namedtuple("InteractionVectors", ("mic", "filters", "patter
 CanonicalVectors = namedtuple("CanonicalVectors", ("coherence", "coherences", "filters", "patterns", "labels", "members"))
 LinearDependence = namedtuple("LinearDependence", ("total", "instantaneous", "lagged", "labels"))
 SeedConnectivity = namedtuple("SeedConnectivity", ("values", "seeds", "targets"))
+SeedJackknife = namedtuple("SeedJackknife", ("results", "seeds", "targets"))
 
 
 class _PendingSpectra:
@@ -1215,11 +1216,96 @@ class Connectivity:
         shape = self._kept_shape() + (self._n_freq, len(seeds), len(targets))
         return SeedConnectivity({name: mem.download(out).reshape(shape) for name, out in zip(names, outs)}, seeds, targets)
 
-    def _seed_spectra(self, planes):
-        """The complex64 / complex128 spectra seed_connectivity reads: asked for without a planes hint (the kernel reads
+    def _seed_spectra(self, planes, method="seed_connectivity"):
+        """The complex64 / complex128 spectra seed_connectivity and seed_jackknife (``method``: who asks, for a refusal's text) read: asked for without a planes hint (the kernel reads
         coefficients; spectra already held as f16 pieces are decoded once), and their complex128 copy where (Im s)^2 or s / |s| of
         this request would leave the float32 range (_guard_spectra, as _accumulators applies it)."""
         return self._guard_spectra(self._device(), planes)
+
+    # ---- delete-one jackknife of seed-based connectivity (sc_seed_jackknife.hip) -----------------------------------------------
+    def seed_jackknife(self, seeds, targets=None, measures=("coherence_magnitude",), over="trials"):
+        """Delete-one jackknife standard errors of a few signals against a list of signals -- cortico-muscular or seed-to-sensor
+        coherence with confidence limits (Chronux coherencyc with err = [2 p], FieldTrip's jackknife of ft_connectivity_wpli) --
+        without the all-pairs jackknife's three [n_frequencies, n_signals, n_signals] arrays per measure: n_seeds x n_targets
+        entries per delete unit instead of n_signals^2 / 2.
+
+        ``seeds``, ``targets``: the rules of ``seed_connectivity``.  ``over``: the rules of ``jackknife``.  ``measures``: a
+        non-empty subset, without repeats, of the six pair measures of ``jackknife`` on its scales -- "coherence_magnitude"
+        (Fisher z of |coherency|), "imaginary_coherence" (signed), "phase_lag_index", "weighted_phase_lag_index",
+        "debiased_squared_phase_lag_index", "debiased_squared_weighted_phase_lag_index" (identity); all of them come from ONE walk
+        over the spectra, against totals that one more walk sums from the same spectra in fp64 (kept for the next request with
+        the same seeds, targets and ``over``).
+
+        Returns ``SeedJackknife(results, seeds, targets)``: ``results[name]`` is a ``statistics.JackknifeResult`` whose
+        ``estimate``, ``bias_corrected`` and ``standard_error`` are float64 arrays [kept axes..., n_frequencies, n_seeds,
+        n_targets], ordered as ``jackknife`` orders them; entry [..., s, t] is what ``self.jackknife((name,), over)[name]`` has at
+        [..., seeds[s], targets[t]]: the cross-spectrum is x_seed conj(x_target), so the antisymmetric measures carry the sign of
+        that entry, and where a seed is its own target all three are NaN.  Off those entries ``estimate`` is
+        ``seed_connectivity``'s value of the same name on the statistic's scale (arctanh(sqrt(value)) for the coherence
+        magnitude).  The warnings are those of ``jackknife``, counted over these entries.  ValueError, before any device work,
+        for what ``seed_connectivity`` and ``jackknife`` refuse, for "power" and for a repeated measure."""
+        from .statistics import JackknifeResult, jackknife_finish
+        C = int(self._shape5[4])
+        seeds, targets, names, mask, planes, over_id, n_units = _lib.seed_jackknife_request(
+            seeds, targets, measures, over, self.expectation_type, self._jackknife_trials(), self.n_observations, C,
+            int(_lib.load().sc_seed_connectivity_max_seeds()))
+        if n_units == 2 and self.n_observations == 2 and "coherence_magnitude" in names:
+            logger.warning("jackknife: with two delete units of one observation each a leave-one-out estimate is a single observation, "
+                           "whose coherence magnitude is identically 1: the coherence_magnitude results are inf, NaN or rounding noise")
+        flat, n_bins = self._seed_jackknife_sums(seeds, targets, mask, planes, over_id, n_units)
+        all_targets = np.arange(C, dtype=np.int32) if targets is None else targets
+        shape = self._kept_shape() + (self._n_freq, len(seeds), len(all_targets))
+        size = n_bins * len(seeds) * len(all_targets)
+        own = seeds[:, None] == all_targets[None, :]                # a seed that is its own target: NaN by definition
+        results = {}
+        for k, name in enumerate(names):
+            theta, s1, s2 = (flat[(3 * k + j) * size:(3 * k + j + 1) * size].reshape(shape) for j in range(3))
+            results[name] = JackknifeResult(*jackknife_finish(theta, s1, s2, n_units), _lib.SEED_JACKKNIFE_MEASURES[name][1], n_units, over)
+        # one count per family, on its first measure, as jackknife does
+        first = next((k for k in names if k in _lib.JACKKNIFE_MEASURES), None)
+        if first is not None:
+            n_nan = int((np.isnan(results[first].estimate) & ~own).sum())
+            if n_nan:
+                logger.warning(f"jackknife: {n_nan} entries of {first} are NaN (a channel without power in a bin)")
+        first = next((k for k in names if k in _lib.JACKKNIFE_PHASE_MEASURES), None)
+        if first is not None:
+            nan = np.isnan(results[first].estimate) & ~own
+            if first == "debiased_squared_weighted_phase_lag_index" and self._device().real_input:
+                nan[..., 0, :, :] = False                            # (Im s = 0 in every observation of the zero and Nyquist bins
+                if self._shape5[3] % 2 == 0:                         # of a real series: NaN by the measure's definition)
+                    nan[..., -1, :, :] = False
+            if nan.any():
+                logger.warning(f"jackknife: {int(nan.sum())} entries of {first} are NaN (coefficients that are not finite, or a pair "
+                               "whose sum |Im s|^2 equals its sum (Im s)^2)")
+        return SeedJackknife(results, seeds, all_targets)
+
+    def _seed_jackknife_sums(self, seeds, targets, mask, planes, over_id, n_units):
+        """(the library's output as a flat float64 NumPy array: theta, sum d, sum d^2 per measure of the mask; n_bins).  The spectra
+        are those ``seed_connectivity`` reads (_seed_spectra: no planes hint, the amplitude guard for requests that read (Im s)^2).
+        The total is a seed record of doubles that the jackknife sums from these spectra itself (_stage_d.seed_jackknife_totals),
+        summed over every rank's trials and cached; a later request with the same seeds, targets, ``over`` and spectra that needs
+        no other plane reads it again."""
+        from . import _stage_d
+        sp = self._seed_spectra(planes & ~_lib.SEED_PLANE_POWER, "seed_jackknife")
+        mem = self._memory(sp.X)
+        who = (seeds.tobytes(), None if targets is None else targets.tobytes(), over_id, bool(sp.f64))
+        mine = [k for k in self._accum_cache if isinstance(k, tuple) and k[0] == "seed_jackknife" and k[2:] == who]
+        have = next((k for k in mine if k[1] & planes == planes), None)
+        if have is None:
+            total = _stage_d.seed_jackknife_totals(mem, sp, self.expectation_type, seeds, targets, planes, over_id, n_freq=self._n_freq)
+            for old in [k for k in mine if k[1] & planes == k[1]]:
+                del self._accum_cache[old]             # a record the new one covers: its memory can go
+            have = ("seed_jackknife", planes) + who
+            self._accum_cache[have] = (self._reduce_over_ranks(total), None)
+        out, n_bins = _stage_d.seed_jackknife(mem, sp, self.expectation_type, seeds, targets, self._accum_cache[have][0], have[1], mask,
+                                              over_id, n_units, n_freq=self._n_freq)
+        n_targets = int(self._shape5[4]) if targets is None else len(targets)
+        return mem.download(self._seed_jackknife_reduce(out, n_bins * len(seeds) * n_targets)), n_bins
+
+    def _seed_jackknife_reduce(self, out, size):
+        """Sum of the partial sums over the processes that hold the trials (nothing to add here).  ``size``: doubles of one of the
+        three arrays -- theta, sum d, sum d^2 -- of every measure in ``out``."""
+        return out
 
     def conditional_spectral_granger_prediction(self):
         """Power at node i explained by node j given every other signal, out[..., i, j] = j -> i | rest (diagonal NaN;

@@ -29,9 +29,7 @@
 // in fp64.  Both kernels run the one walk and the one JkPhaseUnit, so a total is by construction the fp64 sum of the very unit
 // sums that are subtracted from it.  It is what the hosts hand in, because the float32 engine's own records are too coarse in A
 // for the debiased wPLI^2 of a pair near 0.
-#include "sc_common.h"
-
-#include <math.h>
+#include "sc_jackknife_value.h"
 
 namespace {
 
@@ -84,9 +82,7 @@ __device__ __forceinline__ JkPlace jk_place(const JkGeom& p) {
 }
 
 __device__ __forceinline__ int64_t jk_row_offset(const JkGeom& p, int64_t u, int q) {
-    if (p.over == SC_JACKKNIFE_OVER_OBSERVATIONS) return sc_obs_offset(p.a, (int)u);
-    const int w = q / p.q_tapers, k = q - w * p.q_tapers;
-    return (int64_t)w * p.a.sW + u * p.a.sR + (int64_t)k * p.a.sK;
+    return jk_unit_row_offset(p.a, p.over, p.q_tapers, u, q);
 }
 
 // The units of this workgroup's split, row by row: row(xi, xj) for every observation (the two entries of either channel tile
@@ -220,14 +216,13 @@ __global__ __launch_bounds__(256) void jk_kernel(const T2* __restrict__ X, JkArg
                         const double re = Sre[a][b] - (double)Gre[a][b], im = Sim[a][b] - (double)Gim[a][b];
                         const double rr = ri[a] * rj[b];
                         if (want_coh) {
-                            // atanh(x) - atanh(y) = atanh((x - y) / (1 - x y)): no difference of two nearly equal transcendentals
                             const double mag = sqrt(re * re + im * im) * rr;
-                            const double d = atanh((mag - bcoh[a][b]) / (1.0 - mag * bcoh[a][b]));
+                            const double d = jk_fisher_deviation(mag, bcoh[a][b]);
                             coh1[a][b] += d;
                             coh2[a][b] += d * d;
                         }
                         if (want_im) {
-                            const double d = im * rr - bim[a][b];
+                            const double d = jk_imaginary_deviation(im, rr, bim[a][b]);
                             im1[a][b] += d;
                             im2[a][b] += d * d;
                         }
@@ -338,27 +333,7 @@ struct JkPhaseUnit {
     }
 };
 
-// the four statistics from the sums (A, B, N, Q) of n observations; sc_measure.hip's formulas on the identity scale
-__device__ __forceinline__ double jk_pli(double N, double n) { return N / n; }
-__device__ __forceinline__ double jk_debiased_pli2(double pli, double n) { return (n * pli * pli - 1.0) / (n - 1.0); }
-__device__ __forceinline__ double jk_wpli(double A, double B, double n) {
-    double w = B / n;
-    if (w < 2.220446049250313e-16) w = 1.0;
-    return (A / n) / w;
-}
-__device__ __forceinline__ double jk_debiased_wpli2(double A, double B, double Q) {
-    const double den = B * B - Q;
-    return den == 0.0 ? __builtin_nan("") : (A * A - Q) / den;
-}
-
-// one deviation into the two sums about the pivot (the first unit's deviation; see jk_phase_kernel)
-__device__ __forceinline__ void jk_shifted_add(double d, bool first, double& piv, double& s1, double& s2) {
-    if (first) piv = d;
-    const double e = d - piv;
-    s1 += e;
-    s2 += e * e;
-}
-
+// (the four statistics from the sums, the shifted sums and their move back to the origin: sc_jackknife_value.h)
 template <typename T, typename T2>
 __global__ __launch_bounds__(256) void jk_phase_kernel(const T2* __restrict__ X, JkPhaseArgs p) {
     const JkPlace w = jk_place(p.geo);
@@ -437,11 +412,8 @@ __global__ __launch_bounds__(256) void jk_phase_kernel(const T2* __restrict__ X,
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const double r = piv[m][a][b], t1 = s1[m][a][b], t2 = s2[m][a][b];
-                s1[m][a][b] = (double)n_done * r + t1;
-                s2[m][a][b] = r * s1[m][a][b] + (t2 + r * t1);
-            }
+            for (int b = 0; b < 2; ++b)
+                jk_shifted_finish(n_done, piv[m][a][b], s1[m][a][b], s2[m][a][b]);
 
     double* out = p.geo.out + (int64_t)blockIdx.y * p.geo.out_doubles;
     const int64_t CC = (int64_t)C * C, plane2 = p.geo.n_bins * CC;
@@ -593,13 +565,7 @@ JkFold jk_fold_blocks(const JkPlan& pl, bool phase) {
 
 // units per split and number of splits: only when bins x tile pairs leave compute units idle, and never fewer than 16 units each
 void jk_splits(const JkPlan& pl, int64_t n_local, int64_t* per, int64_t* n_splits) {
-    const int64_t base = pl.n_bins * pl.n_tp;
-    int64_t want = base >= 1024 ? 1 : (2048 + base - 1) / base;
-    const int64_t by_units = n_local / 16 > 1 ? n_local / 16 : 1;
-    if (want > by_units) want = by_units;
-    if (want > JK_MAX_SPLITS) want = JK_MAX_SPLITS;
-    *per = (n_local + want - 1) / want;
-    *n_splits = (n_local + *per - 1) / *per;
+    jk_unit_splits(pl.n_bins * pl.n_tp, n_local, JK_MAX_SPLITS, per, n_splits);
 }
 
 // bytes the splits of a unit range need for their partial sums (0: one split, no workspace; 0 too where the plan failed)

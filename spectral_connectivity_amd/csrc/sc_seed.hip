@@ -23,48 +23,18 @@
 // (sc_measure_value.h): the formulas, the eps floors, the n_obs-dependent debiasing and -- where a seed is its own target -- what
 // each measure puts on its diagonal.
 #include "sc_measure_value.h"
+#include "sc_seed_layout.h"
 #include "sc_workspace.h"
 
 namespace {
 
-constexpr int SEED_TILE = 64;                       // targets of a workgroup: one per lane
 constexpr int SEED_ROWS = 32;                       // observation rows per staging block
 constexpr int SEED_WAVES = 4;
 constexpr int SEED_RPW = SEED_ROWS / SEED_WAVES;    // rows of a block a wave walks: its loads in flight
-constexpr int SEED_CHUNK = 4;                       // seeds of a workgroup (7 sums each in a thread's registers)
-constexpr int SEED_MAX = 64;
 constexpr int SEED_MAX_SPLITS = 256;
 constexpr int SEED_MAX_MEASURES = 10;
-constexpr uint32_t SEED_PLANES_ALL = SC_PLANE_CSM | SC_PLANE_ABS_IM | SC_PLANE_IM_SQ | SC_PLANE_SIGN_IM | SC_PLANE_UNIT | SC_SEED_PLANE_POWER;
 
-// where the sums of a record are: planes (in [n_seeds][n_targets] blocks from the start of a bin) or -1, the powers (in doubles) or -1
-struct SeedLayout {
-    int p_csm, p_abs, p_sq, p_sign, p_unit;
-    int64_t pow_off, per_bin;
-};
-
-SeedLayout seed_layout(int n_seeds, int n_targets, uint32_t planes) {
-    SeedLayout l;
-    const uint32_t acc = planes & ~SC_SEED_PLANE_POWER;
-    l.p_csm = (planes & SC_PLANE_CSM) ? sc_plane_offset(acc, SC_PLANE_CSM) : -1;
-    l.p_abs = (planes & SC_PLANE_ABS_IM) ? sc_plane_offset(acc, SC_PLANE_ABS_IM) : -1;
-    l.p_sq = (planes & SC_PLANE_IM_SQ) ? sc_plane_offset(acc, SC_PLANE_IM_SQ) : -1;
-    l.p_sign = (planes & SC_PLANE_SIGN_IM) ? sc_plane_offset(acc, SC_PLANE_SIGN_IM) : -1;
-    l.p_unit = (planes & SC_PLANE_UNIT) ? sc_plane_offset(acc, SC_PLANE_UNIT) : -1;
-    const int64_t cells = (int64_t)sc_plane_count(acc) * n_seeds * n_targets;
-    l.pow_off = (planes & SC_SEED_PLANE_POWER) ? cells : -1;
-    l.per_bin = cells + ((planes & SC_SEED_PLANE_POWER) ? n_seeds + n_targets : 0);
-    return l;
-}
-
-int seed_check_counts(int64_t n_seeds, int64_t n_targets, uint32_t planes) {
-    SC_REQUIRE(n_seeds >= 1 && n_seeds <= SEED_MAX, "n_seeds: 1 ... sc_seed_connectivity_max_seeds()");
-    SC_REQUIRE(n_targets >= 1 && n_targets <= 32768, "n_targets: 1 ... 32768");
-    SC_REQUIRE(planes && !(planes & ~SEED_PLANES_ALL) && (planes & ~SC_SEED_PLANE_POWER),
-               "planes: a set of SC_PLANE_CSM, _ABS_IM, _IM_SQ, _SIGN_IM, _UNIT with at least one of them, and SC_SEED_PLANE_POWER");
-    return SC_OK;
-}
-
+// (the record's layout and the checks of the counts and planes: sc_seed_layout.h; 7 sums per seed of a chunk in a thread's registers)
 struct SeedArgs {
     ScAxes a;
     const int32_t* seeds;

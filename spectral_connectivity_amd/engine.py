@@ -570,6 +570,20 @@ def jackknife_phase_totals(spectra, expectation_type, planes, over, n_freq=None,
     return _stage_d.jackknife_phase_totals(TorchMemory(spectra.device), spectra, expectation_type, planes, over, n_freq, unit_range)
 
 
+def seed_jackknife_totals(spectra, expectation_type, seeds, targets, planes, over, n_freq=None, unit_range=None):
+    """The float64 total seed record of seed_jackknife from the spectra themselves: _stage_d.seed_jackknife_totals."""
+    return _stage_d.seed_jackknife_totals(TorchMemory(spectra.device), spectra, expectation_type, seeds, targets, planes, over, n_freq,
+                                          unit_range)
+
+
+def seed_jackknife(spectra, expectation_type, seeds, targets, total, planes, measures, over, n_units_total, n_freq=None,
+                   unit_range=None):
+    """Delete-one jackknife sums of ``seeds`` against ``targets`` (sc_seed_jackknife.hip) against the total seed record ``total`` with
+    the families ``planes``: _stage_d.seed_jackknife."""
+    return _stage_d.seed_jackknife(TorchMemory(spectra.device), spectra, expectation_type, seeds, targets, total, planes, measures,
+                                   over, n_units_total, n_freq, unit_range)
+
+
 class GraphedMeasures:
     """Stage A, stage B and the epilogue of ONE fixed request, captured once in a hipGraph and replayed per time series.
 

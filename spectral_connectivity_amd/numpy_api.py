@@ -305,9 +305,9 @@ class Connectivity(_TorchHostConnectivity):
             self._spectra = self._decode_planes(sp)
         return super()._jackknife_phase_sums(mask, planes, over_id, n_units)
 
-    def _seed_spectra(self, planes):
+    def _seed_spectra(self, planes, method="seed_connectivity"):
         if self._shape5[4] > 256:
-            raise ValueError("seed_connectivity of more than 256 signals needs device spectra of the whole array: use the PyTorch host "
+            raise ValueError(f"{method} of more than 256 signals needs device spectra of the whole array: use the PyTorch host "
                              "(SC_HIP_HOST=torch)")
         sp = self._device()
         if getattr(sp, "P", None) is not None:          # (the kernel reads complex64: spectra held as f16 pieces are decoded once)

@@ -591,6 +591,17 @@ class ShardedConnectivity(_connectivity_base()):
             pos += 2 * size
         return out
 
+    def _seed_jackknife_reduce(self, out, size):
+        """_jackknife_reduce for seed_jackknife, whose every measure is three arrays of ``size`` doubles: one sum over ranks of the
+        stacked sum d and sum d^2 (theta is the same on every rank; the totals went through _reduce_over_ranks)."""
+        if _no_exchange(self._group):
+            return out
+        blocks = out.view(-1, 3, size)
+        sums = blocks[:, 1:].contiguous()
+        all_reduce_sum_(sums, self._group)
+        blocks[:, 1:] = sums
+        return out
+
     def _canonical_bins(self, n_bins):
         """The bins this rank evaluates: a contiguous 1/N, padded so that every rank holds the same count."""
         per = padded_bins(n_bins, self._world) // self._world

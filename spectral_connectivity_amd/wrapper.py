@@ -42,7 +42,7 @@ _NOT_IN_DATASET = {
     "blockwise_spectral_granger_prediction", "conditional_spectral_granger_prediction",
     "maximized_imaginary_coherence", "multivariate_interaction_measure", "maximized_imaginary_coherence_vectors", "jackknife",
     "canonical_coherence_vectors", "partial_coherency", "partial_coherence_magnitude", "multiple_coherence_magnitude", "linear_dependence", "lagged_coherence",
-    "seed_connectivity",
+    "seed_connectivity", "seed_jackknife",
 }
 _PARTIAL = ("partial_coherency", "partial_coherence_magnitude", "multiple_coherence_magnitude")
 _MT_SKIP = {"time_series", "fft", "tapers", "frequencies", "time"}
@@ -62,7 +62,7 @@ def _xarray():
 def _check_method(method):
     if method in ("group_delay", "canonical_coherence", "blockwise_spectral_granger_prediction", "maximized_imaginary_coherence",
                   "multivariate_interaction_measure", "maximized_imaginary_coherence_vectors", "jackknife", "linear_dependence",
-                  "canonical_coherence_vectors", "seed_connectivity") or "directed" in method:
+                  "canonical_coherence_vectors", "seed_connectivity", "seed_jackknife") or "directed" in method:
         raise ValueError(
             f"The method '{method}' is not supported by the xarray interface. "
             f"Please use the Connectivity class directly instead:\n\n"
